@@ -8,7 +8,15 @@ as the reference, zlib-compatible deflate).  A step = plan the 4096 requests on 
 (TileRequestHandler validation + descriptors) + descriptor upload + every kernel, outputs
 left in HBM.  Inputs are resident before the timed region; D2H is reported separately.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`,
+`ms_per_step`, ...).  `--dump-outputs DIR` then writes what the last timed step computed
+(see dump_outputs); the inputs are the same from run to run, so two builds can be compared
+output for output.  `--full` adds everything that takes runs of its own: the serial pass
+(per-kernel and roofline figures), the secondary lines (the other BASELINE configs, the
+served path, Zarr, filters; `--no-extra` leaves them out) and the CPU baseline
+(`--no-cpu-baseline` leaves it out).
 
 One rank per GPU.  Under torch.distributed.run (WORLD_SIZE set) this process is one rank.
 Otherwise `--gpus N` with N > 1 makes this process a launcher that touches no GPU: it
@@ -56,14 +64,16 @@ class StepStats:
             setattr(self, f, sum(getattr(p, f) for p in parts))
 
 
-def run_steps(svc, ctxs, steps, warmup, barrier, sub=0):
+def run_steps(svc, ctxs, steps, warmup, barrier, sub=0, keep=None):
     """Warmup, then `steps` timed steps; returns (seconds, per-step stats, mean host ms).
 
     Steps are pipelined PIPE_DEPTH deep, as a server feeds its GPU: the host plans and
     launches batch k+1 (request validation, descriptors, upload) while earlier batches run,
     then waits for the oldest one (its own completion event).  The request arrays are built
     once.  sub > 0: a step's requests go as batches of `sub` tiles (PIPE_DEPTH steps' worth
-    in flight); its stats are their sums."""
+    in flight); its stats are their sums.  keep: a list that receives the batches of the
+    last timed step, synced and still open (their outputs in HBM), for the caller to fetch
+    and close."""
     parts = [ctxs] if sub <= 0 else [ctxs[i:i + sub] for i in range(0, len(ctxs), sub)]
     reqs = [pbx.make_reqs(p) for p in parts]
     depth = PIPE_DEPTH * len(parts)
@@ -73,6 +83,7 @@ def run_steps(svc, ctxs, steps, warmup, barrier, sub=0):
         host = 0.0
         out = []
         acc = []
+        retired = [0]
 
         def retire():
             b = q.pop(0)
@@ -82,7 +93,11 @@ def run_steps(svc, ctxs, steps, warmup, barrier, sub=0):
                 if len(acc) == len(parts):
                     out.append(acc[0] if len(parts) == 1 else StepStats(acc))
                     acc.clear()
-            b.close()
+            retired[0] += 1
+            if record and keep is not None and retired[0] > (n - 1) * len(parts):
+                keep.append(b)
+            else:
+                b.close()
 
         for _ in range(n):
             for r in reqs:
@@ -111,6 +126,42 @@ def run_steps(svc, ctxs, steps, warmup, barrier, sub=0):
 
 def mean(stats, field):
     return sum(getattr(s, field) for s in stats) / len(stats)
+
+
+DUMP_SEED, DUMP_TILES, DUMP_BODY_BYTES = 20240, 32, 48 << 20
+
+
+def dump_outputs(dirname, batches):
+    """--dump-outputs: what a caller of the timed path receives from its last timed step,
+    fetched from HBM (pbx_batch_fetch) and written as float64 / float32 .npy files:
+
+      status.npy   [n]     pbx status of every tile of the step, in request order
+      nbytes.npy   [n]     length of every response body (the PNG file)
+      crc32.npy    [n]     zlib.crc32 of every response body
+      sample_index.npy [k] the tiles whose bodies are stored: a fixed seeded choice
+      sample_body.npy [k, m] their bytes, one row per tile, zero-padded to the longest
+
+    The bodies of all tiles (1.6 GB) would not fit the 64 MB a dump may take, so every body
+    is pinned by its length and CRC and k of them are stored whole."""
+    import zlib
+    import numpy as np
+    res = [r for b in batches for r in b.fetch()]
+    n = len(res)
+    body = [b if b is not None else b"" for _, b in res]
+    order = np.random.RandomState(DUMP_SEED).permutation(n)
+    longest = max(map(len, body))
+    k = max(1, min(n, DUMP_TILES, DUMP_BODY_BYTES // (4 * max(longest, 1))))
+    idx = np.sort(order[:k])
+    sample = np.zeros((k, max(len(body[i]) for i in idx)), np.float32)
+    for row, i in enumerate(idx):
+        sample[row, :len(body[i])] = np.frombuffer(body[i], np.uint8)
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in (("status", np.array([s for s, _ in res], np.float64)),
+                      ("nbytes", np.array([len(b) for b in body], np.float64)),
+                      ("crc32", np.array([zlib.crc32(b) for b in body], np.float64)),
+                      ("sample_index", idx.astype(np.float64)),
+                      ("sample_body", sample)):
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 def secondary_steps(svc, ctxs, steps, warmup, barrier):
@@ -916,12 +967,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the serial pass (per-kernel and roofline figures), the "
+                         "secondary lines and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: no secondary lines")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--dry-run", action="store_true",
                     help="rank plumbing only (launch, barrier, max), no HIP call")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -947,7 +1005,12 @@ def main():
     svc.register_plane(iid, 0, 0, 0, pbx.UINT16, side, side, generator="noise", seed=0,
                        plane_no=rank)
     ctxs = grid_ctxs(iid, "png")
-    dt, stats, host_ms = run_steps(svc, ctxs, args.steps, args.warmup, barrier, HEADLINE_SUB)
+    last = [] if args.dump_outputs and rank == 0 else None
+    dt, stats, host_ms = run_steps(svc, ctxs, args.steps, args.warmup, barrier, HEADLINE_SUB, last)
+    if last:
+        dump_outputs(args.dump_outputs, last)
+        for b in last:
+            b.close()
     t = torch.tensor([dt], dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -956,6 +1019,41 @@ def main():
     value = tiles_total / dt
     ms_per_step = 1000.0 * dt / args.steps
     st = stats[-1]
+    out = {
+        "metric": METRIC, "value": round(value, 1), "unit": "tiles/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+        "data": "synthetic (G_NOISE seed 0 plane generated in HBM)",
+        "config": {"workload": "4096 x 512x512 uint16 tiles -> PNG per GPU from a 32768^2 "
+                               "uint16 plane (BASELINE configs[1] shape, metric's PNG format)",
+                   "tiles_per_gpu": len(ctxs), "tile": "512x512", "pixel_type": "uint16",
+                   "format": "png", "png_filter": "none (reference APNGWriter)",
+                   "parallelism": f"dp{world} (request sharding, no collectives)",
+                   "batches_per_step": 1 if HEADLINE_SUB <= 0 else -(-len(ctxs) // HEADLINE_SUB)},
+        "hbm_gbps_step": round((st.in_bytes + st.deflate_out_bytes) * world * args.steps / dt / 1e9, 1),
+        "compressed_bytes_per_tile": round(st.deflate_out_bytes / len(ctxs), 1),
+        "host_ms_per_step": round(host_ms, 3),
+    }
+    # A plain run ends here: set up, warm up, time the steps, print the line.  --full adds
+    # everything that takes runs of its own.
+    if args.full:
+        out.update(serial_pass_lines(svc, ctxs, args.steps, barrier, st, ms_per_step))
+        if not args.no_extra:
+            extra(out, svc, rank, world, barrier, iid, side)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            progress(rank, "cpu baseline")
+            out["cpu_baseline"] = cpu_baseline(threads=args.cpu_threads)
+            out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    svc.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def serial_pass_lines(svc, ctxs, steps, barrier, st, ms_per_step):
+    """--full: the per-kernel, roofline and deflate-chain figures of the headline batch, from
+    a serial pass of its own.  `st`: the stats of the timed pass's last step."""
     # The timed pass overlaps consecutive batches on the library's kernel streams (default
     # 3, each batch's k_lz77 staggered behind the previous one's: pbx_set_kernel_streams),
     # which stretches each kernel's HIP-event duration over the others.  Per-kernel
@@ -963,9 +1061,9 @@ def main():
     # launch order), the configuration the committed rocprofv3 kernel trace uses
     # (PBX_KSTREAMS=1); its tiles/s is reported beside the headline.
     svc.set_kernel_streams(1, 0)
-    dts, stats, _ = run_steps(svc, ctxs, args.steps, 1, barrier, HEADLINE_SUB)
+    dts, stats, _ = run_steps(svc, ctxs, steps, 1, barrier, HEADLINE_SUB)
     svc.set_kernel_streams(KSTREAMS, KSTAGGER)
-    serial_rate = len(ctxs) * args.steps / dts
+    serial_rate = len(ctxs) * steps / dts
 
     # Per-kernel algorithmic bytes per launch over the kernel's mean
     # HIP-event duration on the library's stream:
@@ -1000,17 +1098,7 @@ def main():
     e2e_bytes = st.in_bytes + st.deflate_out_bytes
     chain_traffic, chain_src = load_chain_traffic()
     rp_ms, rp_src = load_rocprof_ms(dom)
-    out = {
-        "metric": METRIC, "value": round(value, 1), "unit": "tiles/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-        "data": "synthetic (G_NOISE seed 0 plane generated in HBM)",
-        "config": {"workload": "4096 x 512x512 uint16 tiles -> PNG per GPU from a 32768^2 "
-                               "uint16 plane (BASELINE configs[1] shape, metric's PNG format)",
-                   "tiles_per_gpu": len(ctxs), "tile": "512x512", "pixel_type": "uint16",
-                   "format": "png", "png_filter": "none (reference APNGWriter)",
-                   "parallelism": f"dp{world} (request sharding, no collectives)",
-                   "batches_per_step": 1 if HEADLINE_SUB <= 0 else -(-len(ctxs) // HEADLINE_SUB)},
+    return {
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
                      "traffic": traffic, "traffic_source": traffic_src,
@@ -1035,26 +1123,10 @@ def main():
                      "issue": load_issue()},
         "kernels": kernels,
         "deflate_chain_ms": round(chain_ms, 3),
-        "hbm_gbps_step": round((st.in_bytes + st.deflate_out_bytes) * world * args.steps / dt / 1e9, 1),
-        "compressed_bytes_per_tile": round(st.deflate_out_bytes / len(ctxs), 1),
-        "host_ms_per_step": round(host_ms, 3),
         "kernel_streams": {"timed_pass": KSTREAMS, "stagger": "k_lz77",
                            "serial_pass_tiles_per_s": round(serial_rate, 1),
                            "note": "kernels/roofline/deflate_chain_ms from the serial pass"},
     }
-
-    if not args.no_extra:
-        extra(out, svc, rank, world, barrier, iid, side)
-
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        progress(rank, "cpu baseline")
-        out["cpu_baseline"] = cpu_baseline(threads=args.cpu_threads)
-        out["speedup_vs_cpu_baseline"] = round(value / out["cpu_baseline"]["value"], 1)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    svc.close()
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -13,8 +13,8 @@ tail -1 $O/t.log
 for i in 1 2; do for L in omero-ms-pixel-buffer_amd/lib/libpbx.so var/libpbx_head.so; do
   PBX_LIB=$PWD/$L timeout -k 10 200 python -u scripts/filter_bench.py 5 > $O/f.log 2>&1 || { tail -20 $O/f.log; exit 1; }
   echo "$L $(grep adaptive $O/f.log)"
-  PBX_LIB=$PWD/$L timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-extra > $O/h.log 2>&1 || { tail -20 $O/h.log; exit 1; }
+  PBX_LIB=$PWD/$L timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-extra > $O/h.log 2>&1 || { tail -20 $O/h.log; exit 1; }
   echo "$L $(tail -1 $O/h.log | cut -c1-160)"
 done; done
-timeout -k 10 600 python -u bench.py --no-cpu-baseline > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full --no-cpu-baseline > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
 tail -1 $O/bench.log > $O/bench.json

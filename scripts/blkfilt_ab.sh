@@ -6,6 +6,6 @@ O=gpurun_out/$1
 mkdir -p $O
 for L in lib/libpbx.so ${AB_LIBS:-lib/var_bf6/libpbx.so lib/var_bf11/libpbx.so}; do
   n=$(echo $L | tr / _)
-  PBX_LIB=$PWD/omero-ms-pixel-buffer_amd/$L timeout -k 10 600 python -u bench.py --no-cpu-baseline > $O/b_$n.json 2> $O/b_$n.err || { tail -20 $O/b_$n.err; exit 1; }
+  PBX_LIB=$PWD/omero-ms-pixel-buffer_amd/$L timeout -k 10 600 python -u bench.py --full --no-cpu-baseline > $O/b_$n.json 2> $O/b_$n.err || { tail -20 $O/b_$n.err; exit 1; }
   echo "$L done"
 done

@@ -54,12 +54,12 @@ for stage in "$@"; do
         done
       done ;;
     rehearse)  # the N-rank bench path with both ranks on the box's one GPU (PBX_BENCH_ONE_GPU)
-      PBX_BENCH_ONE_GPU=1 timeout -k 10 900 python -u bench.py --gpus 2 --steps 5 --warmup 2 > $O/rehearse.json 2> $O/rehearse.err || { tail -30 $O/rehearse.err; exit 1; }
+      PBX_BENCH_ONE_GPU=1 timeout -k 10 900 python -u bench.py --full --gpus 2 --steps 5 --warmup 2 > $O/rehearse.json 2> $O/rehearse.err || { tail -30 $O/rehearse.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/rehearse.json')); print(d['n_gpus'], d['value'], sorted(k for k in d if isinstance(d[k], dict))[:40])" ;;
     knobs)  # the headline under other pipelining settings (streams / stagger / depth / sub-batches)
       for kv in "3 1 2 0" "3 1 3 0" "2 1 2 0" "4 1 3 0" "3 2 2 0" "3 0 2 0" "3 1 2 1024" "3 1 4 1024" "4 1 8 512"; do
         set -- $kv
-        PBX_KSTREAMS=$1 PBX_KSTAGGER=$2 PBX_BENCH_DEPTH=$3 PBX_BENCH_SUB=$4 timeout -k 10 200 python -u bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $O/knob.json 2> $O/knob.err || { tail -20 $O/knob.err; exit 1; }
+        PBX_KSTREAMS=$1 PBX_KSTAGGER=$2 PBX_BENCH_DEPTH=$3 PBX_BENCH_SUB=$4 timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $O/knob.json 2> $O/knob.err || { tail -20 $O/knob.err; exit 1; }
         python3 -c "import json; d=json.load(open('$O/knob.json')); print('streams $1 stagger $2 depth $3 sub $4:', d['value'], d['ms_per_step'])"
       done ;;
     probe3)
@@ -100,13 +100,13 @@ for stage in "$@"; do
         tests/test_gpu_lz77.py tests/test_gpu_huffman.py > $O/pytest_parity.log 2>&1 || { grep -E "FAILED|^E " $O/pytest_parity.log | head -30; tail -5 $O/pytest_parity.log; exit 1; }
       tail -1 $O/pytest_parity.log ;;
     kstats)  # the rocprofv3 kernel averages of a short serial-pass headline run
-      PBX_KSTREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kprof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 2 --no-extra --no-cpu-baseline > $O/kprof_bench.json 2> $O/kprof_bench.err || { tail -20 $O/kprof_bench.err; exit 1; }
+      PBX_KSTREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kprof -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 2 --no-extra --no-cpu-baseline > $O/kprof_bench.json 2> $O/kprof_bench.err || { tail -20 $O/kprof_bench.err; exit 1; }
       find $O/kprof -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_short.csv \;
       cut -d, -f1-4 $O/kernel_stats_short.csv | head -12 ;;
     bench)
-      timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+      timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
       python3 -c "import json; d=json.load(open('$O/bench.json')); print(d['value'], d['ms_per_step'], d['deflate_chain_ms'], d['roofline']['frac'])"
-      PBX_KSTREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --steps 10 --warmup 2 --no-extra --no-cpu-baseline > $O/prof_bench.json 2> $O/prof_bench.err || { tail -20 $O/prof_bench.err; exit 1; }
+      PBX_KSTREAMS=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof -o run --output-format csv -- python3 bench.py --full --steps 10 --warmup 2 --no-extra --no-cpu-baseline > $O/prof_bench.json 2> $O/prof_bench.err || { tail -20 $O/prof_bench.err; exit 1; }
       find $O/prof -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats.csv \; ;;
     *) echo "unknown stage $stage"; exit 2 ;;
   esac

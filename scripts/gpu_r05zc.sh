@@ -10,4 +10,4 @@ for i in 1 2 3; do for LL in $V/libpbx.so $V/var_hw1/libpbx.so; do echo "== $LL"
 PBX_PHASE_PROFILE=1 timeout -k 10 120 python -u scripts/phase_profile.py fake 1 same u8 > gpurun_out/r05zc/phase_c1.log 2>&1 || exit 1
 PBX_LIB=$V/var_hw1/libpbx.so PBX_PHASE_PROFILE=1 timeout -k 10 120 python -u scripts/phase_profile.py fake 1 same u8 > gpurun_out/r05zc/phase_c1_hw1.log 2>&1 || exit 1
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d gpurun_out/r05zc/c1prof -o c1 -- python3 -u scripts/c1_latency.py 1000 > gpurun_out/r05zc/c1prof.log 2>&1 || exit 1
-timeout -k 10 300 python -u bench.py > gpurun_out/r05zc/bench.log 2>&1 || exit 1
+timeout -k 10 300 python -u bench.py --full > bench_r05zc.log 2>&1 || exit 1
