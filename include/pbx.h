@@ -410,6 +410,31 @@ int pbx_device_synchronize(pbx_ctx* ctx);
  * (the reference runs one request per worker thread). */
 int pbx_set_kernel_streams(pbx_ctx* ctx, int32_t streams, int32_t stagger);
 
+/* Deflate strategy of every deflate tile (PNG under any filter setting, deflate-TIFF, tiled
+ * deflate-TIFF).  The reference writes PNG through java.util.zip.Deflater with the default
+ * level and strategy (TileRequestHandler.java:176-199), which searches for matches: DEFAULT
+ * does, and stays the default.
+ *   DEFAULT       every 16 KiB segment of a tile's stream is parsed for matches (runs, the
+ *                 previous sample, the row above), then Huffman coded.
+ *   HUFFMAN_ONLY  no match search at all: literals and a Huffman code, zlib's Z_HUFFMAN_ONLY.
+ *                 The same bytes as DEFAULT (+-0.1 %) on noisy or photon-counting data with the
+ *                 LZ77 kernel at 0.3 (Poisson counts) to 0.85 (uniform noise) of its time; up to
+ *                 100x the bytes on ramps, backgrounds and saturated areas.
+ *   AUTO          per segment: parsed unless fewer than 2 % of a sample of its positions
+ *                 (one in 32) start a paying match, then Huffman-only.  Never more than
+ *                 DEFAULT's bytes + 0.1 % on the measured tile kinds.
+ * Every strategy's output is a valid zlib stream of the same pixels.  The initial value is
+ * $PBX_DEFLATE_STRATEGY (0 / 1 / 2; any other value: pbx_init answers 400), else DEFAULT.  A
+ * batch takes the strategy when it is planned (pbx_batch_plan, pbx_submit, pbx_get_tile(s),
+ * the coalescer's batches); a later set does not change a planned batch.  Thread-safe. */
+enum pbx_deflate_strategy { PBX_DEFLATE_DEFAULT = 0, PBX_DEFLATE_HUFFMAN_ONLY = 1, PBX_DEFLATE_AUTO = 2 };
+int pbx_set_deflate_strategy(pbx_ctx* ctx, int32_t strategy);   /* 400 outside 0..2 */
+int pbx_get_deflate_strategy(pbx_ctx* ctx, int32_t* strategy);
+/* What a launched batch's LZ77 stage did with each segment.  modes (may be NULL): nseg bytes,
+ * 0 = parsed, 1 = Huffman-only, segments in batch order; huffman_only (may be NULL): their
+ * count.  400 if nseg != the batch's segment count or the batch has not been launched. */
+int pbx_batch_lz_modes(pbx_ctx* ctx, pbx_batch* b, uint8_t* modes, uint64_t nseg, uint64_t* huffman_only);
+
 /* sizeof of the ABI structs, for bindings to check their layouts: pbx_config,
  * pbx_plane_desc, pbx_tile_req, pbx_result, pbx_batch_stats, pbx_image_desc,
  * pbx_residency_stats, pbx_spans (in that order).  Returns the number of structs (8). */

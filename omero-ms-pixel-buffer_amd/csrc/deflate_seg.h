@@ -195,6 +195,50 @@ PBX_HD void best_match(const SM& S, const SegParams& sp, uint32_t p, uint32_t se
     }
 }
 
+// ------------------------------------------------------------ deflate strategy (pbx.h)
+// DEFAULT parses every segment; HUFFMAN_ONLY parses none (zlib's Z_HUFFMAN_ONLY: literals
+// and the end of block only); AUTO decides per segment from a sample of its bytes, below.
+enum : int { STRAT_DEFAULT = 0, STRAT_HUFFMAN_ONLY = 1, STRAT_AUTO = 2 };
+// Per-segment mode (pbx_batch_lz_modes): the segment was parsed / coded as literals only.
+enum : uint32_t { LZ_MODE_PARSED = 0, LZ_MODE_HUFFMAN_ONLY = 1 };
+
+// AUTO's sample: the first position of every thread chunk t (p = t CH) with p + 6 <= sl (the
+// longest match_minlen fits the segment).  A sampled chunk is a hit when some candidate
+// distance holds a paying match there: d != 0, not before the window, match_minlen(d) equal
+// bytes.  A segment of n sampled chunks and h hits is coded as literals only when fewer than
+// LZ_AUTO_PERMILLE in a thousand hit; n = 0 (segments shorter than 6 bytes) parses.  On noise
+// and photon-counting data a 3-byte repeat at a given place has a chance well under 1 %, on
+// ramps, backgrounds and saturated areas nearly every chunk hits.
+constexpr uint32_t LZ_AUTO_PERMILLE = 20;
+
+template <class C>
+PBX_HD bool sample_taken(uint32_t tid, const SegParams& sp) { return tid * C::CH + 6 <= sp.sl; }
+
+// Scalar form of the hit test (the device takes the same bytes from its chunk words).
+template <class C, class SM>
+PBX_HD bool ph_sample(uint32_t tid, const SM& S, const SegParams& sp) {
+    if (!sample_taken<C>(tid, sp)) return false;
+    const uint32_t p = tid * C::CH, a = sp.wl + p;
+    for (int k = 0; k < NCAND; k++) {
+        const uint32_t d = cand_dist(sp, k);
+        if (d == 0 || d > a) continue;
+        const uint32_t ml = match_minlen(d);
+        uint32_t n = 0;
+        while (n < ml && lds_byte(S, a + n) == lds_byte(S, a - d + n)) n++;
+        if (n == ml) return true;
+    }
+    return false;
+}
+
+PBX_HD bool sample_huffman_only(uint32_t hits, uint32_t sampled) {
+    return sampled != 0 && hits * 1000u < sampled * LZ_AUTO_PERMILLE;
+}
+
+// The Huffman-only tail of the LZ77 step: no wave keeps a match (the histogram, bit count and
+// bit writing phases then walk literals only).
+template <class C, class SM>
+PBX_HD void ph_no_parse(uint32_t w, SM& S) { S.w_nm[w] = 0; }
+
 // Length of a match of distance D at position p extended past L equal bytes by comparing
 // 4-byte words at offsets L + 4k, up to maxlen (scalar form of the wave-wide compare).
 template <class SM>

@@ -105,18 +105,31 @@ struct SeqWriter {
 };
 
 // k_lz77 of one segment, thread by thread (the phases' effects commute): matches, the
-// histogram (one end of block counted) and the Adler-32 partial sums.
+// histogram (one end of block counted) and the Adler-32 partial sums.  Returns the segment's
+// mode (LZ_MODE_*): parsed, or literals only (HUFFMAN_ONLY always, AUTO by its sample).
 template <class Src>
-void run_lz77(Smem& S, const Src& src, const SegParams& sp, uint32_t& a1, uint32_t& a2) {
+uint32_t run_lz77(Smem& S, const Src& src, const SegParams& sp, int strategy, uint32_t& a1, uint32_t& a2) {
     for (int t = 0; t < C::NT; t++) ph_fill<C>(t, S, src, sp);
     for (int t = 0; t < C::NT; t++) ph_lz_init<C>(t, S);
-    for (int w = 0; w < C::NW; w++) ph_parse_emu<C>(w, S, sp);
+    uint32_t mode = strategy == STRAT_HUFFMAN_ONLY ? LZ_MODE_HUFFMAN_ONLY : LZ_MODE_PARSED;
+    if (strategy == STRAT_AUTO) {
+        uint32_t hits = 0, sampled = 0;
+        for (int t = 0; t < C::NT; t++) {
+            sampled += sample_taken<C>(t, sp);
+            hits += ph_sample<C>(t, S, sp);
+        }
+        if (sample_huffman_only(hits, sampled)) mode = LZ_MODE_HUFFMAN_ONLY;
+    }
+    for (int w = 0; w < C::NW; w++) {
+        if (mode == LZ_MODE_HUFFMAN_ONLY) ph_no_parse<C>(w, S); else ph_parse_emu<C>(w, S, sp);
+    }
     a1 = 0; a2 = 0;
     for (int t = 0; t < C::NT; t++) {
         uint32_t s1, s2, n;
         ph_hist<C, EmuOps>(t, S, sp, s1, s2, n);
         adler_combine(a1, a2, s1, s2, n);
     }
+    return mode;
 }
 
 // One deflate block of nsg segments (k_lz77 per segment, k_huff on the summed histogram,
@@ -124,12 +137,12 @@ void run_lz77(Smem& S, const Src& src, const SegParams& sp, uint32_t& a1, uint32
 // cap is too small.
 template <class Src>
 int run_block(std::vector<std::unique_ptr<Smem>>& LZ, Smem& H, const Src& src, const SegParams* sps,
-              uint32_t nsg, uint8_t* out, uint64_t cap, SegOut* so) {
+              uint32_t nsg, int strategy, uint8_t* out, uint64_t cap, SegOut* so) {
     uint32_t sl = 0, a1 = 0, a2 = 0;
     for (uint32_t k = 0; k < nsg; k++) {
         memset(LZ[k].get(), 0xCD, sizeof(Smem));  // poison: phases must initialise what they read
         uint32_t s1, s2;
-        run_lz77(*LZ[k], src, sps[k], s1, s2);
+        run_lz77(*LZ[k], src, sps[k], strategy, s1, s2);
         adler_combine(a1, a2, s1, s2, sps[k].sl);
         sl += sps[k].sl;
     }
@@ -203,6 +216,85 @@ int run_block(std::vector<std::unique_ptr<Smem>>& LZ, Smem& H, const Src& src, c
     return 0;
 }
 
+// pbxemu_deflate / pbxemu_deflate_strategy (below).
+int deflate_impl(const uint8_t* stream, uint64_t len, uint32_t rowlen, int strategy, uint8_t* out,
+                 uint64_t cap, uint64_t* out_len, SegOut* blks) {
+    uint32_t nseg, seg_len;
+    deflate_split(len, nseg, seg_len);
+    std::vector<std::unique_ptr<Smem>> LZ;
+    for (uint32_t k = 0; k < BLK_SEGS; k++) LZ.emplace_back(new Smem());
+    std::unique_ptr<Smem> H(new Smem());
+    MemStream src{stream};
+    uint64_t o = 0;
+    if (cap < 2) return -1;
+    out[o++] = 0x78;
+    out[o++] = 0x9C;
+    uint32_t s1 = 0, s2 = 0;
+    const uint32_t nb = tile_blocks(nseg);
+    for (uint32_t bi = 0; bi < nb; bi++) {
+        const uint32_t k0 = block_seg0(bi, nseg, nb), nsg = block_seg0(bi + 1, nseg, nb) - k0;
+        SegParams sps[BLK_SEGS];
+        for (uint32_t q = 0; q < nsg; q++) {
+            SegParams& sp = sps[q];
+            const uint64_t s = (uint64_t)(k0 + q) * seg_len;
+            sp.sl = (uint32_t)((len - s) < seg_len ? (len - s) : seg_len);
+            sp.wl = seg_window<C>(s, rowlen);
+            sp.base = s - sp.wl;
+            sp.rowlen = rowlen;
+            sp.last = k0 + q + 1 == nseg;
+        }
+        SegOut so;
+        const int r = run_block(LZ, *H, src, sps, nsg, strategy, out + o, cap - o, &so);
+        if (r) return r;
+        o += so.nbytes;
+        adler_combine(s1, s2, so.adler_s1, so.adler_s2, so.len);
+        if (blks) blks[bi] = so;
+    }
+    if (o + 4 > cap) return -1;
+    const uint32_t ad = adler_final(s1, s2, len);
+    out[o++] = (uint8_t)(ad >> 24);
+    out[o++] = (uint8_t)(ad >> 16);
+    out[o++] = (uint8_t)(ad >> 8);
+    out[o++] = (uint8_t)ad;
+    *out_len = o;
+    return 0;
+}
+
+// pbxemu_lz77 / pbxemu_lz77_strategy (below); modes may be NULL.
+int lz77_impl(const uint8_t* stream, uint64_t len, uint32_t rowlen, int strategy, uint32_t* hist,
+              uint32_t* mrec, uint8_t* modes) {
+    uint32_t nseg, seg_len;
+    deflate_split(len, nseg, seg_len);
+    std::unique_ptr<Smem> S(new Smem());
+    MemStream src{stream};
+    for (uint32_t k = 0; k < nseg; k++) {
+        SegParams sp;
+        const uint64_t s = (uint64_t)k * seg_len;
+        sp.sl = (uint32_t)((len - s) < seg_len ? (len - s) : seg_len);
+        sp.wl = seg_window<C>(s, rowlen);
+        sp.base = s - sp.wl;
+        sp.rowlen = rowlen;
+        sp.last = k + 1 == nseg;
+        memset(S.get(), 0xCD, sizeof(Smem));
+        uint32_t a1, a2;
+        const uint32_t mode = run_lz77(*S, src, sp, strategy, a1, a2);
+        if (modes) modes[k] = (uint8_t)mode;
+        uint32_t* hg = hist + (size_t)k * HIST_WORDS;
+        for (int i = 0; i < 288; i++) hg[i] = S->lfreq[i];
+        for (int i = 0; i < 32; i++) hg[288 + i] = S->dfreq[i];
+        uint32_t* mg = mrec + (size_t)k * MREC_WORDS;
+        memset(mg, 0, MREC_WORDS * 4);
+        for (int w = 0; w < C::NW; w++) {
+            mg[w] = S->w_nm[w];
+            for (uint32_t m = 0; m < S->w_nm[w]; m++) {
+                mg[C::NW + w * C::MAXMW + m] = S->mpos[w * C::MAXMW + m];
+                mg[C::NW + C::NW * C::MAXMW + w * C::MAXMW + m] = S->mdist[w * C::MAXMW + m];
+            }
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -235,85 +327,31 @@ uint32_t pbxemu_nblocks(uint64_t len) { return tile_blocks(pbxemu_nsegs(len)); }
 // 0, -1 if cap is too small, -2 on a broken invariant.
 int pbxemu_deflate(const uint8_t* stream, uint64_t len, uint32_t rowlen, uint8_t* out,
                    uint64_t cap, uint64_t* out_len, SegOut* blks) {
-    uint32_t nseg, seg_len;
-    deflate_split(len, nseg, seg_len);
-    std::vector<std::unique_ptr<Smem>> LZ;
-    for (uint32_t k = 0; k < BLK_SEGS; k++) LZ.emplace_back(new Smem());
-    std::unique_ptr<Smem> H(new Smem());
-    MemStream src{stream};
-    uint64_t o = 0;
-    if (cap < 2) return -1;
-    out[o++] = 0x78;
-    out[o++] = 0x9C;
-    uint32_t s1 = 0, s2 = 0;
-    const uint32_t nb = tile_blocks(nseg);
-    for (uint32_t bi = 0; bi < nb; bi++) {
-        const uint32_t k0 = block_seg0(bi, nseg, nb), nsg = block_seg0(bi + 1, nseg, nb) - k0;
-        SegParams sps[BLK_SEGS];
-        for (uint32_t q = 0; q < nsg; q++) {
-            SegParams& sp = sps[q];
-            const uint64_t s = (uint64_t)(k0 + q) * seg_len;
-            sp.sl = (uint32_t)((len - s) < seg_len ? (len - s) : seg_len);
-            sp.wl = seg_window<C>(s, rowlen);
-            sp.base = s - sp.wl;
-            sp.rowlen = rowlen;
-            sp.last = k0 + q + 1 == nseg;
-        }
-        SegOut so;
-        const int r = run_block(LZ, *H, src, sps, nsg, out + o, cap - o, &so);
-        if (r) return r;
-        o += so.nbytes;
-        adler_combine(s1, s2, so.adler_s1, so.adler_s2, so.len);
-        if (blks) blks[bi] = so;
-    }
-    if (o + 4 > cap) return -1;
-    const uint32_t ad = adler_final(s1, s2, len);
-    out[o++] = (uint8_t)(ad >> 24);
-    out[o++] = (uint8_t)(ad >> 16);
-    out[o++] = (uint8_t)(ad >> 8);
-    out[o++] = (uint8_t)ad;
-    *out_len = o;
-    return 0;
+    return deflate_impl(stream, len, rowlen, STRAT_DEFAULT, out, cap, out_len, blks);
+}
+
+// The same under a deflate strategy (pbx.h enum pbx_deflate_strategy: 0 = pbxemu_deflate's
+// bytes, 1 = no segment is parsed, 2 = per segment by the sample rule of deflate_seg.h).
+// -3 for a strategy outside 0..2.
+int pbxemu_deflate_strategy(const uint8_t* stream, uint64_t len, uint32_t rowlen, int32_t strategy,
+                            uint8_t* out, uint64_t cap, uint64_t* out_len, SegOut* blks) {
+    if (strategy < STRAT_DEFAULT || strategy > STRAT_AUTO) return -3;
+    return deflate_impl(stream, len, rowlen, strategy, out, cap, out_len, blks);
 }
 
 // The LZ77 stage alone (k_lz77's outputs) for every segment of a stream: per segment
 // HIST_WORDS histogram words and MREC_WORDS match-record words laid out as k_lz77 writes
 // them (unused match slots are left 0).
 int pbxemu_lz77(const uint8_t* stream, uint64_t len, uint32_t rowlen, uint32_t* hist, uint32_t* mrec) {
-    uint32_t nseg, seg_len;
-    deflate_split(len, nseg, seg_len);
-    std::unique_ptr<Smem> S(new Smem());
-    MemStream src{stream};
-    for (uint32_t k = 0; k < nseg; k++) {
-        SegParams sp;
-        const uint64_t s = (uint64_t)k * seg_len;
-        sp.sl = (uint32_t)((len - s) < seg_len ? (len - s) : seg_len);
-        sp.wl = seg_window<C>(s, rowlen);
-        sp.base = s - sp.wl;
-        sp.rowlen = rowlen;
-        sp.last = k + 1 == nseg;
-        memset(S.get(), 0xCD, sizeof(Smem));
-        for (int t = 0; t < C::NT; t++) ph_fill<C>(t, *S, src, sp);
-        for (int t = 0; t < C::NT; t++) ph_lz_init<C>(t, *S);
-        for (int w = 0; w < C::NW; w++) ph_parse_emu<C>(w, *S, sp);
-        for (int t = 0; t < C::NT; t++) {
-            uint32_t s1, s2, n;
-            ph_hist<C, EmuOps>(t, *S, sp, s1, s2, n);
-        }
-        uint32_t* hg = hist + (size_t)k * HIST_WORDS;
-        for (int i = 0; i < 288; i++) hg[i] = S->lfreq[i];
-        for (int i = 0; i < 32; i++) hg[288 + i] = S->dfreq[i];
-        uint32_t* mg = mrec + (size_t)k * MREC_WORDS;
-        memset(mg, 0, MREC_WORDS * 4);
-        for (int w = 0; w < C::NW; w++) {
-            mg[w] = S->w_nm[w];
-            for (uint32_t m = 0; m < S->w_nm[w]; m++) {
-                mg[C::NW + w * C::MAXMW + m] = S->mpos[w * C::MAXMW + m];
-                mg[C::NW + C::NW * C::MAXMW + w * C::MAXMW + m] = S->mdist[w * C::MAXMW + m];
-            }
-        }
-    }
-    return 0;
+    return lz77_impl(stream, len, rowlen, STRAT_DEFAULT, hist, mrec, nullptr);
+}
+
+// The same under a deflate strategy; modes (may be NULL): one byte per segment, 0 = parsed,
+// 1 = literals only (what pbx_batch_lz_modes reports).  -3 for a strategy outside 0..2.
+int pbxemu_lz77_strategy(const uint8_t* stream, uint64_t len, uint32_t rowlen, int32_t strategy,
+                         uint32_t* hist, uint32_t* mrec, uint8_t* modes) {
+    if (strategy < STRAT_DEFAULT || strategy > STRAT_AUTO) return -3;
+    return lz77_impl(stream, len, rowlen, strategy, hist, mrec, modes);
 }
 
 uint32_t pbxemu_hist_words(void) { return HIST_WORDS; }

@@ -143,6 +143,7 @@ struct EncSmem {
 static_assert(CRCX_WORDS * 4 <= DC::NW * DC::MAXMW * 6, "the CRC combine tables fit the match lists' room");
 static_assert(sizeof(EncSmem<DC>) * 512 <= 40 * 1024 * DC::NT, "32 encode waves per CU (160 KiB LDS)");
 
+#ifndef PBX_LZ_STRATEGY_TU  // (kernels_deflate_strategy.hip holds k_lz77 alone: no CRC tables)
 // Slicing-by-4 (or 8) CRC-32 tables, built at compile time into device memory (copied to LDS).
 struct CrcTables {
     uint32_t t[PBX_CRC_SLICES][256];
@@ -232,6 +233,7 @@ __device__ __forceinline__ uint32_t crc_mul_tab(const uint32_t* t, uint32_t b) {
     for (int j = 0; j < 8; j++) r ^= t[j * 16 + ((b >> (4 * j)) & 0xFu)];
     return r;
 }
+#endif
 // Sum of x over the wave (row scans by DPP shifts, then the four row totals), uniform.
 __device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);  // row_shr:1
@@ -251,6 +253,7 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t x) {
            (uint32_t)__builtin_amdgcn_readlane((int)x, 47) ^ (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 
+#ifndef PBX_LZ_STRATEGY_TU
 __device__ __forceinline__ uint32_t crc_x8n_small(uint32_t n) {  // n < 2^16
     return crc_multmodp(kCrcPow.lo[n & 0xFFu], kCrcPow.hi[(n >> 8) & 0xFFu]);
 }
@@ -268,6 +271,7 @@ __global__ __launch_bounds__(256) void k_crc_tables() {
     g_crc_x8n[n] = op;
     g_crc_fin[n] = crc_from_raw(0u, op);
 }
+#endif
 
 // Segment geometry from the tile descriptor.
 __device__ __forceinline__ SegParams seg_params(const TileDesc& d, uint32_t k) {
@@ -1395,7 +1399,11 @@ __device__ __forceinline__ void lz_write_out(const LzSmem<C>& S, uint32_t seg, c
 #else
 #define PBX_LZ_BOUNDS __launch_bounds__(C::NT)
 #endif
-template <class C, bool PROF, bool VC = false>
+// STRAT (deflate_seg.h STRAT_*): DEFAULT parses every segment; HUFFMAN_ONLY holds no parse at
+// all (no candidate masks, walk, carry rounds or match lists: fill, literal histogram, end of
+// block, Adler-32); AUTO samples the segment after the fill (ph_sample's rule on the chunk
+// words) and takes one of the two, the same in every thread of the workgroup.
+template <class C, bool PROF, bool VC = false, int STRAT = STRAT_DEFAULT>
 __global__ PBX_LZ_BOUNDS void k_lz77(const TileDesc* __restrict__ dt,
                                                 const uint32_t* __restrict__ seg_tile,
                                                 uint32_t nseg, uint8_t* __restrict__ stream,
@@ -1475,14 +1483,52 @@ __global__ PBX_LZ_BOUNDS void k_lz77(const TileDesc* __restrict__ dt,
         cw[0] = lane ? prev : (wi ? S.buf[wi - 1] : 0u);
     }
     uint32_t cover = 0, smask = 0xFFFFFFFFu;
-#ifndef PBX_LZ_SKIP_PARSE
-#define PBX_LZ_SKIP_PARSE 0  // timing experiments only: no matches (valid output, lower ratio)
-#endif
-    if (PBX_LZ_SKIP_PARSE) {
-        if (lane == 0) S.w_nm[w] = 0;
-        const uint32_t p0 = tid * C::CH;
-        const uint32_t nval = sp.sl > p0 ? sp.sl - p0 : 0u;
+    bool literals = STRAT == STRAT_HUFFMAN_ONLY;  // (uniform) the segment is not parsed
+    if constexpr (STRAT == STRAT_AUTO) {
+        // ph_sample on the chunk's first bytes: distances 1 and 2 from the chunk words (the two
+        // bytes before the chunk are the top of cw[0]), one row up from one unaligned LDS read
+        // (two words more for a 6-byte match_minlen).  Hits and sampled chunks per wave by
+        // ballot, the eight partials through LDS.
+        __shared__ uint32_t samp[C::NW];
+        const bool taken = sample_taken<C>(tid, sp);
+        const uint32_t a0 = sp.wl + cs;
+        bool hit = false;
+#pragma unroll
+        for (int c = 0; c < NCAND; c++) {
+            const uint32_t dc = cand_dist(sp, c);
+            if (dc == 0 || dc > a0) continue;
+            const uint32_t mlc = match_minlen(dc);
+            uint32_t x, x2 = 0;
+            if (c < 2) {
+                x = cw[1] ^ funnel32(cw[1], cw[0], 32 - 8 * dc);
+            } else {
+                x = cw[1] ^ lds_ld4(S, a0 - dc);
+                if (mlc == 6) x2 = (cw[2] ^ lds_ld4(S, a0 - dc + 4)) & 0xFFFFu;
+            }
+            if (mlc == 3) x &= 0xFFFFFFu;
+            hit = hit || (x | x2) == 0;
+        }
+        const uint32_t nh = (uint32_t)__builtin_popcountll(__ballot(taken && hit));
+        const uint32_t ns = (uint32_t)__builtin_popcountll(__ballot(taken));
+        if (lane == 0) samp[w] = nh | (ns << 16);
+        __syncthreads();
+        uint32_t tot = 0;
+#pragma unroll
+        for (int j = 0; j < C::NW; j++) tot += samp[j];
+        tot = __builtin_amdgcn_readfirstlane(tot);
+        literals = sample_huffman_only(tot & 0xFFFFu, tot >> 16);
+    }
+    // the Huffman-only tail: no wave keeps a match, every position of the segment is a literal
+    auto no_parse = [&]() {
+        if (lane == 0) ph_no_parse<C>(w, S);
+        const uint32_t nval = sp.sl > cs ? sp.sl - cs : 0u;
         smask = nval >= 32 ? 0xFFFFFFFFu : (1u << nval) - 1u;
+    };
+    if constexpr (STRAT == STRAT_HUFFMAN_ONLY) {
+        no_parse();
+    } else if constexpr (STRAT == STRAT_AUTO) {
+        if (literals) no_parse();
+        else ph_parse_dev<C, LzSmem<C>, PROF, VC>(tid, S, sp, cw, cover, smask);
     } else {
         ph_parse_dev<C, LzSmem<C>, PROF, VC>(tid, S, sp, cw, cover, smask);
     }
@@ -1553,6 +1599,8 @@ __global__ PBX_LZ_BOUNDS void k_lz77(const TileDesc* __restrict__ dt,
 #define PBX_LZ_SKIP_OUT 0  // timing experiments only: wrong output
 #endif
     if (!PBX_LZ_SKIP_OUT) lz_write_out<C>(S, seg, sp, d.out_off + sp.base + sp.wl, info, hist, mrec, tid);
+    if (STRAT == STRAT_AUTO && tid == 0)  // the segment's mode, in its match record's padding (pbx_batch_lz_modes)
+        mrec[(size_t)seg * MREC_WORDS + MREC_MODE_WORD] = literals ? LZ_MODE_HUFFMAN_ONLY : LZ_MODE_PARSED;
     stamp();
     // (diagnostics: slot 7 = slot 6 + the walk steps, so the lz77 report's "7:" is their mean;
     // slots 30/31 (unused by k_encode) differ by 1 + 1000 x the repair rounds: encode "7:")
@@ -1569,6 +1617,33 @@ __global__ PBX_LZ_BOUNDS void k_lz77(const TileDesc* __restrict__ dt,
     }
 }
 
+// The HUFFMAN_ONLY and AUTO instantiations live in a translation unit of their own
+// (kernels_deflate_strategy.hip includes this file with PBX_LZ_STRATEGY_TU set and keeps only
+// what k_lz77 needs): with them in this one the inliner sees more callers of the fill and
+// parse helpers and schedules DEFAULT's kernels differently (a dozen more scalar-register
+// spill moves in 14,000 instructions).  Apart, DEFAULT's k_lz77 is instruction for instruction
+// the kernel from before the option existed.  a.strategy is HUFFMAN_ONLY or AUTO.
+hipError_t launch_lz77_strategy(hipStream_t st, const DeflateLaunch& a, bool prof, uint32_t self_map);
+#ifdef PBX_LZ_STRATEGY_TU
+hipError_t launch_lz77_strategy(hipStream_t st, const DeflateLaunch& a, bool prof, uint32_t self_map) {
+#define PBX_LZ_LAUNCH(P, V, ST)                                                                              \
+    hipLaunchKernelGGL((k_lz77<DC, P, V, ST>), dim3(a.nseg), dim3(DC::NT), 0, st, a.tiles, a.seg_tile, a.nseg,  \
+                       a.stream, a.info, a.blk, a.hist, a.mrec, a.stamps, a.uniform_nseg, a.uniform_rcp, self_map)
+    if (a.strategy == STRAT_HUFFMAN_ONLY) {  // (the row-filtered form only changes the walk: none here)
+        if (prof) PBX_LZ_LAUNCH(true, false, STRAT_HUFFMAN_ONLY); else PBX_LZ_LAUNCH(false, false, STRAT_HUFFMAN_ONLY);
+    } else if (a.strategy == STRAT_AUTO) {
+        if (prof) {
+            if (a.row_filtered) PBX_LZ_LAUNCH(true, true, STRAT_AUTO); else PBX_LZ_LAUNCH(true, false, STRAT_AUTO);
+        } else {
+            if (a.row_filtered) PBX_LZ_LAUNCH(false, true, STRAT_AUTO); else PBX_LZ_LAUNCH(false, false, STRAT_AUTO);
+        }
+    } else {
+        return hipErrorInvalidValue;
+    }
+#undef PBX_LZ_LAUNCH
+    return hipGetLastError();
+}
+#else
 // ==================================================================== k_huff
 // x of lane (lane ^ M) without an LDS round trip: DPP quad permutes (1, 2), two row shifts
 // and a select (4), a row rotate (8), gfx950's permlane swaps and a select (16, 32).
@@ -3434,11 +3509,14 @@ hipError_t launch_deflate(hipStream_t st, const DeflateLaunch& a, hipEvent_t* ev
     if (!self_map)
         hipLaunchKernelGGL(k_seg_map, dim3((a.nseg + 255) / 256), dim3(256), 0, st, a.tiles, a.ntiles, a.nseg,
                            a.uniform_nseg, a.uniform_rcp, a.seg_tile, a.info, a.blk);
+    if (a.strategy < STRAT_DEFAULT || a.strategy > STRAT_AUTO) return hipErrorInvalidValue;
     const uint32_t lz_grid = a.nseg;
 #define PBX_LZ_LAUNCH(P, V)                                                                                  \
     hipLaunchKernelGGL((k_lz77<DC, P, V>), dim3(lz_grid), dim3(DC::NT), 0, st, a.tiles, a.seg_tile, a.nseg,   \
                        a.stream, a.info, a.blk, a.hist, a.mrec, a.stamps, a.uniform_nseg, a.uniform_rcp, self_map)
-    if (prof) {
+    if (a.strategy != STRAT_DEFAULT) {
+        if (const hipError_t e = launch_lz77_strategy(st, a, prof, self_map); e != hipSuccess) return e;
+    } else if (prof) {
         if (a.row_filtered) PBX_LZ_LAUNCH(true, true); else PBX_LZ_LAUNCH(true, false);
     } else {
         if (a.row_filtered) PBX_LZ_LAUNCH(false, true); else PBX_LZ_LAUNCH(false, false);
@@ -3495,6 +3573,8 @@ hipError_t launch_deflate(hipStream_t st, const DeflateLaunch& a, hipEvent_t* ev
                            a.blk, a.offs, a.out);
     return hipGetLastError();
 }
+
+#endif  // PBX_LZ_STRATEGY_TU
 
 }  // namespace pbx
 

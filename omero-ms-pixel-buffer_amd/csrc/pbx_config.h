@@ -54,7 +54,11 @@ PBX_HD uint32_t block_seg0(uint32_t j, uint32_t nseg, uint32_t nb) {
 constexpr uint32_t HIST_WORDS = 320;  // literal/length + distance histogram
 constexpr uint32_t MREC_WORDS =       // per-wave match counts, positions|lengths, distances
     (DeflateMainCfg::NW + 2 * DeflateMainCfg::NW * DeflateMainCfg::MAXMW + 63) & ~63u;
-constexpr uint32_t CODE_WORDS = 320 + DeflateMainCfg::HDRW;  // codes + block header bits
+// The first padding word of a segment's match record: its mode (LZ_MODE_*), written by the
+// AUTO strategy's k_lz77 only (pbx_batch_lz_modes).
+constexpr uint32_t MREC_MODE_WORD = DeflateMainCfg::NW + 2 * DeflateMainCfg::NW * DeflateMainCfg::MAXMW;
+static_assert(MREC_MODE_WORD < MREC_WORDS, "the match record's padding holds the mode word");
+constexpr uint32_t CODE_WORDS =320 + DeflateMainCfg::HDRW;  // codes + block header bits
 
 // Split of a stream of `len` bytes into segments of at most SEG bytes: an equal split
 // rounded up to 16 bytes (segment starts stay 16-byte aligned for vector loads); the

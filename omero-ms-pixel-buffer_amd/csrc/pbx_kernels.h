@@ -83,6 +83,7 @@ struct DeflateLaunch {
     uint32_t uniform_nseg = 0;  // every tile has this many segments (tile = seg / it), or 0
     uint32_t uniform_rcp = 0;   // recip32(uniform_nseg)
     bool row_filtered = false;  // some tile's stream is PNG-row-filtered (k_lz77's VALU walk form)
+    int32_t strategy = 0;       // deflate strategy of the batch (deflate_seg.h STRAT_*): the k_lz77 instantiation
 };
 // k_lz77, k_huff, k_seg_sizes + k_scan_offsets, k_encode, k_frame.
 // ev[0..3] (and ev2[0..3] if given) are recorded after k_lz77, k_huff, k_scan_offsets, k_encode;

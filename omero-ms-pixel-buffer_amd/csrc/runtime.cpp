@@ -397,6 +397,9 @@ struct pbx_ctx {
     std::atomic<int> stagger{1};
     hipEvent_t stage_ev[4][4] = {};     // [stream][stage]
     std::atomic<int> last_ks{-1};       // stream of the last overlapped deflate batch
+    // Deflate strategy (enum pbx_deflate_strategy; $PBX_DEFLATE_STRATEGY at pbx_init,
+    // pbx_set_deflate_strategy): a batch takes the value when it is planned.
+    std::atomic<int> deflate_strategy{PBX_DEFLATE_DEFAULT};
     hipStream_t copy_stream = nullptr;  // D2H of finished batches, overlapping later kernels
     // Pipelined batches holding both raw / TIFF tiles and deflate tiles run their HBM-bound
     // k_extract on this stream, beside their own (and the previous batch's) issue-bound deflate
@@ -520,6 +523,7 @@ struct pbx_batch {
     // results need no D2H round trip; the block becomes the results' HostBlock at the fetch
     void* h_zc = nullptr;
     uint64_t zc_png_at = 0;
+    int32_t strategy = PBX_DEFLATE_DEFAULT;  // the context's deflate strategy when the batch was planned
     bool launched = false;
     bool attempted = false;  // batch_launch began enqueuing work (it may have failed midway)
     uint64_t ordinal = 0;    // launch ordinal in the context (fault injection)
@@ -1391,6 +1395,12 @@ int pbx_init(const pbx_config* cfg_in, pbx_ctx** out) {
         return fail(PBX_E_BADARG, "bad png_filter %d", cfg.png_filter);
     if (cfg.tiff_tile && (cfg.tiff_tile < 16 || cfg.tiff_tile > 4096 || cfg.tiff_tile % 16))
         return fail(PBX_E_BADARG, "bad tiff_tile %d (0, or a multiple of 16 in [16, 4096])", cfg.tiff_tile);
+    int strategy = PBX_DEFLATE_DEFAULT;
+    if (const char* ds = getenv("PBX_DEFLATE_STRATEGY")) {
+        if (ds[0] < '0' || ds[0] > '2' || ds[1])
+            return fail(PBX_E_BADARG, "bad PBX_DEFLATE_STRATEGY '%s' (0 default, 1 Huffman-only, 2 auto)", ds);
+        strategy = ds[0] - '0';
+    }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return fail(PBX_E_INTERNAL, "no HIP device available (the tile pipeline runs on MI355X only)");
@@ -1404,6 +1414,7 @@ int pbx_init(const pbx_config* cfg_in, pbx_ctx** out) {
     pbx_ctx* ctx = new pbx_ctx();
     ctx->device = dev;
     ctx->cfg = cfg;
+    ctx->deflate_strategy = strategy;
     ctx->hpool.pinned = true;
     ctx->evpool_sync.flags = hipEventDisableTiming;
     if (const char* su = getenv("PBX_SPIN_US")) ctx->spin_us = atoll(su);
@@ -1501,6 +1512,23 @@ int pbx_set_kernel_streams(pbx_ctx* ctx, int32_t streams, int32_t stagger) {
     ctx->nks = streams;
     ctx->stagger = stagger;
     ctx->last_ks = -1;
+    return PBX_OK;
+}
+
+static_assert(PBX_DEFLATE_DEFAULT == STRAT_DEFAULT && PBX_DEFLATE_HUFFMAN_ONLY == STRAT_HUFFMAN_ONLY &&
+              PBX_DEFLATE_AUTO == STRAT_AUTO, "pbx.h's strategies are the kernels'");
+int pbx_set_deflate_strategy(pbx_ctx* ctx, int32_t strategy) {
+    if (!ctx) return fail(PBX_E_BADARG, "null ctx");
+    if (strategy < PBX_DEFLATE_DEFAULT || strategy > PBX_DEFLATE_AUTO)
+        return fail(PBX_E_BADARG, "deflate strategy %d out of range (0 default, 1 Huffman-only, 2 auto)", strategy);
+    std::lock_guard<std::mutex> run(ctx->run_mu);  // not in the middle of a batch's plan + launch
+    ctx->deflate_strategy = strategy;
+    return PBX_OK;
+}
+
+int pbx_get_deflate_strategy(pbx_ctx* ctx, int32_t* strategy) {
+    if (!ctx || !strategy) return fail(PBX_E_BADARG, "null argument");
+    *strategy = ctx->deflate_strategy;
     return PBX_OK;
 }
 
@@ -2579,6 +2607,7 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
     b->status.resize(n);
     b->w.resize(n);
     b->h.resize(n);
+    b->strategy = ctx->deflate_strategy;  // a later pbx_set_deflate_strategy does not change this batch
     const int filter = ctx->cfg.png_filter;
     const bool tiff_deflate = ctx->cfg.tiff_deflate != 0;
     const int32_t tiff_tile = ctx->cfg.tiff_tile;
@@ -2965,6 +2994,7 @@ static int batch_launch(pbx_ctx* ctx, pbx_batch* b, bool overlap, bool fetch_fol
         if (b->dt[k].seg_count != a.uniform_nseg) a.uniform_nseg = 0;
     a.uniform_rcp = recip32(a.uniform_nseg);
     for (uint32_t k = 0; k < ndt && !a.row_filtered; k++) a.row_filtered = b->dt[k].filter != 0;
+    a.strategy = b->strategy;
     // the serving path reads the tile offsets from a mapped copy the scan writes (no D2H
     // copy at the end of the launch)
     void* offs_dev = nullptr;
@@ -3386,6 +3416,26 @@ int pbx_test_batch_lz77(pbx_ctx* ctx, pbx_batch* b, uint32_t* hist, uint32_t* mr
     HIP_TRY(hipEventSynchronize(b->ev[8]));
     HIP_TRY(hipMemcpy(hist, b->d_hist, nseg * HIST_WORDS * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(mrec, b->d_mrec, nseg * MREC_WORDS * 4, hipMemcpyDeviceToHost));
+    return PBX_OK;
+}
+
+int pbx_batch_lz_modes(pbx_ctx* ctx, pbx_batch* b, uint8_t* modes, uint64_t nseg, uint64_t* huffman_only) {
+    if (!ctx || !b) return fail(PBX_E_BADARG, "null argument");
+    if (!b->launched) return fail(PBX_E_BADARG, "batch not launched");
+    if (nseg != b->nseg) return fail(PBX_E_BADARG, "segment count %llu != %u", (unsigned long long)nseg, b->nseg);
+    std::vector<uint8_t> m(b->nseg, b->strategy == PBX_DEFLATE_HUFFMAN_ONLY ? LZ_MODE_HUFFMAN_ONLY : LZ_MODE_PARSED);
+    if (b->strategy == PBX_DEFLATE_AUTO && b->nseg) {  // k_lz77 left every segment's mode in its match record
+        if (ensure_device(ctx)) return PBX_E_INTERNAL;
+        HIP_TRY(hipEventSynchronize(b->ev[8]));
+        std::vector<uint32_t> w(b->nseg);
+        HIP_TRY(hipMemcpy2D(w.data(), 4, (const uint32_t*)b->d_mrec + MREC_MODE_WORD, (size_t)MREC_WORDS * 4, 4, b->nseg,
+                            hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < b->nseg; k++) m[k] = (uint8_t)w[k];
+    }
+    uint64_t n1 = 0;
+    for (uint8_t v : m) n1 += v == LZ_MODE_HUFFMAN_ONLY;
+    if (modes && b->nseg) memcpy(modes, m.data(), b->nseg);
+    if (huffman_only) *huffman_only = n1;
     return PBX_OK;
 }
 

@@ -47,6 +47,9 @@ FMT_RAW, FMT_PNG, FMT_TIF, FMT_UNKNOWN = range(4)
 SRC_HOST, SRC_GEN_FAKE, SRC_GEN_NOISE = range(3)
 BIG_ENDIAN, LITTLE_ENDIAN = 0, 1
 FILTER_NONE, FILTER_SUB, FILTER_UP, FILTER_AVG, FILTER_PAETH, FILTER_ADAPTIVE = range(6)
+# enum pbx_deflate_strategy: match search in every segment (the reference's Deflater default),
+# in none (zlib's Z_HUFFMAN_ONLY), or per segment where a sample of it says matches pay
+DEFLATE_DEFAULT, DEFLATE_HUFFMAN_ONLY, DEFLATE_AUTO = range(3)
 
 
 class PbxConfig(ctypes.Structure):
@@ -139,6 +142,7 @@ EXPORTS = [
     "pbx_node_size", "pbx_node_context", "pbx_node_route", "pbx_node_get_tile",
     "pbx_plane_create_sparse", "pbx_band_write", "pbx_plane_band_info", "pbx_result_spans",
     "pbx_test_stall_batch", "pbx_band_abort", "pbx_test_fail_band_write",
+    "pbx_set_deflate_strategy", "pbx_get_deflate_strategy", "pbx_batch_lz_modes",
 ]
 
 _lib = None
@@ -167,6 +171,9 @@ def lib() -> ctypes.CDLL:
     L.pbx_device_synchronize.argtypes = [vp]
     L.pbx_set_kernel_streams.argtypes = [vp, i32, i32]
     L.pbx_release_cached.argtypes = [vp]
+    L.pbx_set_deflate_strategy.argtypes = [vp, i32]
+    L.pbx_get_deflate_strategy.argtypes = [vp, ctypes.POINTER(i32)]
+    L.pbx_batch_lz_modes.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.pbx_plane_register.argtypes = [vp, ctypes.POINTER(PbxPlaneDesc), ctypes.POINTER(u64)]
     L.pbx_plane_release.argtypes = [vp, u64]
     L.pbx_image_declare.argtypes = [vp, ctypes.POINTER(PbxImageDesc)]
@@ -448,7 +455,13 @@ def ngff_multiscales(image_dir: str):
 
 def make_config(device: Optional[int] = None, png_filter: int = FILTER_NONE,
                 tiff_deflate: bool = False, coalesce: bool = True, stage_rows: bool = False,
-                tiff_tile: Optional[int] = None, request_timeout_us: Optional[int] = None) -> PbxConfig:
+                tiff_tile: Optional[int] = None, request_timeout_us: Optional[int] = None,
+                deflate_strategy: Optional[int] = None) -> PbxConfig:
+    """``deflate_strategy`` is not a field of pbx_config (the struct keeps its size): it is
+    checked here and applied by ``PixelsService`` with the setter right after init."""
+    if deflate_strategy is not None and deflate_strategy not in (DEFLATE_DEFAULT, DEFLATE_HUFFMAN_ONLY,
+                                                                  DEFLATE_AUTO):
+        raise PbxError(E_BADARG, "deflate strategy %r out of range" % (deflate_strategy,))
     cfg = PbxConfig()
     _check(lib().pbx_config_default(ctypes.byref(cfg)))
     cfg.device = -1 if device is None else device
@@ -473,8 +486,11 @@ class PixelsService:
     def __init__(self, device: Optional[int] = None, png_filter: int = FILTER_NONE,
                  tiff_deflate: bool = False, coalesce: bool = True, stage_rows: bool = False,
                  tiff_tile: Optional[int] = None, sparse_band_rows: int = 0,
-                 request_timeout_us: Optional[int] = None, _handle=None):
-        """sparse_band_rows > 0: planes the handler opens on demand are sparse planes of bands
+                 request_timeout_us: Optional[int] = None, deflate_strategy: Optional[int] = None,
+                 _handle=None):
+        """deflate_strategy: DEFLATE_DEFAULT / DEFLATE_HUFFMAN_ONLY / DEFLATE_AUTO (None: the
+        library's initial value, $PBX_DEFLATE_STRATEGY or DEFAULT).
+        sparse_band_rows > 0: planes the handler opens on demand are sparse planes of bands
         of that many rows (region-proportional residency); 0: whole planes (or the handler's
         row band)."""
         import threading
@@ -487,10 +503,12 @@ class PixelsService:
             return
         L = lib()
         cfg = make_config(device, png_filter, tiff_deflate, coalesce, stage_rows, tiff_tile,
-                          request_timeout_us)
+                          request_timeout_us, deflate_strategy)
         h = ctypes.c_void_p()
         _check(L.pbx_init(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
+        if deflate_strategy is not None:
+            self.set_deflate_strategy(deflate_strategy)
 
     def close(self) -> None:
         if self._h and self._owned:
@@ -909,6 +927,16 @@ class PixelsService:
     def synchronize(self) -> None:
         _check(lib().pbx_device_synchronize(self._h))
 
+    def set_deflate_strategy(self, strategy: int) -> None:
+        """Deflate strategy of the batches planned from now on (pbx_set_deflate_strategy)."""
+        _check(lib().pbx_set_deflate_strategy(self._h, strategy))
+
+    @property
+    def deflate_strategy(self) -> int:
+        v = ctypes.c_int32()
+        _check(lib().pbx_get_deflate_strategy(self._h, ctypes.byref(v)))
+        return v.value
+
     def set_kernel_streams(self, streams: int, stagger: int = 1) -> None:
         """Kernel streams for pipelined batches (pbx_set_kernel_streams); 1 = serial."""
         _check(lib().pbx_set_kernel_streams(self._h, streams, stagger))
@@ -986,6 +1014,9 @@ class PixelsNode:
         _check(L.pbx_node_init(ctypes.byref(cfg), n, devs, shard_tile, ctypes.byref(h)))
         self._h = h
         self.services = [PixelsService(_handle=L.pbx_node_context(h, k)) for k in range(n)]
+        if config.get("deflate_strategy") is not None:
+            for s in self.services:
+                s.set_deflate_strategy(config["deflate_strategy"])
 
     def route(self, ctx: TileCtx) -> Tuple[int, int]:
         """(status the serving context would answer, its index); E_NOT_RESIDENT -> the index is
@@ -1115,6 +1146,17 @@ class Batch:
         _check(lib().pbx_test_batch_lz77(self.service.handle, self._h, h.ctypes.data,
                                          m.ctypes.data, nseg))
         return h.reshape(nseg, hist_words), m.reshape(nseg, mrec_words)
+
+    def lz_modes(self):
+        """Per segment of the launched batch, in batch order: 0 = parsed for matches,
+        1 = Huffman-only (pbx_batch_lz_modes), as a uint8 numpy array."""
+        import numpy as np
+        nseg = int(self.stats().segments)
+        m = np.zeros(nseg, np.uint8)
+        n1 = ctypes.c_uint64()
+        _check(lib().pbx_batch_lz_modes(self.service.handle, self._h, m.ctypes.data, nseg, ctypes.byref(n1)))
+        assert int(m.sum()) == n1.value
+        return m
 
     def fetch_into_host(self) -> int:
         """D2H of every result into library-owned pinned memory, then release it; returns
