@@ -280,6 +280,25 @@ int pbx_plane_register_zarr(pbx_ctx* ctx, const pbx_plane_desc* desc, const pbx_
  * serial decode latency.  All planes are registered, or none (400/500). */
 int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
                              const pbx_zarr_chunks* chunks, uint64_t* plane_ids, double* kernel_ms);
+/* Rows [y0, y0 + rows) of ONE band of a sparse plane, decoded on the GPU from the Zarr chunk
+ * rows that cover them: pbx_band_write for a plane stored as NGFF/Zarr, so a cold tile costs
+ * the chunks of its bands and not the plane's (ZarrPixelsService reads only the chunks the region
+ * covers, TileRequestHandler.java:102-109).  `chunks` is as for pbx_plane_register_zarr (chunk
+ * shape, codec, blosc forms, fill_bits) except that data / offsets hold only chunk rows
+ * cy0 = y0 / chunk_y up to (not including) cy1 = ceil((y0 + rows) / chunk_y), each full width
+ * (gx chunks) in C order: (cy1 - cy0) * gx + 1 offsets; an empty range is a missing chunk (fill).
+ * Rows of those chunks outside [y0, y0 + rows) are decoded but not written, so band_rows need not
+ * be a multiple of chunk_y and a band may be written in pieces at any rows.  The bytes land in
+ * the plane's stored byte order: create the sparse plane with source PBX_SRC_HOST and the
+ * .zarray dtype's byte order.  Band states, statuses (400 rows outside one band or a plane that
+ * is not sparse, 409 resident band, 507 no room) and failure handling are pbx_band_write's, and
+ * pieces written by either call may be mixed in one band.  Malformed input the host can see (null
+ * pointers, codec, chunk shape, offsets, blosc headers) is 400 and leaves the band as it was; a
+ * stream a decoder rejects on the device is 400 and fails the band's load like a failed upload.
+ * Upload, decode and placement run on the upload stream: tile batches do not wait behind them.
+ * kernel_ms (may be NULL): [0] device ms of the decode kernels, [1] of the placement kernel. */
+int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                        const pbx_zarr_chunks* chunks, double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -476,8 +495,9 @@ int pbx_test_fail_batch(pbx_ctx* ctx, uint64_t ahead);
  * queue behind it on the device, as behind a wedged one.  Callers of pbx_get_tile get 500 at
  * their deadline (pbx_config.request_timeout_us).  0 releases the stall and disarms. */
 int pbx_test_stall_batch(pbx_ctx* ctx, uint64_t ahead);
-/* Upload failure injection (test hook): the `ahead`-th pbx_band_write from now on fails after
- * joining its band's load, as a failed host-to-device copy would.  0 disables. */
+/* Upload failure injection (test hook): the `ahead`-th pbx_band_write or
+ * pbx_band_write_zarr from now on fails after joining its band's load, as a failed
+ * host-to-device copy would.  0 disables. */
 int pbx_test_fail_band_write(pbx_ctx* ctx, uint64_t ahead);
 
 /* Request sharding across GPUs (one process per GPU, no collectives): the rank that

@@ -1145,7 +1145,10 @@ __global__ __launch_bounds__(256) void k_zarr_copy(const ZStream* __restrict__ s
 // ------------------------------------------------------------------------------- place
 // One workgroup per (chunk, band of ZP_ROWS chunk rows).  Blosc byte-unshuffle (typesize ts
 // within blocks of `blocksize` bytes) + copy into the pitched plane (samples stay in the
-// array's byte order); missing chunks get the fill bytes.  Fast path: each thread makes one
+// array's byte order); missing chunks get the fill bytes.  Only plane rows inside the
+// destination's window [y_lo, y_hi) are written: the whole plane at registration, the rows of
+// one pbx_band_write_zarr call for a band of a sparse plane (ZPlane::dev is then the band's
+// virtual base, band.dev - band_lo * pitch, so rows keep their plane index).  Fast path: each thread makes one
 // aligned 16-byte group of a plane row (16 / bpp samples): unshuffled chunks are one 16-byte
 // load, shuffled ones one load of 16 / bpp bytes from each byte plane, interleaved with byte
 // permutes (v_perm_b32).  Groups straddling a blosc block, row tails and unaligned rows take
@@ -1190,11 +1193,17 @@ __global__ __launch_bounds__(256) void k_zarr_place(const ZChunk* __restrict__ c
     const uint32_t bpp = zp.bpp;
     const uint64_t fill = zp.fill;
     const uint32_t band = blockIdx.x % bands;
-    const int32_t r0 = (int32_t)(band * ZP_ROWS);
+    int32_t r0 = (int32_t)(band * ZP_ROWS);
     if (r0 >= chh) return;  // bands cover the tallest chunk of the set
     const int32_t w = sx - c.x0 < cw ? sx - c.x0 : cw;
     const int32_t h = sy - c.y0 < chh ? sy - c.y0 : chh;
-    const int32_t r1 = r0 + (int32_t)ZP_ROWS < h ? r0 + (int32_t)ZP_ROWS : h;
+    int32_t r1 = r0 + (int32_t)ZP_ROWS < h ? r0 + (int32_t)ZP_ROWS : h;
+    // the destination's row window (plane rows [y_lo, y_hi)), as chunk rows: every body below
+    // walks rows [r0, r1) only, and the clip is the same for the whole workgroup (no exec masks)
+    const int32_t w0 = zp.y_lo - c.y0, w1 = zp.y_hi - c.y0;
+    r0 = r0 > w0 ? r0 : w0;
+    r1 = r1 < w1 ? r1 : w1;
+    if (r0 >= r1) return;  // wholly outside the window (or below the plane)
     const uint8_t* s = (c.flags & ZC_INPUT ? input : scratch) + c.src;
     const uint32_t ts = c.typesize, bs = c.blocksize, nb = c.nbytes;
     const bool missing = (c.flags & ZC_MISSING) != 0;

@@ -112,11 +112,12 @@ struct ZChunk {
     uint32_t plane, pad;                  // index into the ZPlane table of the launch
 };
 struct ZPlane {                           // a destination plane of one decode launch
-    uint8_t* dev;
+    uint8_t* dev;                         // row 0 of the plane (a band: its virtual base)
     int64_t pitch;
     int32_t sx, sy, cw, chh;              // plane and chunk shape
     uint32_t bpp, pad;
     uint64_t fill;                        // fill bytes in stored order (missing chunks)
+    int32_t y_lo, y_hi;                   // plane rows k_zarr_place may write: [y_lo, y_hi)
 };
 // Streams ordered by kind (ZS_LZ4 | ZS_ZLIB | ZS_COPY | ZS_BLOSCLZ | ZS_ZSTD), counts[k] of
 // kind k; err[i] = 0 or a decoder error code per stream.

@@ -1883,6 +1883,7 @@ int pbx_plane_create_sparse(pbx_ctx* ctx, const pbx_plane_desc* d, int32_t band_
     return PBX_OK;
 }
 
+}  // extern "C"
 namespace {
 
 // A loading band back to absent (under reg_mu); its HBM goes to `to_free`.
@@ -1903,10 +1904,9 @@ void free_planes_locked(pbx_ctx* ctx, const std::vector<std::pair<void*, size_t>
     }
 }
 
-// Rows [y0, y0 + rows) of one band of a sparse plane: the first write of an absent band
-// allocates it (within the budget, evicting idle planes / bands), the last one publishes it.
-// data == NULL on a generator plane generates the rows on the GPU instead.
-int band_write(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const void* data, uint64_t bytes) {
+// The band of a sparse plane that holds rows [y0, y0 + rows), or 400: the plane is not sparse,
+// or the rows leave the plane or that one band.
+int band_of_rows(const Plane* q, int32_t y0, int32_t rows, int32_t* band) {
     if (!q->sparse_rows) return fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)q->id);
     // any band of the plane: the owned ones, and guest bands that regions straddling the end of
     // the owned rows cover (validate routes a region by its first row)
@@ -1915,12 +1915,19 @@ int band_write(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const void* dat
     const int32_t k = y0 / q->sparse_rows;
     const int32_t lo = q->band_lo(k), hi = q->band_hi(k);
     if (y0 + rows > hi) return fail(PBX_E_BADARG, "rows %d+%d cross the end of band %d (rows %d..%d)", y0, rows, k, lo, hi);
-    const int bpp = bpp_of(q->pixel_type);
-    const uint64_t row = (uint64_t)q->size_x * bpp;
-    const bool gen = data == nullptr;
-    if (gen && q->gen_source == PBX_SRC_HOST) return fail(PBX_E_BADARG, "null data");
-    if (!gen && bytes < row * (uint64_t)rows)
-        return fail(PBX_E_BADARG, "%llu bytes for %d rows of %llu", (unsigned long long)bytes, rows, (unsigned long long)row);
+    *band = k;
+    return PBX_OK;
+}
+
+// One write of rows [y0, y0 + rows) of band k (band_of_rows) of a sparse plane, whatever fills
+// them: the first write of an absent band allocates it (within the budget, evicting idle planes /
+// bands), the last one publishes it.  `fill(band_dev)` puts the rows into the band (rows
+// [band_lo, band_hi) at the plane's pitch) on ctx->upload_stream and returns once they are
+// there; it runs under ctx->upload_mu.  The caller has checked its own arguments: from here on a
+// failure fails the band's whole load.
+template <class Fill>
+int band_load_rows(pbx_ctx* ctx, Plane* q, int32_t k, int32_t y0, int32_t rows, Fill&& fill) {
+    const int32_t lo = q->band_lo(k), hi = q->band_hi(k);
     if (ensure_device(ctx)) return PBX_E_INTERNAL;
     Band& b = q->bands[(size_t)k];
     bool alloc = false;
@@ -1985,15 +1992,7 @@ int band_write(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const void* dat
     {
         std::lock_guard<std::mutex> u(ctx->upload_mu);
         if (alloc) e = hipMemsetAsync(b.dev + (size_t)q->pitch * (size_t)(hi - lo), 0, 256, ctx->upload_stream);
-        uint8_t* dst = b.dev + (int64_t)(y0 - lo) * q->pitch;
-        if (e == hipSuccess && gen) {
-            e = launch_gen_plane(ctx->upload_stream, dst, q->pitch, q->size_x, y0, rows, q->pixel_type,
-                                 q->gen_source == PBX_SRC_GEN_FAKE ? GEN_FAKE : GEN_NOISE, q->gen_seed,
-                                 q->gen_plane_no, q->z, q->c, q->t);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->upload_stream);
-        } else if (e == hipSuccess) {
-            rc = upload_rows(ctx, dst, q->pitch, (const uint8_t*)data, row, (uint64_t)rows, ctx->upload_stream);
-        }
+        if (e == hipSuccess) rc = fill(b.dev);
     }
     if (e != hipSuccess) rc = fail(PBX_E_INTERNAL, "band write: %s", hipGetErrorString(e));
     if (rc) return leave_failed(rc);
@@ -2023,7 +2022,30 @@ int band_write(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const void* dat
     return PBX_OK;
 }
 
+// pbx_band_write: packed host rows, or (data == NULL on a generator plane) rows generated on
+// the GPU.
+int band_write(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const void* data, uint64_t bytes) {
+    int32_t k = 0;
+    if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
+    const int bpp = bpp_of(q->pixel_type);
+    const uint64_t row = (uint64_t)q->size_x * bpp;
+    const bool gen = data == nullptr;
+    if (gen && q->gen_source == PBX_SRC_HOST) return fail(PBX_E_BADARG, "null data");
+    if (!gen && bytes < row * (uint64_t)rows)
+        return fail(PBX_E_BADARG, "%llu bytes for %d rows of %llu", (unsigned long long)bytes, rows, (unsigned long long)row);
+    return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
+        uint8_t* dst = band_dev + (int64_t)(y0 - q->band_lo(k)) * q->pitch;
+        if (!gen) return upload_rows(ctx, dst, q->pitch, (const uint8_t*)data, row, (uint64_t)rows, ctx->upload_stream);
+        hipError_t e = launch_gen_plane(ctx->upload_stream, dst, q->pitch, q->size_x, y0, rows, q->pixel_type,
+                                        q->gen_source == PBX_SRC_GEN_FAKE ? GEN_FAKE : GEN_NOISE, q->gen_seed,
+                                        q->gen_plane_no, q->z, q->c, q->t);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->upload_stream);
+        return e == hipSuccess ? (int)PBX_OK : fail(PBX_E_INTERNAL, "band write: %s", hipGetErrorString(e));
+    });
+}
+
 }  // namespace
+extern "C" {
 
 int pbx_band_write(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const void* data, uint64_t bytes) {
     if (!ctx) return fail(PBX_E_BADARG, "null ctx");
@@ -2271,14 +2293,17 @@ struct ZarrPlan {
     uint64_t scratch = 0;
 };
 
-int zarr_plan(const pbx_plane_desc* d, const pbx_zarr_chunks* z, int bpp, uint64_t in_base,
-              uint32_t plane_idx, ZarrPlan& P) {
-    const int64_t gx = (d->size_x + z->chunk_x - 1) / z->chunk_x;
-    const int64_t gy = (d->size_y + z->chunk_y - 1) / z->chunk_y;
+// Chunk rows [cy0, cy1) of a plane size_x wide (full width, C order): z->offsets has
+// (cy1 - cy0) * gx + 1 entries and z->data holds those chunks only.  Chunk origins are plane
+// coordinates.  The whole plane is chunk rows [0, gy).
+int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_base, uint32_t plane_idx,
+              int64_t cy0, int64_t cy1, ZarrPlan& P) {
+    const int64_t gx = (size_x + z->chunk_x - 1) / z->chunk_x;
+    const int64_t n = gx * (cy1 - cy0);
     const uint64_t cb = (uint64_t)z->chunk_x * z->chunk_y * bpp;
     if (cb > 0x7fffffffull) return fail(PBX_E_BADARG, "chunk of %llu bytes too large", (unsigned long long)cb);
-    const uint64_t total = z->offsets[gx * gy];
-    for (int64_t i = 0; i < gx * gy; i++) {
+    const uint64_t total = z->offsets[n];
+    for (int64_t i = 0; i < n; i++) {
         const uint64_t o = z->offsets[i], len = z->offsets[i + 1] - o;
         const uint64_t ob = o + in_base;  // device offset in the launch's upload buffer
         if (z->offsets[i + 1] < o || z->offsets[i + 1] > total)
@@ -2286,7 +2311,7 @@ int zarr_plan(const pbx_plane_desc* d, const pbx_zarr_chunks* z, int bpp, uint64
         ZChunk c{};
         c.plane = plane_idx;
         c.x0 = (int32_t)((i % gx) * z->chunk_x);
-        c.y0 = (int32_t)((i / gx) * z->chunk_y);
+        c.y0 = (int32_t)((cy0 + i / gx) * z->chunk_y);
         c.nbytes = (uint32_t)cb;
         c.blocksize = (uint32_t)cb;
         c.typesize = 1;
@@ -2368,6 +2393,149 @@ int zarr_plan(const pbx_plane_desc* d, const pbx_zarr_chunks* z, int bpp, uint64
     return PBX_OK;
 }
 
+// pbx_zarr_chunks fields that can be checked without the plane.
+int zarr_chunks_check(const pbx_zarr_chunks* z) {
+    if (!z->offsets || (!z->data && z->codec != PBX_ZARR_RAW)) return fail(PBX_E_BADARG, "null argument");
+    if (z->chunk_x <= 0 || z->chunk_y <= 0) return fail(PBX_E_BADARG, "bad chunk shape");
+    if (z->codec < PBX_ZARR_RAW || z->codec > PBX_ZARR_ZLIB) return fail(PBX_E_BADARG, "bad codec %d", z->codec);
+    return PBX_OK;
+}
+
+// fill_bits (the sample's bit pattern) as bytes in the stored byte order
+uint64_t zarr_fill(uint64_t fill_bits, int bpp, bool little_endian) {
+    uint64_t fill = 0;
+    for (int j = 0; j < bpp; j++) {
+        const uint64_t byte = (fill_bits >> (8 * j)) & 0xff;
+        fill |= byte << (8 * (little_endian || bpp == 1 ? j : bpp - 1 - j));
+    }
+    return fill;
+}
+
+// The compressed bytes of one pbx_zarr_chunks in a launch's upload buffer.
+struct ZarrInput {
+    const uint8_t* data;
+    uint64_t used;  // bytes of data (offsets[last])
+    uint64_t base;  // where they go in the upload buffer (16-byte aligned)
+    uint64_t len;   // `used` rounded up to 16: the rest is zeroed
+};
+
+// One decode launch on stream `st`: uploads the chunk bytes `in` (in_bytes in all), runs the
+// decoders of P's streams and places P's chunks into the destinations `zp` (plane or band
+// bases and their row windows), then waits for it all.  The launch scratch (input, decoded
+// chunks, tables) comes from the context's device pool and goes back to it.  400 for a stream
+// a decoder rejects; rows already placed are then the caller's to discard.
+int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
+                      const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms) {
+    uint32_t counts[ZS_NKINDS], nstreams = 0;
+    std::vector<ZStream> all;
+    for (uint32_t k = 0; k < ZS_NKINDS; k++) {
+        counts[k] = (uint32_t)P.kind[k].size();
+        nstreams += counts[k];
+        all.insert(all.end(), P.kind[k].begin(), P.kind[k].end());
+    }
+    uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
+    ZStream* d_st = nullptr;
+    ZChunk* d_ch = nullptr;
+    ZPlane* d_pl = nullptr;
+    uint32_t* d_err = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    auto cleanup = [&] {
+        // queued copies, memsets or decoders may still write these blocks on an error path;
+        // the pool hands them to other streams' batches as soon as they are back
+        (void)hipStreamSynchronize(st);
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ch, (void*)d_pl, (void*)d_err})
+            if (q) ctx->dpool.put(q);
+        for (auto& x : ev) if (x) (void)hipEventDestroy(x);
+    };
+    hipError_t e = hipSuccess;
+    auto dget = [&](auto*& ptr, size_t bytes) {
+        if (e != hipSuccess) return;
+        ptr = (std::remove_reference_t<decltype(ptr)>)ctx->dpool.get(std::max<size_t>(bytes, 256), &e);
+    };
+    dget(d_in, in_bytes + 4096);  // decoder window over-read slack
+    if (P.scratch) dget(d_scr, P.scratch);
+    if (counts[ZS_ZSTD]) dget(d_lit, zstd_scratch_bytes(counts[ZS_ZSTD]));
+    if (nstreams) dget(d_st, sizeof(ZStream) * nstreams);
+    dget(d_ch, sizeof(ZChunk) * P.chunks.size());
+    dget(d_pl, sizeof(ZPlane) * zp.size());
+    dget(d_err, sizeof(uint32_t) * (nstreams + 1));
+    for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
+    if (e != hipSuccess) {
+        cleanup();
+        return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
+    }
+    for (size_t k = 0; k < in.size() && e == hipSuccess; k++) {
+        if (in[k].used) {
+            if (int rc = upload_staged(ctx, d_in + in[k].base, in[k].data, in[k].used, st)) {
+                cleanup();
+                return rc;
+            }
+        }
+        if (in[k].len > in[k].used) e = hipMemsetAsync(d_in + in[k].base + in[k].used, 0, in[k].len - in[k].used, st);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(d_in + in_bytes, 0, 4096, st);
+    if (e == hipSuccess && nstreams)
+        e = hipMemcpyAsync(d_st, all.data(), sizeof(ZStream) * nstreams, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(d_ch, P.chunks.data(), sizeof(ZChunk) * P.chunks.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_pl, zp.data(), sizeof(ZPlane) * zp.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nstreams + 1), st);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    if (e == hipSuccess) e = launch_zarr_decode(st, d_st, counts, d_in, d_scr, d_lit, d_err);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+    if (e == hipSuccess) e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
+    if (e == hipSuccess) e = hipEventRecord(ev[2], st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    std::vector<uint32_t> err(nstreams + 1, 0);
+    if (e == hipSuccess && nstreams)
+        e = hipMemcpy(err.data(), d_err, sizeof(uint32_t) * nstreams, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        cleanup();
+        return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
+    }
+    for (uint32_t s = 0; s < nstreams; s++)
+        if (err[s]) {
+            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd"};
+            uint32_t k = 0, first = 0;
+            while (s >= first + counts[k]) first += counts[k++];
+            cleanup();
+            return fail(PBX_E_BADARG, "corrupt chunk stream %u (%s, decoder code %u)", s, names[k], err[s]);
+        }
+    if (kernel_ms) {
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&b, ev[1], ev[2]);
+        kernel_ms[0] = a;
+        kernel_ms[1] = b;
+    }
+    cleanup();
+    return PBX_OK;
+}
+
+// pbx_band_write_zarr: the piece's covering chunk rows are planned on the host first (a
+// malformed piece never joins the band's load), then uploaded, decoded and placed under the
+// band state machine of band_load_rows, with the piece's rows as the placement window.
+int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_zarr_chunks* z, double* kernel_ms) {
+    int32_t k = 0;
+    if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
+    if (int rc = zarr_chunks_check(z)) return rc;
+    const int bpp = bpp_of(q->pixel_type);
+    const int64_t gx = (q->size_x + z->chunk_x - 1) / z->chunk_x;
+    const int64_t cy0 = y0 / z->chunk_y, cy1 = ((int64_t)y0 + rows + z->chunk_y - 1) / z->chunk_y;
+    ZarrPlan P;
+    if (int rc = zarr_plan(q->size_x, z, bpp, 0, 0, cy0, cy1, P)) return rc;
+    const uint64_t used = z->offsets[gx * (cy1 - cy0)], len = (used + 15) & ~15ull;
+    const std::vector<ZarrInput> in{ZarrInput{z->data, used, 0, len}};
+    return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
+        // rows keep their plane index: the destination is the band's virtual base, as in the
+        // tile kernels (pitch and the allocation are 256-byte aligned, so is the base)
+        const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
+                                            q->size_y, z->chunk_x, z->chunk_y, (uint32_t)bpp, 0,
+                                            zarr_fill(z->fill_bits, bpp, q->little_endian), y0, y0 + rows}};
+        return zarr_decode_place(ctx, ctx->upload_stream, P, zp, in, len, z->chunk_y, kernel_ms);
+    });
+}
+
 }  // namespace
 
 int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
@@ -2377,12 +2545,10 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     for (uint64_t k = 0; k < n; k++) {
         const pbx_plane_desc* d = &ds[k];
         const pbx_zarr_chunks* z = &zs[k];
-        if (!z->offsets || (!z->data && z->codec != PBX_ZARR_RAW)) return fail(PBX_E_BADARG, "null argument");
+        if (int rc = zarr_chunks_check(z)) return rc;
         if (!bpp_of(d->pixel_type)) return fail(PBX_E_BADARG, "bad pixel type %d", d->pixel_type);
         if (d->size_x <= 0 || d->size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
         if (d->resolution < 0) return fail(PBX_E_BADARG, "bad resolution");
-        if (z->chunk_x <= 0 || z->chunk_y <= 0) return fail(PBX_E_BADARG, "bad chunk shape");
-        if (z->codec < PBX_ZARR_RAW || z->codec > PBX_ZARR_ZLIB) return fail(PBX_E_BADARG, "bad codec %d", z->codec);
         keys.emplace_back(d->image_id, d->z, d->c, d->t, d->resolution);
     }
     {
@@ -2410,17 +2576,18 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     // host plan: metadata of every chunk of every plane, one upload buffer, one scratch
     ZarrPlan P;
     std::vector<uint64_t> in_base(n + 1, 0);
+    std::vector<ZarrInput> in(n);
     int32_t max_cy = 0;
     for (uint64_t k = 0; k < n; k++) {
         const pbx_plane_desc* d = &ds[k];
         const pbx_zarr_chunks* z = &zs[k];
         const int64_t gx = (d->size_x + z->chunk_x - 1) / z->chunk_x, gy = (d->size_y + z->chunk_y - 1) / z->chunk_y;
-        if (int rc = zarr_plan(d, z, bpp_of(d->pixel_type), in_base[k], (uint32_t)k, P)) return rc;
+        if (int rc = zarr_plan(d->size_x, z, bpp_of(d->pixel_type), in_base[k], (uint32_t)k, 0, gy, P)) return rc;
         in_base[k + 1] = in_base[k] + ((z->offsets[gx * gy] + 15) & ~15ull);
+        in[k] = ZarrInput{z->data, z->offsets[gx * gy], in_base[k], in_base[k + 1] - in_base[k]};
         max_cy = std::max(max_cy, z->chunk_y);
     }
     if (ensure_device(ctx)) return PBX_E_INTERNAL;
-    const uint64_t in_bytes = in_base[n];
     std::vector<Plane> ps(n);
     std::vector<ZPlane> zp(n);
     for (uint64_t k = 0; k < n; k++) {
@@ -2433,118 +2600,30 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
         p.pitch = ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255;
         p.bytes = (size_t)p.pitch * d->size_y + 256;
         p.band_rows = d->size_y;
-        uint64_t fill = 0;  // fill bytes in the stored byte order
-        for (int j = 0; j < bpp; j++) {
-            const uint64_t byte = (zs[k].fill_bits >> (8 * j)) & 0xff;
-            fill |= byte << (8 * (p.little_endian || bpp == 1 ? j : bpp - 1 - j));
-        }
         zp[k] = ZPlane{nullptr, p.pitch, d->size_x, d->size_y, zs[k].chunk_x, zs[k].chunk_y,
-                       (uint32_t)bpp, 0, fill};
+                       (uint32_t)bpp, 0, zarr_fill(zs[k].fill_bits, bpp, p.little_endian), 0, d->size_y};
     }
-    uint32_t counts[ZS_NKINDS], nstreams = 0;
-    std::vector<ZStream> all;
-    for (uint32_t k = 0; k < ZS_NKINDS; k++) {
-        counts[k] = (uint32_t)P.kind[k].size();
-        nstreams += counts[k];
-        all.insert(all.end(), P.kind[k].begin(), P.kind[k].end());
-    }
-    uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
-    ZStream* d_st = nullptr;
-    ZChunk* d_ch = nullptr;
-    ZPlane* d_pl = nullptr;
-    uint32_t* d_err = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    // launch scratch (input, decoded chunks, tables) comes from the context's device pool and
-    // goes back to it: only the planes themselves are new allocations
-    auto cleanup = [&](bool planes_too) {
-        // queued copies, memsets or decoders may still write these blocks on an error path;
-        // the pool hands them to other streams' batches as soon as they are back
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ch, (void*)d_pl, (void*)d_err})
-            if (q) ctx->dpool.put(q);
-        for (auto& x : ev) if (x) (void)hipEventDestroy(x);
-        if (planes_too)
-            for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
-    };
-    hipError_t e = hipSuccess;
-    auto dget = [&](auto*& ptr, size_t bytes) {
-        if (e != hipSuccess) return;
-        ptr = (std::remove_reference_t<decltype(ptr)>)ctx->dpool.get(std::max<size_t>(bytes, 256), &e);
-    };
     for (uint64_t k = 0; k < n; k++) {
         if (int rc = plane_alloc(ctx, ps[k].bytes, &ps[k].dev)) {
             const std::string msg = g_err;
-            cleanup(true);
+            for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
             g_err = msg;
             return rc;
         }
         zp[k].dev = ps[k].dev;
     }
-    dget(d_in, in_bytes + 4096);  // decoder window over-read slack
-    if (P.scratch) dget(d_scr, P.scratch);
-    if (counts[ZS_ZSTD]) dget(d_lit, zstd_scratch_bytes(counts[ZS_ZSTD]));
-    if (nstreams) dget(d_st, sizeof(ZStream) * nstreams);
-    dget(d_ch, sizeof(ZChunk) * P.chunks.size());
-    dget(d_pl, sizeof(ZPlane) * n);
-    dget(d_err, sizeof(uint32_t) * (nstreams + 1));
-    for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
-    if (e != hipSuccess) {
-        cleanup(true);
-        return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
-    }
-    for (uint64_t k = 0; k < n && e == hipSuccess; k++) {
-        const uint64_t len = in_base[k + 1] - in_base[k];
-        const int64_t gx = (ds[k].size_x + zs[k].chunk_x - 1) / zs[k].chunk_x;
-        const int64_t gy = (ds[k].size_y + zs[k].chunk_y - 1) / zs[k].chunk_y;
-        const uint64_t used = zs[k].offsets[gx * gy];
-        if (used) {
-            if (int rc = upload_staged(ctx, d_in + in_base[k], zs[k].data, used, ctx->stream)) {
-                cleanup(true);
-                return rc;
-            }
-        }
-        if (len > used) e = hipMemsetAsync(d_in + in_base[k] + used, 0, len - used, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(d_in + in_bytes, 0, 4096, ctx->stream);
-    if (e == hipSuccess && nstreams)
-        e = hipMemcpyAsync(d_st, all.data(), sizeof(ZStream) * nstreams, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_ch, P.chunks.data(), sizeof(ZChunk) * P.chunks.size(), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pl, zp.data(), sizeof(ZPlane) * n, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nstreams + 1), ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
-    if (e == hipSuccess)
-        e = launch_zarr_decode(ctx->stream, d_st, counts, d_in, d_scr, d_lit, d_err);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
-    if (e == hipSuccess)
-        e = launch_zarr_place(ctx->stream, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
-    for (uint64_t k = 0; k < n && e == hipSuccess; k++)
+    hipError_t e = hipSuccess;
+    for (uint64_t k = 0; k < n && e == hipSuccess; k++)  // over-read slack after the last row
         e = hipMemsetAsync(ps[k].dev + (size_t)ps[k].pitch * ps[k].size_y, 0, 256, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    std::vector<uint32_t> err(nstreams + 1, 0);
-    if (e == hipSuccess && nstreams)
-        e = hipMemcpy(err.data(), d_err, sizeof(uint32_t) * nstreams, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        cleanup(true);
-        return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
+    int rc = e == hipSuccess ? zarr_decode_place(ctx, ctx->stream, P, zp, in, in_base[n], max_cy, kernel_ms)
+                             : fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
+    if (rc) {
+        const std::string msg = g_err;
+        (void)hipStreamSynchronize(ctx->stream);
+        for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
+        g_err = msg;
+        return rc;
     }
-    for (uint32_t s = 0; s < nstreams; s++)
-        if (err[s]) {
-            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd"};
-            uint32_t k = 0, first = 0;
-            while (s >= first + counts[k]) first += counts[k++];
-            cleanup(true);
-            return fail(PBX_E_BADARG, "corrupt chunk stream %u (%s, decoder code %u)", s, names[k], err[s]);
-        }
-    if (kernel_ms) {
-        float a = 0, b = 0;
-        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&b, ev[1], ev[2]);
-        kernel_ms[0] = a;
-        kernel_ms[1] = b;
-    }
-    cleanup(false);
     if (int rc = registry_insert(ctx, ps, plane_ids)) {  // keys re-checked at insertion
         const std::string msg = g_err;
         for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
@@ -2557,6 +2636,19 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
 int pbx_plane_register_zarr(pbx_ctx* ctx, const pbx_plane_desc* d, const pbx_zarr_chunks* z,
                             uint64_t* plane_id, double* kernel_ms) {
     return pbx_planes_register_zarr(ctx, 1, d, z, plane_id, kernel_ms);
+}
+
+int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
+                        double* kernel_ms) {
+    if (!ctx || !z) return fail(PBX_E_BADARG, "null argument");
+    int rc;
+    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
+    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
+    rc = band_write_zarr(ctx, q, y0, rows, z, kernel_ms);
+    const std::string msg = g_err;
+    unpin_one(ctx, q);
+    g_err = msg;
+    return rc;
 }
 
 int pbx_plane_release(pbx_ctx* ctx, uint64_t id) {

@@ -143,6 +143,7 @@ EXPORTS = [
     "pbx_plane_create_sparse", "pbx_band_write", "pbx_plane_band_info", "pbx_result_spans",
     "pbx_test_stall_batch", "pbx_band_abort", "pbx_test_fail_band_write",
     "pbx_set_deflate_strategy", "pbx_get_deflate_strategy", "pbx_batch_lz_modes",
+    "pbx_band_write_zarr",
 ]
 
 _lib = None
@@ -221,6 +222,8 @@ def lib() -> ctypes.CDLL:
     L.pbx_test_fail_band_write.argtypes = [vp, u64]
     L.pbx_plane_create_sparse.argtypes = [vp, ctypes.POINTER(PbxPlaneDesc), i32, i32, i32, ctypes.POINTER(u64)]
     L.pbx_band_write.argtypes = [vp, u64, i32, i32, vp, u64]
+    L.pbx_band_write_zarr.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxZarrChunks),
+                                      ctypes.POINTER(ctypes.c_double)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -395,12 +398,20 @@ def _lead_axes(ndim: int, axes: Optional[Sequence[str]]) -> List[str]:
     return ["t", "c", "z"][3 - (ndim - 2):]
 
 
-def zarr_plane_spec(array_dir: str, image_id: int, z: int, c: int, t: int, level: int = 0,
-                    meta: Optional[dict] = None, axes: Optional[Sequence] = None) -> dict:
-    """register_zarr_planes() arguments for plane (z, c, t) of an NGFF array directory (axes:
-    the multiscales "axes" of the image, else NGFF order t, c, z, y, x with fewer leading axes
-    dropped from the left): chunk files named by dimension_separator "." or "/", absent
-    files = fill_value.  `level` is the stored pyramid level (0 = full resolution)."""
+def _read_chunk_file(path: str) -> Optional[bytes]:
+    """A chunk file's bytes, or None when the file is absent (the chunk reads as fill_value)."""
+    try:
+        with open(path, "rb") as f:
+            return f.read()
+    except FileNotFoundError:
+        return None
+
+
+def _zarr_chunk_rows(array_dir: str, z: int, c: int, t: int, meta: Optional[dict],
+                     axes: Optional[Sequence], y0: Optional[int] = None, rows: int = 0) -> dict:
+    """What zarr_plane_spec and zarr_band_spec share: the array's geometry, codec, byte order
+    and fill, and the chunk files (full width, C order) of the chunk rows covering plane rows
+    [y0, y0 + rows) of plane (z, c, t), or of every chunk row (y0 None)."""
     import numpy as np
     meta = meta or zarr_array_meta(array_dir)
     shape, chunk, dt = meta["shape"], meta["chunks"], meta["dtype"]
@@ -415,17 +426,38 @@ def zarr_plane_spec(array_dir: str, image_id: int, z: int, c: int, t: int, level
             raise PbxError(404, "plane (z=%d, c=%d, t=%d) outside the array" % (z, c, t))
     sep = meta.get("dimension_separator", ".")
     sy, sx, cy, cx = shape[-2], shape[-1], chunk[-2], chunk[-1]
+    if y0 is None:
+        y0, rows = 0, sy
+    elif rows < 0 or y0 < 0 or y0 + rows > sy:
+        raise PbxError(400, "rows %d+%d outside the array (%d rows)" % (y0, rows, sy))
     chunks = []
-    for j in range(-(-sy // cy)):
+    for j in range(y0 // cy, -(-(y0 + rows) // cy)):
         for i in range(-(-sx // cx)):
-            path = os.path.join(array_dir, sep.join(str(v) for v in lead + [j, i]))
-            chunks.append(open(path, "rb").read() if os.path.exists(path) else None)
+            chunks.append(_read_chunk_file(os.path.join(array_dir, sep.join(str(v) for v in lead + [j, i]))))
     native = np.dtype(dt).newbyteorder("=")
     fill_bits = int(np.array([meta.get("fill_value") or 0], dtype=native).view("u%d" % native.itemsize)[0])
-    return dict(image_id=image_id, z=z, c=c, t=t, level=level,
-                pixel_type=_ZARR_DTYPES[dt[1:]], size_x=sx, size_y=sy, chunk_x=cx, chunk_y=cy,
+    return dict(pixel_type=_ZARR_DTYPES[dt[1:]], size_x=sx, size_y=sy, chunk_x=cx, chunk_y=cy,
                 codec=None if comp is None else comp.get("id"), chunks=chunks,
                 big_endian=dt[0] != "<", fill_bits=fill_bits)
+
+
+def zarr_plane_spec(array_dir: str, image_id: int, z: int, c: int, t: int, level: int = 0,
+                    meta: Optional[dict] = None, axes: Optional[Sequence] = None) -> dict:
+    """register_zarr_planes() arguments for plane (z, c, t) of an NGFF array directory (axes:
+    the multiscales "axes" of the image, else NGFF order t, c, z, y, x with fewer leading axes
+    dropped from the left): chunk files named by dimension_separator "." or "/", absent
+    files = fill_value.  `level` is the stored pyramid level (0 = full resolution)."""
+    return dict(_zarr_chunk_rows(array_dir, z, c, t, meta, axes), image_id=image_id, z=z, c=c, t=t,
+                level=level)
+
+
+def zarr_band_spec(array_dir: str, z: int, c: int, t: int, y0: int, rows: int,
+                   meta: Optional[dict] = None, axes: Optional[Sequence] = None) -> dict:
+    """band_write_zarr() arguments for rows [y0, y0 + rows) of plane (z, c, t) of an NGFF array
+    directory: only the files of the chunk rows that cover them are read (paths, axes and
+    absent files as in zarr_plane_spec).  rows == 0 reads no file: the array's geometry, codec
+    and byte order alone."""
+    return dict(_zarr_chunk_rows(array_dir, z, c, t, meta, axes, y0, rows), y0=y0, rows=rows)
 
 
 def pack_chunks(chunks: Sequence[Optional[bytes]]):
@@ -772,6 +804,24 @@ class PixelsService:
         else:
             _check(lib().pbx_band_write(self._h, plane_id, y0, rows, data, len(data)))
 
+    def band_write_zarr(self, plane_id: int, y0: int, rows: int, chunk_x: int, chunk_y: int,
+                        codec: Optional[str], chunks: Sequence[Optional[bytes]], fill_bits: int = 0,
+                        timing: bool = False):
+        """pbx_band_write_zarr: rows [y0, y0 + rows) of one band, decoded on the GPU from the
+        Zarr chunk rows y0 // chunk_y .. ceil((y0 + rows) / chunk_y) - 1 that cover them (each
+        full width, C order; None or b"" = missing chunk -> fill; or pack_chunks()' (data,
+        offsets) pair).  codec as register_zarr_plane.  With timing=True returns the decode /
+        placement kernels' device ms."""
+        if codec not in ZARR_CODECS:
+            raise PbxError(400, "unsupported Zarr compressor %r" % (codec,))
+        data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
+        zc = PbxZarrChunks()
+        zc.chunk_x, zc.chunk_y, zc.codec = chunk_x, chunk_y, ZARR_CODECS[codec]
+        zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, fill_bits
+        ms = (ctypes.c_double * 2)()
+        _check(lib().pbx_band_write_zarr(self._h, plane_id, y0, rows, ctypes.byref(zc), ms))
+        return (ms[0], ms[1]) if timing else None
+
     def band_abort(self, plane_id: int, y0: int) -> None:
         """pbx_band_abort: give back the band holding row y0 when its load is abandoned."""
         _check(lib().pbx_band_abort(self._h, plane_id, y0))
@@ -866,16 +916,23 @@ class PixelsService:
         """Region-proportional loading (TileRequestHandler.java:102-109 reads only the region):
         the sparse plane of the key (created if absent, bands of self.sparse_band_rows rows) gets
         the bands that rows [y, y + h) cover, each read from `source` once; bands another
-        caller is loading are waited for.  Returns the plane id."""
+        caller is loading are waited for.  A source with chunk-level access
+        (PixelSource.band_chunks) hands over the Zarr chunk rows covering each band, which are
+        decoded on the GPU (band_write_zarr); any other source is read with read_rows.  Returns
+        the plane id."""
         self.declare_image(pixels)
         key = (pixels.image_id, z, c, t, level)
         sx, sy = source.level_size(pixels, level)
+        band_chunks = getattr(source, "band_chunks", None)
         with self._exclusive(key):
             found = self.lookup_plane(*key)
             if found is None or found[1] == PS_EVICTED:
+                # chunks stay in the array's byte order (no rows: nothing is read for this)
+                sp = band_chunks(pixels, z, c, t, level, 0, 0) if band_chunks is not None else None
                 try:
                     pid = self.create_sparse_plane(pixels.image_id, z, c, t, pixels.pixel_type, sx, sy,
-                                                   self.sparse_band_rows, level, own=own)
+                                                   self.sparse_band_rows, level, own=own,
+                                                   big_endian=sp["big_endian"] if sp is not None else True)
                 except PbxError as e:
                     if e.status != E_EXISTS:
                         raise
@@ -898,8 +955,14 @@ class PixelsService:
                     if st == BS_ABSENT:
                         r0, r1 = k * B, min((k + 1) * B, sy)
                         try:
-                            self.band_write(pid, r0, r1 - r0,
-                                            source.read_rows(pixels, z, c, t, level, r0, r1 - r0))
+                            sp = (band_chunks(pixels, z, c, t, level, r0, r1 - r0)
+                                  if band_chunks is not None else None)
+                            if sp is not None:
+                                self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
+                                                     sp["codec"], sp["chunks"], sp["fill_bits"])
+                            else:
+                                self.band_write(pid, r0, r1 - r0,
+                                                source.read_rows(pixels, z, c, t, level, r0, r1 - r0))
                             break
                         except PbxError as e:
                             if e.status != E_EXISTS:  # another binding loads it: wait
@@ -1211,6 +1274,63 @@ class PixelSource:
                   rows: int) -> bytes:
         """getTileDirect(z, c, t, 0, y0, sizeX, rows) at that level: packed big-endian rows."""
         raise NotImplementedError
+
+    def band_chunks(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
+                    rows: int) -> Optional[dict]:
+        """Optional, for storage that is Zarr: the chunk rows covering rows [y0, y0 + rows) of
+        the plane at that level, as zarr_band_spec returns them (chunk_x, chunk_y, codec,
+        chunks, fill_bits, big_endian = the array's byte order); load_bands then has them
+        decoded on the GPU instead of calling read_rows.  rows == 0 asks for the byte order and
+        geometry only and must read no chunk.  None (the default): no chunk-level access."""
+        return None
+
+
+class NgffSource(PixelSource):
+    """NGFF multiscale images on disk, {image_id: image directory} -- what ZarrPixelsService
+    opens per image (config.yaml:18): dataset k of .zattrs "multiscales"[0] is stored level k.
+    Planes are loaded band by band from the chunk files covering the requested rows
+    (band_chunks -> zarr_band_spec), so it needs a service with sparse_band_rows."""
+
+    def __init__(self, images: Mapping[int, str]):
+        import threading
+        self.images = dict(images)
+        self._opened: Dict[int, tuple] = {}
+        self._lock = threading.Lock()
+
+    def _open(self, image_id: int):
+        """(axes, [(array directory, .zarray)] per dataset) of an image, read once."""
+        with self._lock:
+            ent = self._opened.get(image_id)
+            if ent is None:
+                ms, root = ngff_multiscales(self.images[image_id])
+                dirs = [os.path.join(root, ds["path"]) for ds in ms["datasets"]]
+                ent = self._opened[image_id] = (ms.get("axes"), [(d, zarr_array_meta(d)) for d in dirs])
+            return ent
+
+    def get_pixels(self, image_id: int) -> Optional[Pixels]:
+        if image_id not in self.images:
+            return None
+        axes, levels = self._open(image_id)
+        meta = levels[0][1]
+        ext = {"t": 1, "c": 1, "z": 1}
+        ext.update(zip(_lead_axes(len(meta["shape"]), axes), meta["shape"][:-2]))
+        return Pixels(image_id, _ZARR_DTYPES[meta["dtype"][1:]], meta["shape"][-1], meta["shape"][-2],
+                      ext["z"], ext["c"], ext["t"], levels=len(levels))
+
+    def level_size(self, pixels: Pixels, level: int) -> Tuple[int, int]:
+        shape = self._open(pixels.image_id)[1][level][1]["shape"]
+        return shape[-1], shape[-2]
+
+    def band_chunks(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
+                    rows: int) -> Optional[dict]:
+        axes, levels = self._open(pixels.image_id)
+        adir, meta = levels[level]
+        return zarr_band_spec(adir, z, c, t, y0, rows, meta, axes)
+
+    def read_rows(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
+                  rows: int) -> bytes:
+        raise PbxError(E_BADARG, "NgffSource hands over Zarr chunks, not rows: serve it from a "
+                       "PixelsService with sparse_band_rows (whole planes: register_ngff_image)")
 
 
 # ----------------------------------------------------------------- TileRequestHandler
