@@ -299,6 +299,37 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* des
  * kernel_ms (may be NULL): [0] device ms of the decode kernels, [1] of the placement kernel. */
 int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                         const pbx_zarr_chunks* chunks, double* kernel_ms);
+
+/* Chunks that hold more than one plane (.zarray "chunks" with a leading t / c / z extent
+ * above 1: bioformats2raw --chunk_depth, dask volumes such as [1, 1, 16, 256, 256]).  A LAYER
+ * is the gy * gx chunk files that share one set of leading chunk indices, as a pbx_zarr_chunks
+ * (C order, data / offsets / missing chunks as above); every chunk of it decodes to
+ * chunk_planes * chunk_y * chunk_x samples in C order, slice-major (edge chunks along the
+ * leading axes are full, as in x and y; blosc nbytes = that product * bytes per sample, which
+ * must be <= 2^31 - 1).  A plane's SLICE is its index inside the chunk: the C-order flattening
+ * of (index mod chunk extent) over the leading axes -- chunks [1, 2, 4, cy, cx] give
+ * slice = (c % 2) * 4 + z % 4. */
+typedef struct pbx_zarr_slice { uint32_t layer, slice; } pbx_zarr_slice;
+/* pbx_planes_register_zarr for deep chunks: plane k (descs[k]) is slice refs[k].slice of every
+ * chunk of layers[refs[k].layer], whose chunks hold chunk_planes[layer] planes.  Every chunk
+ * is uploaded and decoded ONCE, however many planes are cut from it.  Keys, statuses and
+ * all-or-none are pbx_planes_register_zarr's; 400 also for a slice >= chunk_planes,
+ * chunk_planes < 1, a layer that no plane names, and planes of one layer that disagree on
+ * size, pixel type or byte order.  blosc blocks (compressed independently) that hold no byte
+ * of a wanted slice are not decoded.  With every chunk_planes == 1 this is
+ * pbx_planes_register_zarr of chunks[k] = layers[refs[k].layer]. */
+int pbx_planes_register_zarr_deep(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
+                                  const pbx_zarr_slice* refs, uint64_t n_layers,
+                                  const pbx_zarr_chunks* layers, const int32_t* chunk_planes,
+                                  uint64_t* plane_ids, double* kernel_ms);
+/* pbx_band_write_zarr from chunks that hold chunk_planes planes: the rows come from slice
+ * `slice` of the covering chunk rows.  Every rule of pbx_band_write_zarr holds; only the blosc
+ * blocks that hold a byte of the slice's wanted rows are decoded (zlib chunks, raw chunks and
+ * memcpyed frames are taken whole).  400 for chunk_planes < 1 or slice outside
+ * [0, chunk_planes).  chunk_planes == 1 is pbx_band_write_zarr. */
+int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                             const pbx_zarr_chunks* chunks, int32_t chunk_planes, int32_t slice,
+                             double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -518,6 +549,16 @@ int pbx_test_huffman(pbx_ctx* ctx, const uint32_t* hist, const uint32_t* sl_last
  * histogram words and the match records per segment, segments in batch order), compared by
  * tests/ with the CPU emulator.  nseg must equal the batch's segment count. */
 int pbx_test_batch_lz77(pbx_ctx* ctx, pbx_batch* b, uint32_t* hist, uint32_t* mrec, uint64_t nseg);
+
+/* Test hook: the host planner of the Zarr decode alone (no context, no device call).  Plans
+ * slices[0 .. nslices) of `chunks` (a layer of chunk_planes-deep chunks) for a plane of
+ * size_x x size_y samples of bpp bytes: rows == 0 plans the whole plane (registration: every
+ * chunk row, offsets as pbx_planes_register_zarr_deep), else rows [y0, y0 + rows) (offsets of
+ * the covering chunk rows, as pbx_band_write_zarr_deep).  out: streams planned, the sum of
+ * their decoded lengths, blosc blocks skipped, scratch bytes.  400 as the real calls. */
+int pbx_test_zarr_plan(const pbx_zarr_chunks* chunks, int32_t size_x, int32_t size_y, int32_t bpp,
+                       int32_t chunk_planes, const int32_t* slices, int32_t nslices, int32_t y0,
+                       int32_t rows, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

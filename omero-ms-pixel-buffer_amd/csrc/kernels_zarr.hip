@@ -1152,7 +1152,10 @@ __global__ __launch_bounds__(256) void k_zarr_copy(const ZStream* __restrict__ s
 // aligned 16-byte group of a plane row (16 / bpp samples): unshuffled chunks are one 16-byte
 // load, shuffled ones one load of 16 / bpp bytes from each byte plane, interleaved with byte
 // permutes (v_perm_b32).  Groups straddling a blosc block, row tails and unaligned rows take
-// the sample-by-sample path.
+// the sample-by-sample path.  A chunk that holds several planes (ZChunk::e0 = the slice's first
+// element) has one ZChunk per wanted plane, all on the same decoded bytes: element indices start
+// at e0, so blosc blocks straddle slices and rows like they straddle rows, and only bytes of the
+// slice's rows [r0, r1) are read (the planner leaves the other blocks undecoded).
 constexpr uint32_t ZP_ROWS = 16;
 
 __device__ __forceinline__ uint32_t zperm(uint32_t hi, uint32_t lo, uint32_t sel) {
@@ -1206,6 +1209,7 @@ __global__ __launch_bounds__(256) void k_zarr_place(const ZChunk* __restrict__ c
     if (r0 >= r1) return;  // wholly outside the window (or below the plane)
     const uint8_t* s = (c.flags & ZC_INPUT ? input : scratch) + c.src;
     const uint32_t ts = c.typesize, bs = c.blocksize, nb = c.nbytes;
+    const uint32_t e0 = c.e0;  // the plane's slice of a chunk that holds several planes
     const bool missing = (c.flags & ZC_MISSING) != 0;
     const bool bit = (c.flags & ZC_BITSHUF) != 0;
     const uint32_t G = 16 / bpp;  // samples per 16-byte group
@@ -1218,12 +1222,13 @@ __global__ __launch_bounds__(256) void k_zarr_place(const ZChunk* __restrict__ c
         const int32_t groups = w8 >> 3, total = (r1 - r0) * groups;
         for (int32_t g = (int32_t)threadIdx.x; g < total; g += 256) {
             const int32_t rr = g / groups, r = r0 + rr, col = 8 * (g - rr * groups);
-            const uint32_t e = (uint32_t)r * (uint32_t)cw + (uint32_t)col;
+            const uint32_t e = e0 + (uint32_t)r * (uint32_t)cw + (uint32_t)col;
             const uint32_t B = e * bpp, blk = B / bs;
             const uint32_t bsize = nb - blk * bs < bs ? nb - blk * bs : bs, ne = bsize / ts;
             uint8_t* o = base + (int64_t)r * pitch + (int64_t)col * bpp;
-            const uint32_t i = (B - blk * bs) / ts;  // element index in the block (multiple of 8)
-            if (bsize < ts || (ne & 7u) || i + 8 > ne) {
+            const uint32_t i = (B - blk * bs) / ts;  // element index in the block: a multiple of 8 unless
+            // the blocks before it hold a number of elements that is not (then: byte by byte)
+            if (bsize < ts || (ne & 7u) || (i & 7u) || i + 8 > ne) {
                 for (uint32_t q = 0; q < 8 * bpp; q++) o[q] = (uint8_t)zsample_byte(s, ts, bs, nb, e + q / bpp, bpp, q % bpp, true);
                 continue;
             }
@@ -1243,7 +1248,7 @@ __global__ __launch_bounds__(256) void k_zarr_place(const ZChunk* __restrict__ c
         for (int32_t r = r0; r < r1; r++) {  // row tails (and chunks whose width is not 8k)
             uint8_t* o = base + (int64_t)r * pitch;
             for (int32_t col = w8 + (int32_t)threadIdx.x; col < w; col += 256) {
-                const uint32_t e = (uint32_t)r * (uint32_t)cw + (uint32_t)col;
+                const uint32_t e = e0 + (uint32_t)r * (uint32_t)cw + (uint32_t)col;
                 for (uint32_t j = 0; j < bpp; j++) o[(int64_t)col * bpp + j] = (uint8_t)zsample_byte(s, ts, bs, nb, e, bpp, j, true);
             }
         }
@@ -1261,7 +1266,7 @@ __global__ __launch_bounds__(256) void k_zarr_place(const ZChunk* __restrict__ c
                 for (uint32_t j = 0; j < 4; j++) f |= (uint32_t)(fill >> (8 * (j % bpp)) & 0xffu) << (8 * j);
                 o = make_uint4(f, f, f, f);
             } else {
-                const uint32_t e = (uint32_t)r * (uint32_t)cw + (uint32_t)col;
+                const uint32_t e = e0 + (uint32_t)r * (uint32_t)cw + (uint32_t)col;
                 if (ts <= 1 || bpp == 1) {
                     __builtin_memcpy(&o, s + (size_t)e * bpp, 16);
                 } else {
@@ -1301,7 +1306,7 @@ __global__ __launch_bounds__(256) void k_zarr_place(const ZChunk* __restrict__ c
     for (int32_t r = r0; r < r1; r++) {  // the rest of every row, sample by sample
         uint8_t* o = base + (int64_t)r * pitch;
         for (int32_t col = wg + (int32_t)threadIdx.x; col < w; col += 256) {
-            const uint32_t e = (uint32_t)r * (uint32_t)cw + (uint32_t)col;
+            const uint32_t e = e0 + (uint32_t)r * (uint32_t)cw + (uint32_t)col;
             for (uint32_t j = 0; j < bpp; j++) {
                 const uint32_t v = missing ? (uint32_t)(fill >> (8 * j)) & 0xffu : zsample_byte(s, ts, bs, nb, e, bpp, j);
                 o[(int64_t)col * bpp + j] = (uint8_t)v;

@@ -109,8 +109,11 @@ struct ZChunk {
                                           // with ZC_BITSHUF the bit-shuffle element size)
     uint32_t flags;                       // ZC_*
     int32_t x0, y0;                       // chunk origin in the plane
-    uint32_t plane, pad;                  // index into the ZPlane table of the launch
+    uint32_t plane;                       // index into the ZPlane table of the launch
+    uint32_t e0;                          // first element of the plane's slice in the decoded chunk
+                                          // (slice * chunk_y * chunk_x; 0 for one plane per chunk)
 };
+static_assert(sizeof(ZChunk) == 40, "ZChunk is uploaded as is");
 struct ZPlane {                           // a destination plane of one decode launch
     uint8_t* dev;                         // row 0 of the plane (a band: its virtual base)
     int64_t pitch;

@@ -2291,17 +2291,39 @@ struct ZarrPlan {
     std::vector<ZStream> kind[ZS_NKINDS];  // streams by decoder (enum ZS_*)
     std::vector<ZChunk> chunks;
     uint64_t scratch = 0;
+    uint64_t skipped = 0;  // blosc blocks left undecoded (deep chunks only)
+};
+
+// A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
+// and its index in the launch's ZPlane table.
+struct ZarrWant {
+    uint32_t slice, plane;
 };
 
 // Chunk rows [cy0, cy1) of a plane size_x wide (full width, C order): z->offsets has
 // (cy1 - cy0) * gx + 1 entries and z->data holds those chunks only.  Chunk origins are plane
-// coordinates.  The whole plane is chunk rows [0, gy).
-int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_base, uint32_t plane_idx,
-              int64_t cy0, int64_t cy1, ZarrPlan& P) {
+// coordinates.  The whole plane is chunk rows [0, gy).  Every chunk holds `depth` planes
+// (slice-major) and gets one ZChunk per wanted plane, all on the one decoded copy.  With
+// depth > 1 only the blosc blocks that hold a byte of plane rows [y_lo, y_hi) of a wanted slice
+// get streams (include/pbx.h); scratch stays sized and addressed for whole chunks.
+int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_base, int64_t cy0, int64_t cy1,
+              int32_t depth, const std::vector<ZarrWant>& want, int64_t y_lo, int64_t y_hi, ZarrPlan& P) {
     const int64_t gx = (size_x + z->chunk_x - 1) / z->chunk_x;
     const int64_t n = gx * (cy1 - cy0);
-    const uint64_t cb = (uint64_t)z->chunk_x * z->chunk_y * bpp;
-    if (cb > 0x7fffffffull) return fail(PBX_E_BADARG, "chunk of %llu bytes too large", (unsigned long long)cb);
+    const uint64_t pb = (uint64_t)z->chunk_x * z->chunk_y * bpp;  // one plane of the chunk
+    if (pb > 0x7fffffffull || pb * (uint64_t)depth > 0x7fffffffull)
+        return fail(PBX_E_BADARG, "chunk of %llu bytes too large", (unsigned long long)(pb * (uint64_t)depth));
+    const uint64_t cb = pb * (uint64_t)depth, rowb = (uint64_t)z->chunk_x * bpp;
+    const uint32_t pe = (uint32_t)z->chunk_x * (uint32_t)z->chunk_y;
+    static const bool no_skip = getenv("PBX_ZARR_NO_BLOCK_SKIP") != nullptr;  // A/B: decode every block
+    const bool skip = depth > 1 && !no_skip;
+    auto emit = [&](ZChunk c) {
+        for (const ZarrWant& w : want) {
+            c.plane = w.plane;
+            c.e0 = w.slice * pe;
+            P.chunks.push_back(c);
+        }
+    };
     const uint64_t total = z->offsets[n];
     for (int64_t i = 0; i < n; i++) {
         const uint64_t o = z->offsets[i], len = z->offsets[i + 1] - o;
@@ -2309,7 +2331,6 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
         if (z->offsets[i + 1] < o || z->offsets[i + 1] > total)
             return fail(PBX_E_BADARG, "chunk %lld: bad offsets", (long long)i);
         ZChunk c{};
-        c.plane = plane_idx;
         c.x0 = (int32_t)((i % gx) * z->chunk_x);
         c.y0 = (int32_t)((cy0 + i / gx) * z->chunk_y);
         c.nbytes = (uint32_t)cb;
@@ -2317,7 +2338,7 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
         c.typesize = 1;
         if (len == 0) {
             c.flags = ZC_MISSING;
-            P.chunks.push_back(c);
+            emit(c);
             continue;
         }
         if (z->codec == PBX_ZARR_RAW) {
@@ -2325,7 +2346,7 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
                                       (unsigned long long)len, (unsigned long long)cb);
             c.src = ob;
             c.flags = ZC_INPUT;
-            P.chunks.push_back(c);
+            emit(c);
             continue;
         }
         const uint64_t dst = P.scratch;
@@ -2333,7 +2354,7 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
             if (len > 0xffffffffull) return fail(PBX_E_BADARG, "chunk %lld too large", (long long)i);
             P.kind[ZS_ZLIB].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)cb, ZS_ZLIB, 0});
             c.src = dst;
-            P.chunks.push_back(c);
+            emit(c);
             P.scratch += (cb + 255) & ~255ull;
             continue;
         }
@@ -2350,7 +2371,7 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
             if (16ull + nbytes > cbytes) return fail(PBX_E_BADARG, "chunk %lld: short memcpyed frame", (long long)i);
             c.src = ob + 16;
             c.flags = ZC_INPUT;
-            P.chunks.push_back(c);
+            emit(c);
             continue;
         }
         const uint32_t codec = flags >> 5;  // 0 blosclz, 1 lz4 / lz4hc, 2 snappy, 3 zlib, 4 zstd
@@ -2361,9 +2382,23 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
         if (bs == 0 || bs > nbytes || (bs % ts)) return fail(PBX_E_BADARG, "chunk %lld: blosc blocksize %u", (long long)i, bs);
         const uint32_t nblocks = (nbytes + bs - 1) / bs, leftover = nbytes % bs;
         if (16ull + 4ull * nblocks > cbytes) return fail(PBX_E_BADARG, "chunk %lld: short block table", (long long)i);
+        // the chunk's rows of the wanted window, the same in every wanted slice
+        const int64_t ra = std::max<int64_t>(y_lo - c.y0, 0), rb = std::min<int64_t>(y_hi - c.y0, z->chunk_y);
         for (uint32_t b = 0; b < nblocks; b++) {
             const bool is_left = leftover && b == nblocks - 1;
             const uint32_t bsize = is_left ? leftover : bs;
+            if (skip) {
+                const uint64_t b0 = (uint64_t)b * bs, b1 = b0 + bsize;
+                bool needed = false;
+                for (size_t k = 0; k < want.size() && !needed && ra < rb; k++) {
+                    const uint64_t s0 = want[k].slice * pb;
+                    needed = b0 < s0 + (uint64_t)rb * rowb && s0 + (uint64_t)ra * rowb < b1;
+                }
+                if (!needed) {
+                    P.skipped++;
+                    continue;
+                }
+            }
             const bool split = !(flags & 0x10) && ts <= 16 && bsize / ts >= 128 && !is_left;
             const uint32_t nsp = split ? ts : 1, neb = bsize / nsp;
             if (neb * nsp != bsize) return fail(PBX_E_BADARG, "chunk %lld: block %u not a multiple of typesize", (long long)i, b);
@@ -2387,7 +2422,7 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
         } else {
             c.typesize = (flags & 0x1) ? ts : 1;
         }
-        P.chunks.push_back(c);
+        emit(c);
         P.scratch += (cb + 255) & ~255ull;
     }
     return PBX_OK;
@@ -2398,6 +2433,13 @@ int zarr_chunks_check(const pbx_zarr_chunks* z) {
     if (!z->offsets || (!z->data && z->codec != PBX_ZARR_RAW)) return fail(PBX_E_BADARG, "null argument");
     if (z->chunk_x <= 0 || z->chunk_y <= 0) return fail(PBX_E_BADARG, "bad chunk shape");
     if (z->codec < PBX_ZARR_RAW || z->codec > PBX_ZARR_ZLIB) return fail(PBX_E_BADARG, "bad codec %d", z->codec);
+    return PBX_OK;
+}
+
+// A slice of chunks that hold `depth` planes.
+int zarr_slice_check(int32_t depth, int64_t slice) {
+    if (depth < 1) return fail(PBX_E_BADARG, "chunk_planes %d < 1", depth);
+    if (slice < 0 || slice >= depth) return fail(PBX_E_BADARG, "slice %lld outside chunks of %d planes", (long long)slice, depth);
     return PBX_OK;
 }
 
@@ -2515,15 +2557,19 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
 // pbx_band_write_zarr: the piece's covering chunk rows are planned on the host first (a
 // malformed piece never joins the band's load), then uploaded, decoded and placed under the
 // band state machine of band_load_rows, with the piece's rows as the placement window.
-int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_zarr_chunks* z, double* kernel_ms) {
+int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
+                    int32_t depth, int32_t slice, double* kernel_ms) {
     int32_t k = 0;
     if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
     if (int rc = zarr_chunks_check(z)) return rc;
+    if (int rc = zarr_slice_check(depth, slice)) return rc;
     const int bpp = bpp_of(q->pixel_type);
     const int64_t gx = (q->size_x + z->chunk_x - 1) / z->chunk_x;
     const int64_t cy0 = y0 / z->chunk_y, cy1 = ((int64_t)y0 + rows + z->chunk_y - 1) / z->chunk_y;
     ZarrPlan P;
-    if (int rc = zarr_plan(q->size_x, z, bpp, 0, 0, cy0, cy1, P)) return rc;
+    if (int rc = zarr_plan(q->size_x, z, bpp, 0, cy0, cy1, depth, {ZarrWant{(uint32_t)slice, 0}}, y0,
+                           (int64_t)y0 + rows, P))
+        return rc;
     const uint64_t used = z->offsets[gx * (cy1 - cy0)], len = (used + 15) & ~15ull;
     const std::vector<ZarrInput> in{ZarrInput{z->data, used, 0, len}};
     return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
@@ -2536,20 +2582,36 @@ int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     });
 }
 
-}  // namespace
-
-int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
-                             const pbx_zarr_chunks* zs, uint64_t* plane_ids, double* kernel_ms) {
-    if (!ctx || !ds || !zs || !plane_ids || n == 0) return fail(PBX_E_BADARG, "null argument");
+// pbx_planes_register_zarr (layer k = plane k, one plane per chunk) and its deep form: plane k
+// is slice refs[k].slice of the chunks of layer zs[refs[k].layer], which hold depths[layer]
+// planes each.  A layer's chunks are planned, uploaded and decoded once; its planes follow one
+// another in the ZChunk table.
+int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
+                         uint64_t n_layers, const pbx_zarr_chunks* zs, const int32_t* depths,
+                         uint64_t* plane_ids, double* kernel_ms) {
     std::vector<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t>> keys;
+    std::vector<std::vector<ZarrWant>> want(n_layers);
     for (uint64_t k = 0; k < n; k++) {
         const pbx_plane_desc* d = &ds[k];
-        const pbx_zarr_chunks* z = &zs[k];
+        if (refs[k].layer >= n_layers) return fail(PBX_E_BADARG, "plane %llu: no layer %u", (unsigned long long)k, refs[k].layer);
+        const pbx_zarr_chunks* z = &zs[refs[k].layer];
         if (int rc = zarr_chunks_check(z)) return rc;
+        if (int rc = zarr_slice_check(depths[refs[k].layer], refs[k].slice)) return rc;
+        want[refs[k].layer].push_back(ZarrWant{refs[k].slice, (uint32_t)k});
         if (!bpp_of(d->pixel_type)) return fail(PBX_E_BADARG, "bad pixel type %d", d->pixel_type);
         if (d->size_x <= 0 || d->size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
         if (d->resolution < 0) return fail(PBX_E_BADARG, "bad resolution");
         keys.emplace_back(d->image_id, d->z, d->c, d->t, d->resolution);
+    }
+    for (uint64_t l = 0; l < n_layers; l++) {
+        if (want[l].empty()) return fail(PBX_E_BADARG, "layer %llu: no plane names it", (unsigned long long)l);
+        const pbx_plane_desc& a = ds[want[l][0].plane];
+        for (const ZarrWant& w : want[l]) {
+            const pbx_plane_desc& b = ds[w.plane];
+            if (a.size_x != b.size_x || a.size_y != b.size_y || a.pixel_type != b.pixel_type ||
+                (a.byte_order == PBX_LITTLE_ENDIAN) != (b.byte_order == PBX_LITTLE_ENDIAN))
+                return fail(PBX_E_BADARG, "planes of layer %llu disagree on size, type or byte order", (unsigned long long)l);
+        }
     }
     {
         auto sorted = keys;
@@ -2575,16 +2637,18 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     }
     // host plan: metadata of every chunk of every plane, one upload buffer, one scratch
     ZarrPlan P;
-    std::vector<uint64_t> in_base(n + 1, 0);
-    std::vector<ZarrInput> in(n);
+    std::vector<uint64_t> in_base(n_layers + 1, 0);
+    std::vector<ZarrInput> in(n_layers);
     int32_t max_cy = 0;
-    for (uint64_t k = 0; k < n; k++) {
-        const pbx_plane_desc* d = &ds[k];
-        const pbx_zarr_chunks* z = &zs[k];
+    for (uint64_t l = 0; l < n_layers; l++) {
+        const pbx_plane_desc* d = &ds[want[l][0].plane];
+        const pbx_zarr_chunks* z = &zs[l];
         const int64_t gx = (d->size_x + z->chunk_x - 1) / z->chunk_x, gy = (d->size_y + z->chunk_y - 1) / z->chunk_y;
-        if (int rc = zarr_plan(d->size_x, z, bpp_of(d->pixel_type), in_base[k], (uint32_t)k, 0, gy, P)) return rc;
-        in_base[k + 1] = in_base[k] + ((z->offsets[gx * gy] + 15) & ~15ull);
-        in[k] = ZarrInput{z->data, z->offsets[gx * gy], in_base[k], in_base[k + 1] - in_base[k]};
+        if (int rc = zarr_plan(d->size_x, z, bpp_of(d->pixel_type), in_base[l], 0, gy, depths[l], want[l], 0,
+                               gy * z->chunk_y, P))
+            return rc;
+        in_base[l + 1] = in_base[l] + ((z->offsets[gx * gy] + 15) & ~15ull);
+        in[l] = ZarrInput{z->data, z->offsets[gx * gy], in_base[l], in_base[l + 1] - in_base[l]};
         max_cy = std::max(max_cy, z->chunk_y);
     }
     if (ensure_device(ctx)) return PBX_E_INTERNAL;
@@ -2600,8 +2664,9 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
         p.pitch = ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255;
         p.bytes = (size_t)p.pitch * d->size_y + 256;
         p.band_rows = d->size_y;
-        zp[k] = ZPlane{nullptr, p.pitch, d->size_x, d->size_y, zs[k].chunk_x, zs[k].chunk_y,
-                       (uint32_t)bpp, 0, zarr_fill(zs[k].fill_bits, bpp, p.little_endian), 0, d->size_y};
+        const pbx_zarr_chunks& z = zs[refs[k].layer];
+        zp[k] = ZPlane{nullptr, p.pitch, d->size_x, d->size_y, z.chunk_x, z.chunk_y,
+                       (uint32_t)bpp, 0, zarr_fill(z.fill_bits, bpp, p.little_endian), 0, d->size_y};
     }
     for (uint64_t k = 0; k < n; k++) {
         if (int rc = plane_alloc(ctx, ps[k].bytes, &ps[k].dev)) {
@@ -2615,7 +2680,7 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     hipError_t e = hipSuccess;
     for (uint64_t k = 0; k < n && e == hipSuccess; k++)  // over-read slack after the last row
         e = hipMemsetAsync(ps[k].dev + (size_t)ps[k].pitch * ps[k].size_y, 0, 256, ctx->stream);
-    int rc = e == hipSuccess ? zarr_decode_place(ctx, ctx->stream, P, zp, in, in_base[n], max_cy, kernel_ms)
+    int rc = e == hipSuccess ? zarr_decode_place(ctx, ctx->stream, P, zp, in, in_base[n_layers], max_cy, kernel_ms)
                              : fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
     if (rc) {
         const std::string msg = g_err;
@@ -2633,22 +2698,76 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     return PBX_OK;
 }
 
+}  // namespace
+
+int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
+                             const pbx_zarr_chunks* zs, uint64_t* plane_ids, double* kernel_ms) {
+    if (!ctx || !ds || !zs || !plane_ids || n == 0) return fail(PBX_E_BADARG, "null argument");
+    if (n > 0xffffffffull) return fail(PBX_E_BADARG, "too many planes");
+    std::vector<pbx_zarr_slice> refs(n);
+    for (uint64_t k = 0; k < n; k++) refs[k] = pbx_zarr_slice{(uint32_t)k, 0};
+    const std::vector<int32_t> depths(n, 1);
+    return register_zarr_layers(ctx, n, ds, refs.data(), n, zs, depths.data(), plane_ids, kernel_ms);
+}
+
+int pbx_planes_register_zarr_deep(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
+                                  uint64_t n_layers, const pbx_zarr_chunks* layers, const int32_t* chunk_planes,
+                                  uint64_t* plane_ids, double* kernel_ms) {
+    if (!ctx || !ds || !refs || !layers || !chunk_planes || !plane_ids || n == 0 || n_layers == 0)
+        return fail(PBX_E_BADARG, "null argument");
+    if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, layers, chunk_planes, plane_ids, kernel_ms);
+}
+
+int pbx_test_zarr_plan(const pbx_zarr_chunks* z, int32_t size_x, int32_t size_y, int32_t bpp, int32_t depth,
+                       const int32_t* slices, int32_t nslices, int32_t y0, int32_t rows, uint64_t out[4]) {
+    if (!z || !slices || !out || nslices < 1) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = zarr_chunks_check(z)) return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    if (bpp != 1 && bpp != 2 && bpp != 4 && bpp != 8) return fail(PBX_E_BADARG, "bad sample size %d", bpp);
+    if (rows < 0 || y0 < 0 || (int64_t)y0 + rows > size_y) return fail(PBX_E_BADARG, "rows outside the plane");
+    std::vector<ZarrWant> want;
+    for (int32_t k = 0; k < nslices; k++) {
+        if (int rc = zarr_slice_check(depth, slices[k])) return rc;
+        want.push_back(ZarrWant{(uint32_t)slices[k], (uint32_t)k});
+    }
+    const int64_t gy = ((int64_t)size_y + z->chunk_y - 1) / z->chunk_y;
+    const int64_t cy0 = rows ? y0 / z->chunk_y : 0, cy1 = rows ? ((int64_t)y0 + rows + z->chunk_y - 1) / z->chunk_y : gy;
+    ZarrPlan P;
+    if (int rc = zarr_plan(size_x, z, bpp, 0, cy0, cy1, depth, want, rows ? y0 : 0,
+                           rows ? (int64_t)y0 + rows : gy * z->chunk_y, P))
+        return rc;
+    out[0] = out[1] = 0;
+    for (const auto& v : P.kind) {
+        out[0] += v.size();
+        for (const ZStream& t : v) out[1] += t.dlen;
+    }
+    out[2] = P.skipped;
+    out[3] = P.scratch;
+    return PBX_OK;
+}
+
 int pbx_plane_register_zarr(pbx_ctx* ctx, const pbx_plane_desc* d, const pbx_zarr_chunks* z,
                             uint64_t* plane_id, double* kernel_ms) {
     return pbx_planes_register_zarr(ctx, 1, d, z, plane_id, kernel_ms);
 }
 
-int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
-                        double* kernel_ms) {
+int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
+                             int32_t depth, int32_t slice, double* kernel_ms) {
     if (!ctx || !z) return fail(PBX_E_BADARG, "null argument");
     int rc;
     Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
     if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
-    rc = band_write_zarr(ctx, q, y0, rows, z, kernel_ms);
+    rc = band_write_zarr(ctx, q, y0, rows, z, depth, slice, kernel_ms);
     const std::string msg = g_err;
     unpin_one(ctx, q);
     g_err = msg;
     return rc;
+}
+
+int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
+                        double* kernel_ms) {
+    return pbx_band_write_zarr_deep(ctx, id, y0, rows, z, 1, 0, kernel_ms);
 }
 
 int pbx_plane_release(pbx_ctx* ctx, uint64_t id) {

@@ -90,6 +90,10 @@ class PbxZarrChunks(ctypes.Structure):
                 ("fill_bits", ctypes.c_uint64)]
 
 
+class PbxZarrSlice(ctypes.Structure):
+    _fields_ = [("layer", ctypes.c_uint32), ("slice", ctypes.c_uint32)]
+
+
 ZARR_RAW, ZARR_BLOSC, ZARR_ZLIB = 0, 1, 2
 ZARR_CODECS = {None: ZARR_RAW, "blosc": ZARR_BLOSC, "zlib": ZARR_ZLIB}
 _ZARR_DTYPES = {"i1": INT8, "u1": UINT8, "i2": INT16, "u2": UINT16, "i4": INT32, "u4": UINT32,
@@ -143,7 +147,8 @@ EXPORTS = [
     "pbx_plane_create_sparse", "pbx_band_write", "pbx_plane_band_info", "pbx_result_spans",
     "pbx_test_stall_batch", "pbx_band_abort", "pbx_test_fail_band_write",
     "pbx_set_deflate_strategy", "pbx_get_deflate_strategy", "pbx_batch_lz_modes",
-    "pbx_band_write_zarr",
+    "pbx_band_write_zarr", "pbx_planes_register_zarr_deep", "pbx_band_write_zarr_deep",
+    "pbx_test_zarr_plan",
 ]
 
 _lib = None
@@ -224,6 +229,14 @@ def lib() -> ctypes.CDLL:
     L.pbx_band_write.argtypes = [vp, u64, i32, i32, vp, u64]
     L.pbx_band_write_zarr.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxZarrChunks),
                                       ctypes.POINTER(ctypes.c_double)]
+    L.pbx_planes_register_zarr_deep.argtypes = [vp, u64, ctypes.POINTER(PbxPlaneDesc),
+                                                ctypes.POINTER(PbxZarrSlice), u64,
+                                                ctypes.POINTER(PbxZarrChunks), ctypes.POINTER(i32),
+                                                ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double)]
+    L.pbx_band_write_zarr_deep.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxZarrChunks), i32, i32,
+                                           ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_zarr_plan.argtypes = [ctypes.POINTER(PbxZarrChunks), i32, i32, i32, i32,
+                                     ctypes.POINTER(i32), i32, i32, i32, ctypes.POINTER(u64)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -379,8 +392,9 @@ def zarr_array_meta(array_dir: str) -> dict:
         raise PbxError(400, "only Zarr v2 C-order arrays without filters are supported")
     if meta["dtype"][1:] not in _ZARR_DTYPES:
         raise PbxError(400, "unsupported dtype %s" % meta["dtype"])
-    if len(meta["shape"]) < 2 or len(meta["shape"]) > 5 or any(cs != 1 for cs in meta["chunks"][:-2]):
-        raise PbxError(400, "need shape [..., y, x] with one plane per chunk")
+    if len(meta["shape"]) < 2 or len(meta["shape"]) > 5 or len(meta["chunks"]) != len(meta["shape"]) or \
+            any(not isinstance(cs, int) or cs < 1 for cs in meta["chunks"]):
+        raise PbxError(400, "need shape [..., y, x] and chunks of the same rank")
     return meta
 
 
@@ -408,10 +422,14 @@ def _read_chunk_file(path: str) -> Optional[bytes]:
 
 
 def _zarr_chunk_rows(array_dir: str, z: int, c: int, t: int, meta: Optional[dict],
-                     axes: Optional[Sequence], y0: Optional[int] = None, rows: int = 0) -> dict:
+                     axes: Optional[Sequence], y0: Optional[int] = None, rows: int = 0,
+                     cache: Optional[dict] = None) -> dict:
     """What zarr_plane_spec and zarr_band_spec share: the array's geometry, codec, byte order
     and fill, and the chunk files (full width, C order) of the chunk rows covering plane rows
-    [y0, y0 + rows) of plane (z, c, t), or of every chunk row (y0 None)."""
+    [y0, y0 + rows) of plane (z, c, t), or of every chunk row (y0 None).  Chunks that hold
+    more than one plane (a leading chunk extent above 1) add chunk_planes, the plane's slice of
+    every chunk, and layer = what names the chunk files (planes of one layer share them); with
+    `cache` (a dict the caller keeps for one registration) a layer's files are read once."""
     import numpy as np
     meta = meta or zarr_array_meta(array_dir)
     shape, chunk, dt = meta["shape"], meta["chunks"], meta["dtype"]
@@ -430,25 +448,38 @@ def _zarr_chunk_rows(array_dir: str, z: int, c: int, t: int, meta: Optional[dict
         y0, rows = 0, sy
     elif rows < 0 or y0 < 0 or y0 + rows > sy:
         raise PbxError(400, "rows %d+%d outside the array (%d rows)" % (y0, rows, sy))
-    chunks = []
-    for j in range(y0 // cy, -(-(y0 + rows) // cy)):
-        for i in range(-(-sx // cx)):
-            chunks.append(_read_chunk_file(os.path.join(array_dir, sep.join(str(v) for v in lead + [j, i]))))
+    depth, slc = 1, 0
+    for v, e in zip(lead, chunk[:-2]):
+        depth, slc = depth * e, slc * e + v % e
+    clead = [v // e for v, e in zip(lead, chunk[:-2])]
+    layer = (array_dir, tuple(clead), y0, rows)
+    chunks = cache.get(layer) if cache is not None else None
+    if chunks is None:
+        chunks = []
+        for j in range(y0 // cy, -(-(y0 + rows) // cy)):
+            for i in range(-(-sx // cx)):
+                chunks.append(_read_chunk_file(os.path.join(array_dir, sep.join(str(v) for v in clead + [j, i]))))
+        if cache is not None:
+            cache[layer] = chunks
+    deep = dict(chunk_planes=depth, slice=slc, layer=layer) if depth > 1 else {}
     native = np.dtype(dt).newbyteorder("=")
     fill_bits = int(np.array([meta.get("fill_value") or 0], dtype=native).view("u%d" % native.itemsize)[0])
     return dict(pixel_type=_ZARR_DTYPES[dt[1:]], size_x=sx, size_y=sy, chunk_x=cx, chunk_y=cy,
                 codec=None if comp is None else comp.get("id"), chunks=chunks,
-                big_endian=dt[0] != "<", fill_bits=fill_bits)
+                big_endian=dt[0] != "<", fill_bits=fill_bits, **deep)
 
 
 def zarr_plane_spec(array_dir: str, image_id: int, z: int, c: int, t: int, level: int = 0,
-                    meta: Optional[dict] = None, axes: Optional[Sequence] = None) -> dict:
+                    meta: Optional[dict] = None, axes: Optional[Sequence] = None,
+                    cache: Optional[dict] = None) -> dict:
     """register_zarr_planes() arguments for plane (z, c, t) of an NGFF array directory (axes:
     the multiscales "axes" of the image, else NGFF order t, c, z, y, x with fewer leading axes
     dropped from the left): chunk files named by dimension_separator "." or "/", absent
-    files = fill_value.  `level` is the stored pyramid level (0 = full resolution)."""
-    return dict(_zarr_chunk_rows(array_dir, z, c, t, meta, axes), image_id=image_id, z=z, c=c, t=t,
-                level=level)
+    files = fill_value.  `level` is the stored pyramid level (0 = full resolution).  For
+    chunks that hold several planes the spec also has chunk_planes, slice and layer; `cache`
+    (one dict for all the specs of a registration) has the planes of a layer share its files."""
+    return dict(_zarr_chunk_rows(array_dir, z, c, t, meta, axes, cache=cache), image_id=image_id, z=z,
+                c=c, t=t, level=level)
 
 
 def zarr_band_spec(array_dir: str, z: int, c: int, t: int, y0: int, rows: int,
@@ -456,7 +487,7 @@ def zarr_band_spec(array_dir: str, z: int, c: int, t: int, y0: int, rows: int,
     """band_write_zarr() arguments for rows [y0, y0 + rows) of plane (z, c, t) of an NGFF array
     directory: only the files of the chunk rows that cover them are read (paths, axes and
     absent files as in zarr_plane_spec).  rows == 0 reads no file: the array's geometry, codec
-    and byte order alone."""
+    and byte order alone.  Chunks that hold several planes add chunk_planes and slice."""
     return dict(_zarr_chunk_rows(array_dir, z, c, t, meta, axes, y0, rows), y0=y0, rows=rows)
 
 
@@ -624,8 +655,21 @@ class PixelsService:
         each dict holds register_zarr_plane's arguments (image_id, z, c, t, pixel_type,
         size_x, size_y, chunk_x, chunk_y, codec, chunks[, big_endian, fill_bits,
         level]).  All are registered or none.  Returns the plane ids (and the kernels'
-        device ms with timing=True)."""
+        device ms with timing=True).  If some dict has chunk_planes > 1 (chunks that hold
+        several planes, with its slice; zarr_plane_spec), the planes go through
+        register_zarr_planes_deep, those with an equal "layer" sharing one set of chunks."""
         import numpy as np
+        if any(p.get("chunk_planes", 1) > 1 for p in planes):
+            layers, index, refs = [], {}, []
+            for k, p in enumerate(planes):
+                key = p.get("layer", ("plane", k))  # no layer named: chunks of its own
+                if key not in index:
+                    index[key] = len(layers)
+                    layers.append(dict(chunk_x=p["chunk_x"], chunk_y=p["chunk_y"], codec=p["codec"],
+                                       chunks=p["chunks"], fill_bits=p.get("fill_bits", 0),
+                                       chunk_planes=p.get("chunk_planes", 1)))
+                refs.append((index[key], p.get("slice", 0)))
+            return self.register_zarr_planes_deep(planes, refs, layers, timing)
         n = len(planes)
         descs = (PbxPlaneDesc * n)()
         zcs = (PbxZarrChunks * n)()
@@ -647,6 +691,44 @@ class PixelsService:
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
         _check(lib().pbx_planes_register_zarr(self._h, n, descs, zcs, ids, ms))
+        del keep
+        return (list(ids), (ms[0], ms[1])) if timing else list(ids)
+
+    def register_zarr_planes_deep(self, planes: Sequence[dict], refs: Sequence[Tuple[int, int]],
+                                  layers: Sequence[dict], timing: bool = False):
+        """pbx_planes_register_zarr_deep: planes[k] (image_id, z, c, t, pixel_type, size_x, size_y
+        [, big_endian, level]) is slice refs[k][1] of every chunk of layers[refs[k][0]]; a layer
+        is a dict of chunk_x, chunk_y, codec, chunks (as register_zarr_plane), chunk_planes
+        [, fill_bits].  Every chunk is uploaded and decoded once.  Returns as
+        register_zarr_planes."""
+        n, nl = len(planes), len(layers)
+        descs = (PbxPlaneDesc * n)()
+        rf = (PbxZarrSlice * n)()
+        zcs = (PbxZarrChunks * max(nl, 1))()
+        depths = (ctypes.c_int32 * max(nl, 1))()
+        keep = []
+        for k, p in enumerate(planes):
+            d = descs[k]
+            d.image_id, d.z, d.c, d.t = p["image_id"], p["z"], p["c"], p["t"]
+            d.resolution = p.get("level", 0)
+            d.pixel_type, d.size_x, d.size_y = p["pixel_type"], p["size_x"], p["size_y"]
+            d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
+            if not (0 <= refs[k][0] < 2 ** 32 and 0 <= refs[k][1] < 2 ** 32):
+                raise PbxError(400, "plane %d: bad layer or slice %r" % (k, tuple(refs[k])))
+            rf[k].layer, rf[k].slice = refs[k]
+        for k, l in enumerate(layers):
+            if l["codec"] not in ZARR_CODECS:
+                raise PbxError(400, "unsupported Zarr compressor %r" % (l["codec"],))
+            chunks = l["chunks"]
+            data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
+            keep += [offsets, data]
+            zc = zcs[k]
+            zc.chunk_x, zc.chunk_y, zc.codec = l["chunk_x"], l["chunk_y"], ZARR_CODECS[l["codec"]]
+            zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, l.get("fill_bits", 0)
+            depths[k] = l.get("chunk_planes", 1)
+        ids = (ctypes.c_uint64 * n)()
+        ms = (ctypes.c_double * 2)()
+        _check(lib().pbx_planes_register_zarr_deep(self._h, n, descs, rf, nl, zcs, depths, ids, ms))
         del keep
         return (list(ids), (ms[0], ms[1])) if timing else list(ids)
 
@@ -674,7 +756,8 @@ class PixelsService:
         meta = zarr_array_meta(array_dir)
         if planes is None:
             planes = self._array_planes(meta, axes)
-        specs = [zarr_plane_spec(array_dir, image_id, z, c, t, level, meta, axes) for z, c, t in planes]
+        cache: dict = {}  # planes of one deep chunk share its files: read once, decoded once
+        specs = [zarr_plane_spec(array_dir, image_id, z, c, t, level, meta, axes, cache) for z, c, t in planes]
         ids = self.register_zarr_planes(specs)
         return dict(zip([tuple(p) for p in planes], ids))
 
@@ -691,12 +774,12 @@ class PixelsService:
         registered, or none.  Returns {level: {(z, c, t): plane id}}."""
         ms, root = ngff_multiscales(image_dir)
         axes = ms.get("axes")
-        specs, keys = [], []
+        specs, keys, cache = [], [], {}
         for k, ds in enumerate(ms["datasets"]):
             adir = os.path.join(root, ds["path"])
             meta = zarr_array_meta(adir)
             for z, c, t in (planes if planes is not None else self._array_planes(meta, axes)):
-                specs.append(zarr_plane_spec(adir, image_id, z, c, t, k, meta, axes))
+                specs.append(zarr_plane_spec(adir, image_id, z, c, t, k, meta, axes, cache))
                 keys.append((k, (z, c, t)))
         ids = self.register_zarr_planes(specs)
         out: Dict[int, Dict[Tuple[int, int, int], int]] = {}
@@ -806,12 +889,13 @@ class PixelsService:
 
     def band_write_zarr(self, plane_id: int, y0: int, rows: int, chunk_x: int, chunk_y: int,
                         codec: Optional[str], chunks: Sequence[Optional[bytes]], fill_bits: int = 0,
-                        timing: bool = False):
+                        timing: bool = False, chunk_planes: int = 1, slice: int = 0):
         """pbx_band_write_zarr: rows [y0, y0 + rows) of one band, decoded on the GPU from the
         Zarr chunk rows y0 // chunk_y .. ceil((y0 + rows) / chunk_y) - 1 that cover them (each
         full width, C order; None or b"" = missing chunk -> fill; or pack_chunks()' (data,
         offsets) pair).  codec as register_zarr_plane.  With timing=True returns the decode /
-        placement kernels' device ms."""
+        placement kernels' device ms.  chunk_planes > 1: the chunks hold that many planes and
+        the rows are those of slice `slice` of each (pbx_band_write_zarr_deep)."""
         if codec not in ZARR_CODECS:
             raise PbxError(400, "unsupported Zarr compressor %r" % (codec,))
         data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
@@ -819,7 +903,11 @@ class PixelsService:
         zc.chunk_x, zc.chunk_y, zc.codec = chunk_x, chunk_y, ZARR_CODECS[codec]
         zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, fill_bits
         ms = (ctypes.c_double * 2)()
-        _check(lib().pbx_band_write_zarr(self._h, plane_id, y0, rows, ctypes.byref(zc), ms))
+        if chunk_planes == 1 and slice == 0:
+            _check(lib().pbx_band_write_zarr(self._h, plane_id, y0, rows, ctypes.byref(zc), ms))
+        else:
+            _check(lib().pbx_band_write_zarr_deep(self._h, plane_id, y0, rows, ctypes.byref(zc),
+                                                  chunk_planes, slice, ms))
         return (ms[0], ms[1]) if timing else None
 
     def band_abort(self, plane_id: int, y0: int) -> None:
@@ -959,7 +1047,9 @@ class PixelsService:
                                   if band_chunks is not None else None)
                             if sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
-                                                     sp["codec"], sp["chunks"], sp["fill_bits"])
+                                                     sp["codec"], sp["chunks"], sp["fill_bits"],
+                                                     chunk_planes=sp.get("chunk_planes", 1),
+                                                     slice=sp.get("slice", 0))
                             else:
                                 self.band_write(pid, r0, r1 - r0,
                                                 source.read_rows(pixels, z, c, t, level, r0, r1 - r0))
@@ -1279,7 +1369,8 @@ class PixelSource:
                     rows: int) -> Optional[dict]:
         """Optional, for storage that is Zarr: the chunk rows covering rows [y0, y0 + rows) of
         the plane at that level, as zarr_band_spec returns them (chunk_x, chunk_y, codec,
-        chunks, fill_bits, big_endian = the array's byte order); load_bands then has them
+        chunks, fill_bits, big_endian = the array's byte order, and chunk_planes / slice for
+        chunks that hold several planes); load_bands then has them
         decoded on the GPU instead of calling read_rows.  rows == 0 asks for the byte order and
         geometry only and must read no chunk.  None (the default): no chunk-level access."""
         return None
