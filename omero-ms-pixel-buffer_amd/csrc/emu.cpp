@@ -307,6 +307,26 @@ int pbxemu_split_max(void) { return (int)SPLIT_MAX; }
 // The device's division by a precomputed reciprocal (pbx_common.h div_rcp), for the tests.
 uint32_t pbxemu_div_rcp(uint32_t n, uint32_t d) { return div_rcp(n, d, recip32(d)); }
 
+// The TIFF header writers the kernels share (pbx_common.h), for the tests.  Strips: writes the
+// TIFF_DATA_OFFSET header bytes and returns that offset.  Tiled: writes the header and IFD
+// (not the TileOffsets / TileByteCounts arrays of n > 1 sub-tiles) and returns the data offset;
+// *arrays (may be NULL) is where the arrays start.  predictor: tag 317's value (1 or 2).
+uint32_t pbxemu_tiff_header(uint8_t* out, uint32_t w, uint32_t h, uint32_t bpp, uint32_t sf, uint32_t compression,
+                            uint32_t nbytes, uint32_t predictor) {
+    write_tiff_header(out, w, h, bpp, sf, compression, nbytes, predictor);
+    return TIFF_DATA_OFFSET;
+}
+uint64_t pbxemu_tiff_tiled_header(uint8_t* out, uint32_t w, uint32_t h, uint32_t t, uint32_t bpp, uint32_t sf,
+                                  uint32_t compression, uint32_t n, uint32_t off0, uint32_t cnt0, uint32_t predictor,
+                                  uint32_t* arrays) {
+    const bool pred = predictor == TIFF_PRED_HORIZONTAL;
+    write_tiff_tiled_ifd(out, w, h, t, bpp, sf, compression, n, off0, cnt0, pred);
+    if (arrays) *arrays = tiff_tiled_arrays(pred);
+    return tiff_tiled_data_offset(n, pred);
+}
+// Rows per wave of the fast predictor kernel (the heights the GPU tests straddle).
+uint32_t pbxemu_tiff_pred_run_rows(void) { return TIFF_PRED3_RUN; }
+
 // Deflate `len` bytes into a zlib stream exactly as the batch pipeline does for one tile
 // (segments of seg_len_for(len) bytes, window, per-segment blocks, combined Adler-32).
 // rowlen: repeating-row candidate distance.  Per-segment results go to segs (may be NULL,

@@ -3273,7 +3273,7 @@ __device__ __forceinline__ void frame_tile(const TileDesc& d, uint8_t* __restric
     if (d.flags & TF_TILED) return;  // header and tile arrays: k_tiff_tiled
     if (tiff) {
         write_tiff_header(base, d.w, d.h, d.bpp, tiff_sample_format(d.pixel_type), 8,
-                          ZLIB_HDR_BYTES + payload + 4);
+                          ZLIB_HDR_BYTES + payload + 4, (d.flags & TF_PRED) ? TIFF_PRED_HORIZONTAL : TIFF_PRED_NONE);
         return;
     }
     c = crc_be32(c ^ 0xFFFFFFFFu, adler) ^ 0xFFFFFFFFu;
@@ -3420,7 +3420,8 @@ __device__ void frame_wave_tile(const TileDesc& d, uint8_t* __restrict__ base, c
     if (d.flags & TF_TILED) return;  // header and tile arrays: k_tiff_tiled
     if (tiff) {
         if (lane == 0)
-            write_tiff_header(base, d.w, d.h, d.bpp, tiff_sample_format(d.pixel_type), 8, ZLIB_HDR_BYTES + payload + 4);
+            write_tiff_header(base, d.w, d.h, d.bpp, tiff_sample_format(d.pixel_type), 8, ZLIB_HDR_BYTES + payload + 4,
+                              (d.flags & TF_PRED) ? TIFF_PRED_HORIZONTAL : TIFF_PRED_NONE);
         return;
     }
     if (lane == 0) {

@@ -611,7 +611,8 @@ __global__ __launch_bounds__(256) void k_tiff_tiled(const TiledHdr* __restrict__
                                                     uint8_t* __restrict__ zout) {
     const TiledHdr j = th[blockIdx.x];
     const uint32_t tid = threadIdx.x;
-    const uint64_t D = tiff_tiled_data_offset(j.n);
+    const bool pred = j.pred != 0;  // Predictor = 2: one more IFD entry, the arrays 16 bytes later
+    const uint64_t D = tiff_tiled_data_offset(j.n, pred);
     const uint64_t sub = (uint64_t)j.t * j.t * j.bpp;
     uint8_t* p = j.comp == 1 ? fixed + j.off : zout + offs[j.first];
     auto entry = [&](uint32_t k, uint32_t& off, uint32_t& cnt) {
@@ -627,15 +628,15 @@ __global__ __launch_bounds__(256) void k_tiff_tiled(const TiledHdr* __restrict__
     if (tid == 0) {
         uint32_t off0, cnt0;
         entry(0, off0, cnt0);
-        write_tiff_tiled_ifd(p, j.w, j.h, j.t, j.bpp, j.sf, j.comp, j.n, off0, cnt0);
+        write_tiff_tiled_ifd(p, j.w, j.h, j.t, j.bpp, j.sf, j.comp, j.n, off0, cnt0, pred);
     }
     if (j.n > 1) {
         for (uint32_t k = tid; k < j.n; k += 256) {
             uint32_t off, cnt;
             entry(k, off, cnt);
-            tiff_tiled_entry(p, j.n, k, off, cnt);
+            tiff_tiled_entry(p, j.n, k, off, cnt, pred);
         }
-        for (uint64_t i = TIFF_TILED_ARRAYS + 8ull * j.n + tid; i < D; i += 256) p[i] = 0;
+        for (uint64_t i = tiff_tiled_arrays(pred) + 8ull * j.n + tid; i < D; i += 256) p[i] = 0;
     }
 }
 

@@ -36,6 +36,8 @@ enum : uint32_t {
     TF_DIRECT_OK = 128u,  // adaptive PNG tile of TF_DIRECT's geometry: in the None mode
                           // k_adaptive_mode sets TF_DIRECT on it (no filter pass; k_lz77 reads
                           // its rows from the plane)
+    TF_PRED = 256u,    // deflate-TIFF tile of an integer type whose stream rows are horizontally
+                       // differenced (TIFF Predictor = 2): its header carries tag 317
     TF_BRIDGE = 1u << 30,  // host only, cleared before upload: `plane` is an offset into the
                            // batch's bridge buffer (a region straddling sparse-plane bands)
 };
@@ -49,9 +51,15 @@ constexpr uint32_t PNG_IDAT_DATA_OFF =
     PNG_SIG_BYTES + PNG_IHDR_BYTES + PNG_ACTL_BYTES + PNG_FCTL_BYTES + 8;  // 99
 constexpr uint32_t ZLIB_HDR_BYTES = 2;
 constexpr uint32_t PNG_TAIL_BYTES = 4 /*adler*/ + 4 /*IDAT crc*/ + 12 /*IEND*/;
-// TIFF: header + 11-entry IFD, strip data at a 16-byte aligned offset.
+// TIFF: header + 11-entry IFD (12 with the Predictor tag: ends at 158), strip data at a
+// 16-byte aligned offset.
 constexpr uint32_t TIFF_NTAGS = 11;
 constexpr uint32_t TIFF_DATA_OFFSET = 160;
+// TIFF 6.0 section 14, tag 317: 1 = none, 2 = horizontal differencing (pbx.h's values).
+constexpr uint32_t TIFF_TAG_PREDICTOR = 317;
+constexpr uint32_t TIFF_PRED_NONE = 1, TIFF_PRED_HORIZONTAL = 2;
+// Rows one wave of k_tiff_pred3 differences (its whole run is loaded at once).
+constexpr uint32_t TIFF_PRED3_RUN = 8;
 
 // Per-tile descriptor (device side).  64-byte aligned POD, filled by the host planner.
 // Division by a divisor known ahead (a tile's row length, a batch's segments per tile)
@@ -82,7 +90,8 @@ struct alignas(16) TileDesc {
     uint32_t seg_len;       // nominal segment length (the last may be shorter)
     uint32_t rowlen_rcp;    // deflate tiles: recip32(rowlen), divisions by rowlen on the device
     uint32_t blk_first;     // first workgroup of this tile (extract / filter bands)
-    uint32_t rows_per_blk;  // extract: rows handled by one workgroup
+    uint32_t rows_per_blk;  // extract: rows handled by one workgroup; TF_PRED tiles: the tile's
+                            // first wave of k_tiff_pred3
     uint32_t hblk_first;    // deflate tiles: first Huffman block index in the batch
     uint32_t vw, vh;        // tiled-TIFF edge sub-tile: valid w x h inside the padded w x h
                             // geometry (bytes outside read as 0); 0 = no padding
@@ -146,19 +155,25 @@ PBX_HD uint32_t tiff_sample_format(int32_t pt) {
 
 // Classic big-endian ("MM") TIFF header + 11-entry IFD; one strip of nbytes at
 // TIFF_DATA_OFFSET (TiffWriter with PixelsBigEndian=true, TileRequestHandler.java:155,182-186).
-// Writes exactly TIFF_DATA_OFFSET bytes.
+// Writes exactly TIFF_DATA_OFFSET bytes.  predictor == TIFF_PRED_HORIZONTAL adds the Predictor
+// entry (tag 317, SHORT, 2) between tags 284 and 339; the reference's writer has none.
 PBX_HD void write_tiff_header(uint8_t* p, uint32_t w, uint32_t h, uint32_t bpp, uint32_t sf,
-                              uint32_t compression, uint32_t nbytes) {
+                              uint32_t compression, uint32_t nbytes, uint32_t predictor = TIFF_PRED_NONE) {
     for (uint32_t i = 0; i < TIFF_DATA_OFFSET; i++) p[i] = 0;
     p[0] = 'M'; p[1] = 'M'; put_be16(p + 2, 42); put_be32(p + 4, 8);
-    put_be16(p + 8, TIFF_NTAGS);
+    const uint32_t np = predictor == TIFF_PRED_HORIZONTAL ? 1u : 0u;
+    put_be16(p + 8, TIFF_NTAGS + np);
     const uint16_t tag[TIFF_NTAGS] = {256, 257, 258, 259, 262, 273, 277, 278, 279, 284, 339};
     const uint16_t typ[TIFF_NTAGS] = {4, 4, 3, 3, 3, 4, 3, 4, 4, 3, 3};
     const uint32_t val[TIFF_NTAGS] = {w, h, 8 * bpp, compression, 1, TIFF_DATA_OFFSET, 1, h, nbytes, 1, sf};
     for (uint32_t k = 0; k < TIFF_NTAGS; k++) {
-        uint8_t* e = p + 10 + 12 * k;
+        uint8_t* e = p + 10 + 12 * (k + (tag[k] > TIFF_TAG_PREDICTOR ? np : 0u));
         put_be16(e, tag[k]); put_be16(e + 2, typ[k]); put_be32(e + 4, 1);
         if (typ[k] == 3) { put_be16(e + 8, val[k]); } else { put_be32(e + 8, val[k]); }
+    }
+    if (np) {
+        uint8_t* e = p + 10 + 12 * (TIFF_NTAGS - 1);
+        put_be16(e, TIFF_TAG_PREDICTOR); put_be16(e + 2, 3); put_be32(e + 4, 1); put_be16(e + 8, TIFF_PRED_HORIZONTAL);
     }
     // next-IFD offset (0) is already zero
 }
@@ -167,38 +182,48 @@ PBX_HD void write_tiff_header(uint8_t* p, uint32_t w, uint32_t h, uint32_t bpp, 
 // sub-tiles the TileOffsets array at 160 and TileByteCounts at 160 + 4n; sub-tile data from
 // the 16-byte aligned offset tiff_tiled_data_offset(n), row-major over the region, every
 // sub-tile T x T samples (edge sub-tiles zero-padded), raw or one zlib stream each.
+// With the Predictor tag (pred) the IFD has 13 entries and ends at 170: the arrays start at 176.
 constexpr uint32_t TIFF_TILED_NTAGS = 12;
 constexpr uint32_t TIFF_TILED_ARRAYS = 160;
+constexpr uint32_t TIFF_TILED_ARRAYS_PRED = 176;
 
-PBX_HD uint64_t tiff_tiled_data_offset(uint64_t n) {
-    return n > 1 ? (TIFF_TILED_ARRAYS + 8 * n + 15) & ~15ull : TIFF_TILED_ARRAYS;
+PBX_HD uint32_t tiff_tiled_arrays(bool pred) { return pred ? TIFF_TILED_ARRAYS_PRED : TIFF_TILED_ARRAYS; }
+PBX_HD uint64_t tiff_tiled_data_offset(uint64_t n, bool pred = false) {
+    const uint64_t a = tiff_tiled_arrays(pred);
+    return n > 1 ? (a + 8 * n + 15) & ~15ull : a;
 }
 
-// Header and IFD (bytes [0, 160)); for n == 1 the one offset / byte count sit in the entries,
-// else the caller writes tiff_tiled_entry(k) for every sub-tile.
+// Header and IFD (bytes [0, tiff_tiled_arrays(pred))); for n == 1 the one offset / byte count
+// sit in the entries, else the caller writes tiff_tiled_entry(k) for every sub-tile.
 PBX_HD void write_tiff_tiled_ifd(uint8_t* p, uint32_t w, uint32_t h, uint32_t t, uint32_t bpp,
                                  uint32_t sf, uint32_t compression, uint32_t n, uint32_t off0,
-                                 uint32_t cnt0) {
-    for (uint32_t i = 0; i < TIFF_TILED_ARRAYS; i++) p[i] = 0;
+                                 uint32_t cnt0, bool pred = false) {
+    const uint32_t arrays = tiff_tiled_arrays(pred), np = pred ? 1u : 0u;
+    for (uint32_t i = 0; i < arrays; i++) p[i] = 0;
     p[0] = 'M'; p[1] = 'M'; put_be16(p + 2, 42); put_be32(p + 4, 8);
-    put_be16(p + 8, TIFF_TILED_NTAGS);
+    put_be16(p + 8, TIFF_TILED_NTAGS + np);
     const uint16_t tag[TIFF_TILED_NTAGS] = {256, 257, 258, 259, 262, 277, 284, 322, 323, 324, 325, 339};
     const uint16_t typ[TIFF_TILED_NTAGS] = {4, 4, 3, 3, 3, 3, 3, 4, 4, 4, 4, 3};
     const uint32_t val[TIFF_TILED_NTAGS] = {w, h, 8 * bpp, compression, 1, 1, 1, t, t,
-                                            n > 1 ? TIFF_TILED_ARRAYS : off0,
-                                            n > 1 ? TIFF_TILED_ARRAYS + 4 * n : cnt0, sf};
+                                            n > 1 ? arrays : off0,
+                                            n > 1 ? arrays + 4 * n : cnt0, sf};
     for (uint32_t k = 0; k < TIFF_TILED_NTAGS; k++) {
-        uint8_t* e = p + 10 + 12 * k;
+        uint8_t* e = p + 10 + 12 * (k + (tag[k] > TIFF_TAG_PREDICTOR ? np : 0u));
         put_be16(e, tag[k]); put_be16(e + 2, typ[k]);
         put_be32(e + 4, (tag[k] == 324 || tag[k] == 325) ? n : 1u);
         if (typ[k] == 3) { put_be16(e + 8, val[k]); } else { put_be32(e + 8, val[k]); }
     }
+    if (np) {  // between 284 and 322
+        uint8_t* e = p + 10 + 12 * 7;
+        put_be16(e, TIFF_TAG_PREDICTOR); put_be16(e + 2, 3); put_be32(e + 4, 1); put_be16(e + 8, TIFF_PRED_HORIZONTAL);
+    }
 }
 
 // Sub-tile k's TileOffsets / TileByteCounts entries (n > 1).
-PBX_HD void tiff_tiled_entry(uint8_t* p, uint32_t n, uint32_t k, uint32_t off, uint32_t cnt) {
-    put_be32(p + TIFF_TILED_ARRAYS + 4 * k, off);
-    put_be32(p + TIFF_TILED_ARRAYS + 4 * n + 4 * k, cnt);
+PBX_HD void tiff_tiled_entry(uint8_t* p, uint32_t n, uint32_t k, uint32_t off, uint32_t cnt, bool pred = false) {
+    const uint32_t arrays = tiff_tiled_arrays(pred);
+    put_be32(p + arrays + 4 * k, off);
+    put_be32(p + arrays + 4 * n + 4 * k, cnt);
 }
 
 // A tiled-TIFF response's header job (k_tiff_tiled).  comp 1: the response starts at `off`
@@ -207,7 +232,9 @@ PBX_HD void tiff_tiled_entry(uint8_t* p, uint32_t n, uint32_t k, uint32_t off, u
 struct alignas(16) TiledHdr {
     uint64_t off;
     uint32_t first, n, w, h, t, bpp, sf, comp;
+    uint32_t pred, pad_;  // pred: the IFD carries Predictor = 2 (comp 8 only); in the struct's padding
 };
+static_assert(sizeof(TiledHdr) == 48, "TiledHdr keeps its size");
 
 // ----------------------------------------------------------------------------- CRC-32 math
 // Standard reflected CRC-32 (poly 0xEDB88320) with zlib's crc32_combine formulation:

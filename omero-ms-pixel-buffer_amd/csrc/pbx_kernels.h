@@ -61,6 +61,21 @@ hipError_t launch_rows(hipStream_t st, const TileDesc* d_tiles, uint32_t ntiles,
                        uint32_t max_rb, uint8_t* stream);
 inline uint32_t rows_blocks_for(uint32_t h) { return (h + ROWS_BAND - 1) / ROWS_BAND; }
 
+// TIFF Predictor = 2 (kernels_tiff_predictor.hip): the horizontally differenced stream of TF_PRED
+// tiles.  k_tiff_pred3: 16-byte aligned source rows of whole 16-byte chunks (<= filter3_max_rb()),
+// one wave per run of tiff_pred3_run_rows() rows, no LDS; nwaves = the runs of every tile
+// (TileDesc::rows_per_blk = a tile's first wave; a tile with none is skipped).  k_tiff_pred:
+// every other tile (any x, any width, padded tiled-TIFF sub-tiles), one workgroup per band of
+// TIFF_PRED_BAND rows staged in LDS (TileDesc::blk_first = a tile's first workgroup; a tile
+// with none is skipped); max_rb = the widest row of at most ROWS_MAX_RB bytes (wider rows use
+// no LDS).  The sub-tiles of tiled responses are in both kernels' tile ranges.
+constexpr uint32_t TIFF_PRED_BAND = 16;
+uint32_t tiff_pred3_run_rows();
+hipError_t launch_tiff_pred3(hipStream_t st, const TileDesc* d_tiles, uint32_t ntiles, uint32_t nwaves,
+                             uint32_t max_rb, uint8_t* stream);
+hipError_t launch_tiff_pred(hipStream_t st, const TileDesc* d_tiles, uint32_t ntiles, uint32_t nblocks,
+                            uint32_t max_rb, uint8_t* stream);
+
 // K3-K6: deflate of every tile's stream into its compacted container.
 struct DeflateLaunch {
     const TileDesc* tiles;  // deflate tiles (seg_first / seg_count / out_off = stream offset)

@@ -400,6 +400,9 @@ struct pbx_ctx {
     // Deflate strategy (enum pbx_deflate_strategy; $PBX_DEFLATE_STRATEGY at pbx_init,
     // pbx_set_deflate_strategy): a batch takes the value when it is planned.
     std::atomic<int> deflate_strategy{PBX_DEFLATE_DEFAULT};
+    // TIFF predictor of deflated TIFF responses (enum pbx_tiff_predictor; $PBX_TIFF_PREDICTOR at
+    // pbx_init, pbx_set_tiff_predictor): a batch takes the value when it is planned.
+    std::atomic<int> tiff_predictor{PBX_TIFF_PREDICTOR_NONE};
     hipStream_t copy_stream = nullptr;  // D2H of finished batches, overlapping later kernels
     // Pipelined batches holding both raw / TIFF tiles and deflate tiles run their HBM-bound
     // k_extract on this stream, beside their own (and the previous batch's) issue-bound deflate
@@ -492,6 +495,12 @@ struct pbx_batch {
     uint32_t ndirect_tiles = 0, nrows_tiles = 0, rows_blocks = 0, rows_max_rb = 0;
     uint32_t nfilt2_tiles = 0, filt2_blocks = 0, filt2_max_rb = 0;  // k_filter2 group
     uint32_t nfilt3_tiles = 0, filt3_waves = 0, filt3_max_rb = 0;   // k_filter3 group
+    // TF_PRED tiles, after every other deflate tile: npred3_tiles fast ones, then npredt_tiles
+    // sub-tiles of tiled responses (each fast or general), then npred_tiles general ones.
+    // k_tiff_pred3 takes the first two groups (pred3_waves runs), k_tiff_pred the last two.
+    uint32_t npred3_tiles = 0, npredt_tiles = 0, npred_tiles = 0;
+    uint32_t pred3_waves = 0, pred3_max_rb = 0, pred_blocks = 0, pred_max_rb = 0;
+    uint32_t pred_fast = 0, pred_general = 0;  // pbx_batch_pred_tiles
     uint32_t filt3_filter = 0;  // its PNG filter (the context's: every k_filter3 tile's d.filter)
     bool adaptive = false;      // some PNG tile takes the adaptive filter (k_adaptive_mode first)
     uint32_t adaptive_max_rb = 0;  // the widest row (bytes) of those tiles
@@ -524,6 +533,7 @@ struct pbx_batch {
     void* h_zc = nullptr;
     uint64_t zc_png_at = 0;
     int32_t strategy = PBX_DEFLATE_DEFAULT;  // the context's deflate strategy when the batch was planned
+    int32_t predictor = PBX_TIFF_PREDICTOR_NONE;  // and its TIFF predictor
     bool launched = false;
     bool attempted = false;  // batch_launch began enqueuing work (it may have failed midway)
     uint64_t ordinal = 0;    // launch ordinal in the context (fault injection)
@@ -1401,6 +1411,12 @@ int pbx_init(const pbx_config* cfg_in, pbx_ctx** out) {
             return fail(PBX_E_BADARG, "bad PBX_DEFLATE_STRATEGY '%s' (0 default, 1 Huffman-only, 2 auto)", ds);
         strategy = ds[0] - '0';
     }
+    int predictor = PBX_TIFF_PREDICTOR_NONE;
+    if (const char* tp = getenv("PBX_TIFF_PREDICTOR")) {
+        if (tp[0] < '1' || tp[0] > '2' || tp[1])
+            return fail(PBX_E_BADARG, "bad PBX_TIFF_PREDICTOR '%s' (1 none, 2 horizontal)", tp);
+        predictor = tp[0] - '0';
+    }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return fail(PBX_E_INTERNAL, "no HIP device available (the tile pipeline runs on MI355X only)");
@@ -1415,6 +1431,7 @@ int pbx_init(const pbx_config* cfg_in, pbx_ctx** out) {
     ctx->device = dev;
     ctx->cfg = cfg;
     ctx->deflate_strategy = strategy;
+    ctx->tiff_predictor = predictor;
     ctx->hpool.pinned = true;
     ctx->evpool_sync.flags = hipEventDisableTiming;
     if (const char* su = getenv("PBX_SPIN_US")) ctx->spin_us = atoll(su);
@@ -1529,6 +1546,23 @@ int pbx_set_deflate_strategy(pbx_ctx* ctx, int32_t strategy) {
 int pbx_get_deflate_strategy(pbx_ctx* ctx, int32_t* strategy) {
     if (!ctx || !strategy) return fail(PBX_E_BADARG, "null argument");
     *strategy = ctx->deflate_strategy;
+    return PBX_OK;
+}
+
+static_assert(PBX_TIFF_PREDICTOR_NONE == TIFF_PRED_NONE && PBX_TIFF_PREDICTOR_HORIZONTAL == TIFF_PRED_HORIZONTAL,
+              "pbx.h's predictors are tag 317's values");
+int pbx_set_tiff_predictor(pbx_ctx* ctx, int32_t predictor) {
+    if (!ctx) return fail(PBX_E_BADARG, "null ctx");
+    if (predictor != PBX_TIFF_PREDICTOR_NONE && predictor != PBX_TIFF_PREDICTOR_HORIZONTAL)
+        return fail(PBX_E_BADARG, "TIFF predictor %d out of range (1 none, 2 horizontal)", predictor);
+    std::lock_guard<std::mutex> run(ctx->run_mu);  // not in the middle of a batch's plan + launch
+    ctx->tiff_predictor = predictor;
+    return PBX_OK;
+}
+
+int pbx_get_tiff_predictor(pbx_ctx* ctx, int32_t* predictor) {
+    if (!ctx || !predictor) return fail(PBX_E_BADARG, "null argument");
+    *predictor = ctx->tiff_predictor;
     return PBX_OK;
 }
 
@@ -2819,6 +2853,7 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
     b->w.resize(n);
     b->h.resize(n);
     b->strategy = ctx->deflate_strategy;  // a later pbx_set_deflate_strategy does not change this batch
+    b->predictor = ctx->tiff_predictor;   // nor a later pbx_set_tiff_predictor
     const int filter = ctx->cfg.png_filter;
     const bool tiff_deflate = ctx->cfg.tiff_deflate != 0;
     const int32_t tiff_tile = ctx->cfg.tiff_tile;
@@ -2826,7 +2861,18 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
     // deflate arena): they go to k_filter, after the other banded tiles
     std::vector<TileDesc> dt_direct, dt_rows, dt_filt2, dt_filt3, dt_band, dt_tiled;
     std::vector<uint32_t> req_direct, req_rows, req_filt2, req_filt3, req_band, req_tiled;
+    // Predictor = 2 tiles (TF_PRED) are classes of their own, never TF_DIRECT: the fast kernel's,
+    // the sub-tiles of tiled responses (consecutive too), the general kernel's
+    std::vector<TileDesc> dt_pred3, dt_predt, dt_pred;
+    std::vector<uint32_t> req_pred3, req_predt, req_pred;
     static const bool use_f3 = !getenv("PBX_FILTER3") || atoi(getenv("PBX_FILTER3")) != 0;
+    // $PBX_TIFF_PRED_FAST=0: every predictor tile through k_tiff_pred (A/B timing, equivalence tests)
+    static const bool use_p3 = !getenv("PBX_TIFF_PRED_FAST") || atoi(getenv("PBX_TIFF_PRED_FAST")) != 0;
+    // k_tiff_pred3's tiles: 16-byte aligned source rows of whole 16-byte chunks, no padding
+    auto pred_fast_ok = [&](const TileDesc& t) {
+        const uint32_t rb = (uint32_t)t.w * (uint32_t)t.bpp;
+        return use_p3 && !t.vw && ((int64_t)t.x * t.bpp) % 16 == 0 && rb % 16 == 0 && rb <= filter3_max_rb();
+    };
     for (uint64_t i = 0; i < n; i++) {
         const pbx_tile_req& r = reqs[i];
         Plane* pp = nullptr;
@@ -2869,13 +2915,16 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
         const uint64_t tile_bytes = (uint64_t)w * h * bpp;
         b->in_bytes += tile_bytes;
         const bool deflate = r.format == PBX_FMT_PNG || (r.format == PBX_FMT_TIF && tiff_deflate);
+        // horizontal differencing: deflated TIFF of integer samples only (not defined for IEEE ones)
+        const bool pred = b->predictor == PBX_TIFF_PREDICTOR_HORIZONTAL && deflate && r.format == PBX_FMT_TIF &&
+                          pl.pixel_type <= PBX_UINT32;
         if (r.format == PBX_FMT_TIF && tiff_tile) {
             // Tiled TIFF: the region as ntx x nty sub-tiles of T x T samples (edge ones
             // zero-padded), each raw or its own zlib stream, behind one header
             const uint32_t T = (uint32_t)tiff_tile;
             const uint32_t ntx = ((uint32_t)w + T - 1) / T, nty = ((uint32_t)h + T - 1) / T;
             const uint64_t nsub = (uint64_t)ntx * nty, sub = (uint64_t)T * T * bpp;
-            const uint64_t D = tiff_tiled_data_offset(nsub);
+            const uint64_t D = tiff_tiled_data_offset(nsub, pred);
             // The response must fit a Java byte[] (the reference's int tileSize rule, :100-103:
             // past 2^31-1 bytes getTile returns null -> 404); zero-padding the edge sub-tiles
             // can push it past the unpadded tile's size, and a deflated sub-tile is at most its
@@ -2896,9 +2945,10 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
                 th.off = b->fixed_bytes;
                 b->fixed_bytes += (D + nsub * sub + 255) & ~255ull;
             } else {
-                th.first = (uint32_t)dt_tiled.size();  // rebased below
+                th.first = (uint32_t)(pred ? dt_predt : dt_tiled).size();  // rebased below
+                th.pred = pred ? 1u : 0u;
             }
-            d.flags |= TF_TIFF | TF_TILED;
+            d.flags |= TF_TIFF | TF_TILED | (pred ? TF_PRED : 0u);
             for (uint32_t ty = 0; ty < nty; ty++)
                 for (uint32_t tx = 0; tx < ntx; tx++) {
                     TileDesc s = d;
@@ -2922,8 +2972,8 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
                         s.filter = 0;
                         s.rowlen = T * (uint32_t)bpp;
                         s.stream_len = (uint64_t)T * s.rowlen;
-                        dt_tiled.push_back(s);
-                        req_tiled.push_back((uint32_t)i);
+                        (pred ? dt_predt : dt_tiled).push_back(s);
+                        (pred ? req_predt : req_tiled).push_back((uint32_t)i);
                     }
                 }
             b->th.push_back(th);
@@ -2975,7 +3025,12 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
             if (d.filter == PBX_FILTER_ADAPTIVE && d.rowlen >= 32 && rb <= ROWS_MAX_RB && aligned && bpp <= 4 &&
                 !ctx->cfg.stage_rows)
                 d.flags |= TF_DIRECT_OK;
-            if (rows_ok && aligned && bpp <= 4 && !ctx->cfg.stage_rows) {
+            if (pred) {
+                d.flags |= TF_PRED;
+                const bool f = pred_fast_ok(d);
+                (f ? dt_pred3 : dt_pred).push_back(d);
+                (f ? req_pred3 : req_pred).push_back((uint32_t)i);
+            } else if (rows_ok && aligned && bpp <= 4 && !ctx->cfg.stage_rows) {
                 d.flags |= TF_DIRECT;
                 dt_direct.push_back(d);
                 req_direct.push_back((uint32_t)i);
@@ -3001,15 +3056,26 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
     b->dt.insert(b->dt.end(), dt_filt3.begin(), dt_filt3.end());
     b->dt.insert(b->dt.end(), dt_band.begin(), dt_band.end());
     b->dt.insert(b->dt.end(), dt_tiled.begin(), dt_tiled.end());
+    const uint32_t tiled0 = (uint32_t)(b->dt.size() - dt_tiled.size());
+    b->npred3_tiles = (uint32_t)dt_pred3.size();
+    b->dt.insert(b->dt.end(), dt_pred3.begin(), dt_pred3.end());
+    const uint32_t predt0 = (uint32_t)b->dt.size();
+    b->npredt_tiles = (uint32_t)dt_predt.size();
+    b->dt.insert(b->dt.end(), dt_predt.begin(), dt_predt.end());
+    b->npred_tiles = (uint32_t)dt_pred.size();
+    b->dt.insert(b->dt.end(), dt_pred.begin(), dt_pred.end());
     b->dt_req = std::move(req_direct);
     b->dt_req.insert(b->dt_req.end(), req_rows.begin(), req_rows.end());
     b->dt_req.insert(b->dt_req.end(), req_filt2.begin(), req_filt2.end());
     b->dt_req.insert(b->dt_req.end(), req_filt3.begin(), req_filt3.end());
     b->dt_req.insert(b->dt_req.end(), req_band.begin(), req_band.end());
     b->dt_req.insert(b->dt_req.end(), req_tiled.begin(), req_tiled.end());
-    const uint32_t tiled0 = (uint32_t)(b->dt.size() - dt_tiled.size());
+    b->dt_req.insert(b->dt_req.end(), req_pred3.begin(), req_pred3.end());
+    b->dt_req.insert(b->dt_req.end(), req_predt.begin(), req_predt.end());
+    b->dt_req.insert(b->dt_req.end(), req_pred.begin(), req_pred.end());
     for (TiledHdr& th : b->th)
-        if (th.comp == 8) th.first += tiled0;
+        if (th.comp == 8) th.first += th.pred ? predt0 : tiled0;
+    const uint32_t pred0 = predt0 - b->npred3_tiles;  // the first TF_PRED tile
     for (size_t k = 0; k < b->dt.size(); k++) {
         TileDesc& d = b->dt[k];
         deflate_split(d.stream_len, d.seg_count, d.seg_len);
@@ -3024,6 +3090,24 @@ int pbx_batch_plan(pbx_ctx* ctx, const pbx_tile_req* reqs, uint64_t n, pbx_batch
         d.out_off = b->stream_cap;  // the tile's filtered stream in the stream buffer
         b->stream_cap += (d.stream_len + 256 + 255) & ~255ull;
         if (k < b->ndirect_tiles) continue;  // k_lz77 assembles it from the plane
+        if (k >= pred0) {
+            // rows_per_blk (an extract field): the tile's first wave of k_tiff_pred3; blk_first:
+            // its first workgroup of k_tiff_pred.  A sub-tile of a tiled response lies in both
+            // kernels' ranges and takes waves of the one, or workgroups of the other.
+            const bool f = k < predt0 || (k < predt0 + b->npredt_tiles && pred_fast_ok(d));
+            d.rows_per_blk = b->pred3_waves;
+            d.blk_first = b->pred_blocks;
+            if (f) {
+                b->pred3_waves += ((uint32_t)d.h + tiff_pred3_run_rows() - 1) / tiff_pred3_run_rows();
+                b->pred3_max_rb = std::max<uint32_t>(b->pred3_max_rb, d.rowlen);
+                b->pred_fast++;
+            } else {
+                b->pred_blocks += ((uint32_t)d.h + TIFF_PRED_BAND - 1) / TIFF_PRED_BAND;
+                if (d.rowlen <= ROWS_MAX_RB) b->pred_max_rb = std::max<uint32_t>(b->pred_max_rb, d.rowlen);
+                b->pred_general++;
+            }
+            continue;
+        }
         if (k < b->ndirect_tiles + b->nrows_tiles) {
             d.blk_first = b->rows_blocks;
             b->rows_blocks += rows_blocks_for((uint32_t)d.h);
@@ -3167,17 +3251,25 @@ static int batch_launch(pbx_ctx* ctx, pbx_batch* b, bool overlap, bool fetch_fol
         if (fine || nft) HIP_TRY(hipEventRecord(b->ev[2], st));
     }
     const TileDesc* d_rows = (const TileDesc*)b->d_dt + b->ndirect_tiles;
+    const uint32_t npred_all = b->npred3_tiles + b->npredt_tiles + b->npred_tiles;  // the last tiles of d_dt
     if (b->adaptive)  // the tile mode of every adaptive tile (the filtered ones follow k_rows')
         HIP_TRY(launch_adaptive_mode(st, (TileDesc*)b->d_dt + b->ndirect_tiles + b->nrows_tiles,
-                                     ndt - b->ndirect_tiles - b->nrows_tiles, b->adaptive_max_rb));
+                                     ndt - npred_all - b->ndirect_tiles - b->nrows_tiles, b->adaptive_max_rb));
     HIP_TRY(launch_rows(st, d_rows, b->nrows_tiles, b->rows_blocks, b->rows_max_rb, (uint8_t*)b->d_stream));
     HIP_TRY(launch_filter2(st, d_rows + b->nrows_tiles, b->nfilt2_tiles, b->filt2_blocks, b->filt2_max_rb,
                            (uint8_t*)b->d_stream));
     HIP_TRY(launch_filter3(st, d_rows + b->nrows_tiles + b->nfilt2_tiles, b->nfilt3_tiles, b->filt3_waves,
                            b->filt3_max_rb, b->filt3_filter, (uint8_t*)b->d_stream));
     HIP_TRY(launch_filter(st, d_rows + b->nrows_tiles + b->nfilt2_tiles + b->nfilt3_tiles,
-                          ndt - b->ndirect_tiles - b->nrows_tiles - b->nfilt2_tiles - b->nfilt3_tiles,
+                          ndt - npred_all - b->ndirect_tiles - b->nrows_tiles - b->nfilt2_tiles - b->nfilt3_tiles,
                           b->filt_blocks, (uint8_t*)b->d_stream));
+    if (npred_all) {
+        const TileDesc* d_pred = (const TileDesc*)b->d_dt + (ndt - npred_all);
+        HIP_TRY(launch_tiff_pred3(st, d_pred, b->npred3_tiles + b->npredt_tiles, b->pred3_waves, b->pred3_max_rb,
+                                  (uint8_t*)b->d_stream));
+        HIP_TRY(launch_tiff_pred(st, d_pred + b->npred3_tiles, b->npredt_tiles + b->npred_tiles, b->pred_blocks,
+                                 b->pred_max_rb, (uint8_t*)b->d_stream));
+    }
     if (fine) HIP_TRY(hipEventRecord(b->ev[3], st));
     // Diagnostic build of the deflate kernel: PBX_PHASE_PROFILE=1 stamps every phase.
     static const bool prof = getenv("PBX_PHASE_PROFILE") != nullptr;
@@ -3647,6 +3739,13 @@ int pbx_batch_lz_modes(pbx_ctx* ctx, pbx_batch* b, uint8_t* modes, uint64_t nseg
     for (uint8_t v : m) n1 += v == LZ_MODE_HUFFMAN_ONLY;
     if (modes && b->nseg) memcpy(modes, m.data(), b->nseg);
     if (huffman_only) *huffman_only = n1;
+    return PBX_OK;
+}
+
+int pbx_batch_pred_tiles(pbx_ctx* ctx, pbx_batch* b, uint32_t* fast, uint32_t* general) {
+    if (!ctx || !b) return fail(PBX_E_BADARG, "null argument");
+    if (fast) *fast = b->pred_fast;
+    if (general) *general = b->pred_general;
     return PBX_OK;
 }
 

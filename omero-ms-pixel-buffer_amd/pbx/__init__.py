@@ -50,6 +50,9 @@ FILTER_NONE, FILTER_SUB, FILTER_UP, FILTER_AVG, FILTER_PAETH, FILTER_ADAPTIVE = 
 # enum pbx_deflate_strategy: match search in every segment (the reference's Deflater default),
 # in none (zlib's Z_HUFFMAN_ONLY), or per segment where a sample of it says matches pay
 DEFLATE_DEFAULT, DEFLATE_HUFFMAN_ONLY, DEFLATE_AUTO = range(3)
+# enum pbx_tiff_predictor (tag 317's values): deflated TIFF samples as they are (the reference's
+# TiffWriter), or every row horizontally differenced (integer pixel types only)
+TIFF_PREDICTOR_NONE, TIFF_PREDICTOR_HORIZONTAL = 1, 2
 
 
 class PbxConfig(ctypes.Structure):
@@ -147,6 +150,7 @@ EXPORTS = [
     "pbx_plane_create_sparse", "pbx_band_write", "pbx_plane_band_info", "pbx_result_spans",
     "pbx_test_stall_batch", "pbx_band_abort", "pbx_test_fail_band_write",
     "pbx_set_deflate_strategy", "pbx_get_deflate_strategy", "pbx_batch_lz_modes",
+    "pbx_set_tiff_predictor", "pbx_get_tiff_predictor", "pbx_batch_pred_tiles",
     "pbx_band_write_zarr", "pbx_planes_register_zarr_deep", "pbx_band_write_zarr_deep",
     "pbx_test_zarr_plan",
 ]
@@ -179,6 +183,9 @@ def lib() -> ctypes.CDLL:
     L.pbx_release_cached.argtypes = [vp]
     L.pbx_set_deflate_strategy.argtypes = [vp, i32]
     L.pbx_get_deflate_strategy.argtypes = [vp, ctypes.POINTER(i32)]
+    L.pbx_set_tiff_predictor.argtypes = [vp, i32]
+    L.pbx_get_tiff_predictor.argtypes = [vp, ctypes.POINTER(i32)]
+    L.pbx_batch_pred_tiles.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.pbx_batch_lz_modes.argtypes = [vp, vp, vp, u64, ctypes.POINTER(u64)]
     L.pbx_plane_register.argtypes = [vp, ctypes.POINTER(PbxPlaneDesc), ctypes.POINTER(u64)]
     L.pbx_plane_release.argtypes = [vp, u64]
@@ -519,12 +526,15 @@ def ngff_multiscales(image_dir: str):
 def make_config(device: Optional[int] = None, png_filter: int = FILTER_NONE,
                 tiff_deflate: bool = False, coalesce: bool = True, stage_rows: bool = False,
                 tiff_tile: Optional[int] = None, request_timeout_us: Optional[int] = None,
-                deflate_strategy: Optional[int] = None) -> PbxConfig:
-    """``deflate_strategy`` is not a field of pbx_config (the struct keeps its size): it is
-    checked here and applied by ``PixelsService`` with the setter right after init."""
+                deflate_strategy: Optional[int] = None, tiff_predictor: Optional[int] = None) -> PbxConfig:
+    """``deflate_strategy`` and ``tiff_predictor`` are not fields of pbx_config (the struct keeps
+    its size): they are checked here and applied by ``PixelsService`` with their setters right
+    after init."""
     if deflate_strategy is not None and deflate_strategy not in (DEFLATE_DEFAULT, DEFLATE_HUFFMAN_ONLY,
                                                                   DEFLATE_AUTO):
         raise PbxError(E_BADARG, "deflate strategy %r out of range" % (deflate_strategy,))
+    if tiff_predictor is not None and tiff_predictor not in (TIFF_PREDICTOR_NONE, TIFF_PREDICTOR_HORIZONTAL):
+        raise PbxError(E_BADARG, "TIFF predictor %r out of range" % (tiff_predictor,))
     cfg = PbxConfig()
     _check(lib().pbx_config_default(ctypes.byref(cfg)))
     cfg.device = -1 if device is None else device
@@ -550,9 +560,11 @@ class PixelsService:
                  tiff_deflate: bool = False, coalesce: bool = True, stage_rows: bool = False,
                  tiff_tile: Optional[int] = None, sparse_band_rows: int = 0,
                  request_timeout_us: Optional[int] = None, deflate_strategy: Optional[int] = None,
-                 _handle=None):
+                 tiff_predictor: Optional[int] = None, _handle=None):
         """deflate_strategy: DEFLATE_DEFAULT / DEFLATE_HUFFMAN_ONLY / DEFLATE_AUTO (None: the
         library's initial value, $PBX_DEFLATE_STRATEGY or DEFAULT).
+        tiff_predictor: TIFF_PREDICTOR_NONE / TIFF_PREDICTOR_HORIZONTAL for deflated TIFF
+        responses of integer pixel types (None: $PBX_TIFF_PREDICTOR or NONE).
         sparse_band_rows > 0: planes the handler opens on demand are sparse planes of bands
         of that many rows (region-proportional residency); 0: whole planes (or the handler's
         row band)."""
@@ -566,12 +578,14 @@ class PixelsService:
             return
         L = lib()
         cfg = make_config(device, png_filter, tiff_deflate, coalesce, stage_rows, tiff_tile,
-                          request_timeout_us, deflate_strategy)
+                          request_timeout_us, deflate_strategy, tiff_predictor)
         h = ctypes.c_void_p()
         _check(L.pbx_init(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
         if deflate_strategy is not None:
             self.set_deflate_strategy(deflate_strategy)
+        if tiff_predictor is not None:
+            self.set_tiff_predictor(tiff_predictor)
 
     def close(self) -> None:
         if self._h and self._owned:
@@ -1090,6 +1104,16 @@ class PixelsService:
         _check(lib().pbx_get_deflate_strategy(self._h, ctypes.byref(v)))
         return v.value
 
+    def set_tiff_predictor(self, predictor: int) -> None:
+        """TIFF predictor of the batches planned from now on (pbx_set_tiff_predictor)."""
+        _check(lib().pbx_set_tiff_predictor(self._h, predictor))
+
+    @property
+    def tiff_predictor(self) -> int:
+        v = ctypes.c_int32()
+        _check(lib().pbx_get_tiff_predictor(self._h, ctypes.byref(v)))
+        return v.value
+
     def set_kernel_streams(self, streams: int, stagger: int = 1) -> None:
         """Kernel streams for pipelined batches (pbx_set_kernel_streams); 1 = serial."""
         _check(lib().pbx_set_kernel_streams(self._h, streams, stagger))
@@ -1170,6 +1194,9 @@ class PixelsNode:
         if config.get("deflate_strategy") is not None:
             for s in self.services:
                 s.set_deflate_strategy(config["deflate_strategy"])
+        if config.get("tiff_predictor") is not None:
+            for s in self.services:
+                s.set_tiff_predictor(config["tiff_predictor"])
 
     def route(self, ctx: TileCtx) -> Tuple[int, int]:
         """(status the serving context would answer, its index); E_NOT_RESIDENT -> the index is
@@ -1299,6 +1326,13 @@ class Batch:
         _check(lib().pbx_test_batch_lz77(self.service.handle, self._h, h.ctypes.data,
                                          m.ctypes.data, nseg))
         return h.reshape(nseg, hist_words), m.reshape(nseg, mrec_words)
+
+    def pred_tiles(self) -> Tuple[int, int]:
+        """(fast, general): the planned batch's tiles (sub-tiles, for tiled TIFF) that go to the
+        fast and to the general predictor kernel (pbx_batch_pred_tiles)."""
+        f, g = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().pbx_batch_pred_tiles(self.service.handle, self._h, ctypes.byref(f), ctypes.byref(g)))
+        return f.value, g.value
 
     def lz_modes(self):
         """Per segment of the launched batch, in batch order: 0 = parsed for matches,
