@@ -247,20 +247,43 @@ int pbx_residency_stats_get(pbx_ctx* ctx, pbx_residency_stats* out);
  * kernel_ms (may be NULL): device time of the downsampling kernels (HIP events). */
 int pbx_plane_build_pyramid(pbx_ctx* ctx, uint64_t plane_id, int32_t levels, uint64_t* ids,
                             double* kernel_ms);
-/* NGFF / Zarr v2 planes: the reference's pixels service is ZarrPixelsService
+/* NGFF / Zarr planes: the reference's pixels service is ZarrPixelsService
  * (PixelBufferVerticle.java:29,56; beanRefContext.xml:51; config.yaml:18), which reads Zarr
  * chunks through omero-zarr-pixel-buffer 0.6.1 / JZarr (build.gradle:57) on every
  * getTileDirect.  Here the chunks of one (z, c, t, resolution) plane are uploaded once and
  * decoded on the GPU (one wave per compressed stream) straight into a resident HBM plane,
  * which then serves tiles like any registered plane.  Codec = the .zarray "compressor":
  * null, blosc (c-blosc 1.x frames: blosclz / lz4 / lz4hc / zlib / zstd, byte shuffle, bit
- * shuffle or none, split or not), zlib.  snappy and blosc2 frames -> 400. */
-enum pbx_zarr_codec { PBX_ZARR_RAW = 0, PBX_ZARR_BLOSC = 1, PBX_ZARR_ZLIB = 2 };
+ * shuffle or none, split or not), zlib.  snappy and blosc2 frames -> 400.
+ *
+ * Zarr v3 (NGFF 0.5) codec pipelines come down to the same call: after "bytes", at most one of
+ * blosc (the same c-blosc 1 frames), gzip or zstd, then optionally crc32c; the inner chunks of a
+ * "sharding_indexed" shard are cut out by the host and handed over as the chunk grid.
+ *   ZSTD  a present chunk is exactly ONE zstd frame (RFC 8878) that decodes to the whole chunk
+ *         (numcodecs' v2 "zstd" compressor writes the same).  The host checks the magic, walks
+ *         the block headers to the frame's end and answers 400 for a skippable frame, a
+ *         dictionary id, a content size other than the chunk's bytes, a truncated frame or bytes
+ *         after it.  A frame without a content size is accepted: the decoder's length check and
+ *         the optional XXH64 content checksum decide on the device.
+ *   GZIP  a present chunk is exactly ONE RFC 1952 member.  The host parses the header (CM = 8;
+ *         FEXTRA, FNAME, FCOMMENT and FHCRC are skipped; a reserved FLG bit is 400) and the
+ *         trailer: ISIZE must be the chunk's bytes.  The device inflates the body, requires it to
+ *         end exactly 8 bytes before the chunk's end (a second member or trailing bytes are 400)
+ *         and compares the CRC-32 of the decoded bytes with the trailer's (k_zarr_crc).
+ * Both are taken whole for chunks that hold several planes, as zlib is. */
+enum pbx_zarr_codec { PBX_ZARR_RAW = 0, PBX_ZARR_BLOSC = 1, PBX_ZARR_ZLIB = 2, PBX_ZARR_ZSTD = 3,
+                      PBX_ZARR_GZIP = 4 };
+/* pbx_zarr_chunks.flags.  CRC32C: the v3 "crc32c" codec as the last codec of a chunk -- the last
+ * 4 bytes of every present chunk are the little-endian CRC-32C (Castagnoli) of the bytes before
+ * them.  The planner cuts them off (a present chunk shorter than 4 bytes is 400) and hands the
+ * codec the rest; the device checks every chunk's uploaded bytes (k_zarr_crc) and a mismatch is
+ * 400 like a decoder error.  Valid with every codec, RAW included.  Any other bit is 400. */
+#define PBX_ZARR_F_CRC32C 1
 
 typedef struct pbx_zarr_chunks {
     int32_t chunk_x, chunk_y;   /* .zarray "chunks" (the x and y extents; edge chunks are full) */
     int32_t codec;              /* enum pbx_zarr_codec */
-    int32_t reserved;
+    int32_t flags;              /* PBX_ZARR_F_*; 0 = none */
     const uint8_t* data;        /* the chunk files concatenated, C order over the chunk grid */
     const uint64_t* offsets;    /* gx*gy + 1 entries (gx = ceil(size_x/chunk_x), ...); chunk
                                    i = cy*gx + cx is data[offsets[i] .. offsets[i+1]); an empty
@@ -270,7 +293,8 @@ typedef struct pbx_zarr_chunks {
 
 /* desc: image/z/c/t/resolution/pixel_type/size as pbx_plane_register; byte_order = the
  * .zarray dtype's ('<' little, '>' / '|' big); source/host_data are ignored.
- * kernel_ms (may be NULL): [0] device ms of the decode kernels, [1] of the placement kernel.
+ * kernel_ms (may be NULL): [0] device ms of the decode kernels and the checksum kernel
+ * (k_zarr_crc: crc32c chunks, gzip trailers), [1] of the placement kernel.
  * A malformed or unsupported chunk fails the whole plane with 400 (nothing registered). */
 int pbx_plane_register_zarr(pbx_ctx* ctx, const pbx_plane_desc* desc, const pbx_zarr_chunks* chunks,
                             uint64_t* plane_id, double* kernel_ms);
@@ -324,7 +348,7 @@ int pbx_planes_register_zarr_deep(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc
                                   uint64_t* plane_ids, double* kernel_ms);
 /* pbx_band_write_zarr from chunks that hold chunk_planes planes: the rows come from slice
  * `slice` of the covering chunk rows.  Every rule of pbx_band_write_zarr holds; only the blosc
- * blocks that hold a byte of the slice's wanted rows are decoded (zlib chunks, raw chunks and
+ * blocks that hold a byte of the slice's wanted rows are decoded (zlib, gzip, zstd and raw chunks and
  * memcpyed frames are taken whole).  400 for chunk_planes < 1 or slice outside
  * [0, chunk_planes).  chunk_planes == 1 is pbx_band_write_zarr. */
 int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,

@@ -1,11 +1,14 @@
-// kernels_zarr.hip — NGFF/Zarr v2 chunk decode into a resident HBM plane:
+// kernels_zarr.hip — NGFF/Zarr (v2 and v3 codecs) chunk decode into a resident HBM plane:
 // the step before getTileDirect when the reference's pixels service is ZarrPixelsService
 // (PixelBufferVerticle.java:29,56; beanRefContext.xml:51; omero-zarr-pixel-buffer 0.6.1,
 // build.gradle:57).  Chunk formats are restated in oracle/zarr_oracle.c.
 //
 //   k_zarr_lz4      one wave per compressed stream (a blosc split): LZ4 block decode
-//   k_zarr_inflate  one wave per zlib stream (Zarr "zlib" chunks, blosc-zlib splits)
+//   k_zarr_inflate  one wave per zlib stream (Zarr "zlib" chunks, blosc-zlib splits; k_zarr_inflate2,
+//                   two waves per stream, also takes the deflate body of a gzip member)
 //   k_zarr_copy     one wave per stored stream (blosc splits kept raw)
+//   k_zarr_crc      one wave or one workgroup per checked byte range: the CRC-32 of a gzip
+//                   member's decoded bytes, the CRC-32C of a Zarr v3 crc32c chunk's uploaded bytes
 //   k_zarr_place    per chunk rows: blosc byte-unshuffle + placement into the pitched plane,
 //                   fill value for missing chunks
 //
@@ -970,7 +973,10 @@ __device__ __forceinline__ void zp_producer(const ZStream& t, const uint8_t* src
         bi.bits(bp & 7);
         if (!bad && bi.consumed_bytes() > bi.ilen) bad = 26;
     }
-    if (!bad) {  // RFC 1950 trailer: Adler-32 of the output, big-endian, at the next byte
+    if (!bad && t.kind == ZS_GZIP) {  // the member's CRC-32 and ISIZE follow, and nothing else
+        const uint32_t q = (bi.ipos * 8 - bi.cnt + 7) >> 3;
+        if (q + 8 != bi.ilen) bad = 31;
+    } else if (!bad) {  // RFC 1950 trailer: Adler-32 of the output, big-endian, at the next byte
         const uint32_t q = (bi.ipos * 8 - bi.cnt + 7) >> 3;
         if (q + 4 > bi.ilen) bad = 28;
         else lds_store_volatile(sb + ZP_CTRL + ZPC_ADLER, bi.win.byte(q) << 24 | bi.win.byte(q + 1) << 16 |
@@ -1098,7 +1104,8 @@ __device__ __forceinline__ void zp_consumer(const ZStream& t, const uint8_t* src
     o.finish();
     // the zlib trailer (stored by the producer before its end token): java.util.zip's
     // Inflater fails such a stream too
-    if (!code && o.adler32() != lds_load_volatile(sb + ZP_CTRL + ZPC_ADLER)) code = 29;
+    // (a gzip member's CRC-32 is k_zarr_crc's, over the decoded chunk)
+    if (!code && t.kind != ZS_GZIP && o.adler32() != lds_load_volatile(sb + ZP_CTRL + ZPC_ADLER)) code = 29;
     if (lane == 0) *errp = code;
     ZDIAG(if (si == 0 && lane == 0) printf("[zp consumer] total %lu wait %lu parallel %lu batches %u chunks %u jumps %u\n",
                                            (unsigned long)(__builtin_amdgcn_s_memtime() - c0), (unsigned long)cwait,
@@ -1315,9 +1322,169 @@ __global__ __launch_bounds__(256) void k_zarr_place(const ZChunk* __restrict__ c
     }
 }
 
+// ---------------------------------------------------------------------------- checksums
+// k_zarr_crc: CRC-32 (gzip trailers, over the decoded chunk) and CRC-32C (the Zarr v3 crc32c
+// codec, over the uploaded chunk bytes) of byte ranges of any alignment, compared with the value
+// the file carries.  T threads share a range: a wave for a short one, the workgroup for a long
+// one.  The range is framed from the 16-byte boundary A at or below its first byte into T runs of
+// R bytes (R a multiple of 16), thread t taking [A + t R, A + (t + 1) R) with aligned 16-byte
+// loads; bytes of the frame outside the range count as zeros (only pieces that hold data are
+// loaded).  A thread's register starts at 0, so the zeros before the range change nothing, and
+// every run has the same length, so the partial CRCs join in a tree whose level k multiplies by
+// the constant x^(8 R 2^k) (crc(A || B) = crc(A) x^(8|B|) ^ crc(B), as k_encode joins its
+// segments).  The z zeros after the range are not undone: the expected raw CRC is multiplied by
+// x^(8z) instead, which compares the same (x is invertible mod P).  Bytes go through
+// slicing-by-4 tables in LDS, four lookups per dword.
+constexpr uint32_t CRC32C_POLY = 0x82F63B78u;
+
+template <uint32_t P>
+constexpr uint32_t zk_mul_c(uint32_t a, uint32_t b) {
+    uint32_t p = 0;
+    for (int i = 31; i >= 0; i--) {
+        if ((a >> i) & 1u) p ^= b;
+        b = (b >> 1) ^ ((b & 1u) ? P : 0u);
+    }
+    return p;
+}
+template <uint32_t P>
+constexpr X8Table zk_make_x8() {  // v[k] = x^(8 * 2^k) mod P
+    X8Table t{};
+    uint32_t p = 1u << 30;
+    for (int k = 0; k < 3; k++) p = zk_mul_c<P>(p, p);
+    t.v[0] = p;
+    for (int k = 1; k < 40; k++) t.v[k] = zk_mul_c<P>(t.v[k - 1], t.v[k - 1]);
+    return t;
+}
+template <uint32_t P>
+__device__ __forceinline__ uint32_t zk_mul(uint32_t a, uint32_t b) {  // a(x) b(x) mod P
+    if constexpr (P == CRC_POLY) return crc_multmodp(a, b);
+    uint32_t p = 0;
+#pragma unroll
+    for (int i = 31; i >= 0; i--) {
+        p ^= ((a >> i) & 1u) ? b : 0u;
+        b = (b >> 1) ^ ((b & 1u) ? P : 0u);
+    }
+    return p;
+}
+// x^(8n) mod P for a wave-uniform n: only the set bits of n cost a multiplication
+template <uint32_t P>
+__device__ __forceinline__ uint32_t zk_x8n(uint32_t n) {
+    constexpr X8Table t = zk_make_x8<P>();
+    n = rfl(n);
+    uint32_t p = 1u << 31;
+#pragma unroll
+    for (int k = 0; k < 32; k++)
+        if ((n >> k) & 1u) p = zk_mul<P>(t.v[k], p);
+    return p;
+}
+static_assert(zk_make_x8<CRC_POLY>().v[5] == make_x8().v[5], "the CRC-32 constants of pbx_common.h");
+
+// the bytes of the dword at frame offset a that lie inside the range [head, span)
+__device__ __forceinline__ uint32_t zk_mask(uint32_t v, uint32_t a, uint32_t head, uint32_t span) {
+    const int64_t lo = (int64_t)head - (int64_t)a, hi = (int64_t)span - (int64_t)a;
+    const uint32_t l = lo < 0 ? 0u : lo > 4 ? 4u : (uint32_t)lo, h = hi < 0 ? 0u : hi > 4 ? 4u : (uint32_t)hi;
+    if (h <= l) return 0;
+    const uint32_t below_h = h == 4 ? 0xFFFFFFFFu : (1u << (8 * h)) - 1, below_l = (1u << (8 * l)) - 1;  // l < 4
+    return v & below_h & ~below_l;
+}
+
+template <uint32_t P, uint32_t T>
+__global__ __launch_bounds__(256) void k_zarr_crc(const ZCheck* __restrict__ ck, uint32_t n,
+                                                  const uint8_t* __restrict__ input,
+                                                  const uint8_t* __restrict__ scratch, uint32_t* __restrict__ err) {
+    static_assert(T == 64 || T == 256, "a wave or the workgroup per range");
+    __shared__ uint32_t tab[4][256];
+    __shared__ uint32_t part[4];
+    {
+        uint32_t t0 = threadIdx.x;
+        for (int k = 0; k < 8; k++) t0 = (t0 & 1) ? P ^ (t0 >> 1) : t0 >> 1;
+        tab[0][threadIdx.x] = t0;
+        __syncthreads();
+        const uint32_t t1 = (t0 >> 8) ^ tab[0][t0 & 0xFF], t2 = (t1 >> 8) ^ tab[0][t1 & 0xFF],
+                       t3 = (t2 >> 8) ^ tab[0][t2 & 0xFF];
+        tab[1][threadIdx.x] = t1; tab[2][threadIdx.x] = t2; tab[3][threadIdx.x] = t3;
+        __syncthreads();
+    }
+    const uint32_t lane = threadIdx.x & 63, w = rfl(threadIdx.x >> 6);
+    const uint32_t ci = T == 64 ? blockIdx.x * 4 + w : blockIdx.x;
+    if (ci >= n) return;  // (a whole wave of the one-wave form; no barrier follows there)
+    const ZCheck c = ck[ci];
+    const uint64_t p = (uint64_t)(uintptr_t)(c.buf == ZK_SCRATCH ? scratch : input) + c.off;
+    const uint64_t A = p & ~15ull;
+    const uint32_t head = (uint32_t)(p - A), span = head + c.len;  // the range in the frame: [head, span)
+    const uint32_t R = rfl(((span + T - 1) / T + 15) & ~15u);
+    const uint32_t t = T == 64 ? lane : threadIdx.x;
+    const uint64_t s = (uint64_t)t * R;
+    uint32_t crc = 0;
+    if (s < span) {
+        const uint4* q = (const uint4*)(uintptr_t)(A + s);
+        for (uint32_t o = 0; o < R; o += 16) {
+            const uint32_t a = (uint32_t)s + o;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (a < span) {
+                v = q[o >> 4];
+                if (a < head || span - a < 16) {
+                    v.x = zk_mask(v.x, a, head, span);
+                    v.y = zk_mask(v.y, a + 4, head, span);
+                    v.z = zk_mask(v.z, a + 8, head, span);
+                    v.w = zk_mask(v.w, a + 12, head, span);
+                }
+            }
+            const uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                crc ^= x[j];
+                crc = tab[3][crc & 0xFF] ^ tab[2][(crc >> 8) & 0xFF] ^ tab[1][(crc >> 16) & 0xFF] ^ tab[0][crc >> 24];
+            }
+        }
+    }
+    // join: level k appends the 2^k runs of the right half to the left half's CRC
+    uint32_t op = zk_x8n<P>(R);
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        crc = ((lane >> k) & 1u) ? crc : zk_mul<P>(op, crc);
+        crc ^= (uint32_t)__shfl_xor((int)crc, 1 << k, 64);
+        op = zk_mul<P>(op, op);
+    }
+    if (T == 256) {  // op = x^(8 * 64 R): one wave's bytes
+        if (lane == 0) part[w] = crc;
+        __syncthreads();
+        if (threadIdx.x >= 64) return;
+        crc = part[0];
+        for (int i = 1; i < 4; i++) crc = zk_mul<P>(op, crc) ^ part[i];
+    }
+    // the range's standard CRC from its raw one: raw ^ (~0 shifted over len bytes) ^ ~0
+    const uint32_t want_raw = c.expect ^ 0xFFFFFFFFu ^ zk_mul<P>(zk_x8n<P>(c.len), 0xFFFFFFFFu);
+    const uint32_t z = T * R - span;  // zeros the frame has after the range
+    if (lane == 0) err[ci] = crc != zk_mul<P>(zk_x8n<P>(z), want_raw) ? ZK_ERR_MISMATCH : 0u;
+}
+
+uint32_t zarr_crc_split() {
+    static const uint32_t v = [] {
+        // ranges of at least this many bytes get a workgroup: measured, a wave per
+        // range is faster up to 64 KiB (1.6 against 0.8 TB/s there) and slower from 128 KiB on
+        const char* e = getenv("PBX_ZARR_CRC_SPLIT");  // (A/B)
+        return e && atoll(e) > 0 ? (uint32_t)atoll(e) : 131072u;
+    }();
+    return v;
+}
+
+hipError_t launch_zarr_crc(hipStream_t st, const ZCheck* d_checks, uint32_t n_wave, uint32_t n, uint32_t poly,
+                           const uint8_t* input, const uint8_t* scratch, uint32_t* err) {
+    const uint32_t n_wg = n - n_wave;
+    if (poly == ZK_CRC32) {
+        if (n_wave) hipLaunchKernelGGL((k_zarr_crc<CRC_POLY, 64>), dim3((n_wave + 3) / 4), dim3(256), 0, st, d_checks, n_wave, input, scratch, err);
+        if (n_wg) hipLaunchKernelGGL((k_zarr_crc<CRC_POLY, 256>), dim3(n_wg), dim3(256), 0, st, d_checks + n_wave, n_wg, input, scratch, err + n_wave);
+    } else {
+        if (n_wave) hipLaunchKernelGGL((k_zarr_crc<CRC32C_POLY, 64>), dim3((n_wave + 3) / 4), dim3(256), 0, st, d_checks, n_wave, input, scratch, err);
+        if (n_wg) hipLaunchKernelGGL((k_zarr_crc<CRC32C_POLY, 256>), dim3(n_wg), dim3(256), 0, st, d_checks + n_wave, n_wg, input, scratch, err + n_wave);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const uint32_t* counts,
                               const uint8_t* src, uint8_t* scratch, uint8_t* zstd_lit, uint32_t* err) {
-    // streams are ordered by kind: lz4, inflate, copy, blosclz, zstd
+    // streams are ordered by kind: lz4, inflate, copy, blosclz, zstd, gzip
     uint32_t first = 0;
     for (uint32_t k = 0; k < ZS_NKINDS; k++) {
         const uint32_t n = counts[k];
@@ -1328,8 +1495,9 @@ hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const ui
         const dim3 g((n + ZWAVES - 1) / ZWAVES), b(64 * ZWAVES);
         switch (k) {
         case ZS_LZ4: hipLaunchKernelGGL(k_zarr_lz4, g, b, ZWAVES * ZL_BYTES, st, s, n, src, scratch, e); break;
+        case ZS_GZIP:  // (always the two-wave decoder: the one-wave form knows zlib framing only)
         case ZS_ZLIB:
-            if (getenv("PBX_INFLATE_1WAVE")) {  // the single-wave decoder (A/B)
+            if (k == ZS_ZLIB && getenv("PBX_INFLATE_1WAVE")) {  // the single-wave decoder (A/B)
                 static std::once_flag once[64];
                 int dev = 0;
                 (void)hipGetDevice(&dev);

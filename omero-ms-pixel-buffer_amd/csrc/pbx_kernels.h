@@ -111,7 +111,10 @@ hipError_t launch_huffman(hipStream_t st, uint32_t nblk, BlkInfo* blk, SegInfo* 
                           const uint32_t* hist, uint32_t* codes);
 
 // NGFF/Zarr chunk decode (kernels_zarr.hip).  One wave per stream.
-enum : uint32_t { ZS_LZ4 = 0, ZS_ZLIB = 1, ZS_COPY = 2, ZS_BLOSCLZ = 3, ZS_ZSTD = 4, ZS_NKINDS = 5 };
+// ZS_GZIP: a raw deflate body followed by the 8 trailer bytes of its RFC 1952 member (the host
+// has parsed the header); k_zarr_inflate2 takes no zlib header and no Adler-32 for it and
+// requires the deflate data to end exactly 8 bytes before the stream's end.
+enum : uint32_t { ZS_LZ4 = 0, ZS_ZLIB = 1, ZS_COPY = 2, ZS_BLOSCLZ = 3, ZS_ZSTD = 4, ZS_GZIP = 5, ZS_NKINDS = 6 };
 struct ZStream {
     uint64_t src_off;  // compressed bytes in the uploaded chunk buffer
     uint64_t dst_off;  // decoded bytes in the scratch buffer
@@ -137,7 +140,7 @@ struct ZPlane {                           // a destination plane of one decode l
     uint64_t fill;                        // fill bytes in stored order (missing chunks)
     int32_t y_lo, y_hi;                   // plane rows k_zarr_place may write: [y_lo, y_hi)
 };
-// Streams ordered by kind (ZS_LZ4 | ZS_ZLIB | ZS_COPY | ZS_BLOSCLZ | ZS_ZSTD), counts[k] of
+// Streams ordered by kind (ZS_LZ4 | ZS_ZLIB | ZS_COPY | ZS_BLOSCLZ | ZS_ZSTD | ZS_GZIP), counts[k] of
 // kind k; err[i] = 0 or a decoder error code per stream.
 // zstd_lit: zstd_scratch_bytes(counts[ZS_ZSTD]) bytes (a block's literals per zstd frame).
 hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const uint32_t* counts,
@@ -145,6 +148,24 @@ hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const ui
 size_t zstd_scratch_bytes(uint32_t nstreams);
 hipError_t launch_zarr_zstd(hipStream_t st, const ZStream* d_streams, uint32_t n, const uint8_t* src,
                             uint8_t* scratch, uint8_t* litbuf, uint32_t* err);
+// Checksums of byte ranges (k_zarr_crc): the v3 crc32c codec over the uploaded chunk bytes, the
+// gzip trailer's CRC-32 over the decoded chunk.  Ranges have any byte alignment and length.
+enum : uint32_t { ZK_INPUT = 0, ZK_SCRATCH = 1 };             // ZCheck::buf
+enum : uint32_t { ZK_CRC32 = 0, ZK_CRC32C = 1, ZK_NPOLY = 2 };  // ZCheck::poly
+constexpr uint32_t ZK_ERR_MISMATCH = 40;  // err[] code of a range whose checksum differs
+struct ZCheck {
+    uint64_t off;      // first byte, in the buffer `buf` names
+    uint32_t len;      // bytes
+    uint32_t expect;   // the checksum the range must have (standard: init and final xor ~0)
+    uint32_t buf, poly;
+};
+static_assert(sizeof(ZCheck) == 24, "ZCheck is uploaded as is");
+// The checks d_checks[0 .. n) must all have polynomial `poly` and be ordered short ranges first:
+// the first n_wave get one wave each, the rest a workgroup each (zarr_crc_split() bytes is where
+// the host draws the line).  err[i] = 0 or ZK_ERR_MISMATCH.
+uint32_t zarr_crc_split();
+hipError_t launch_zarr_crc(hipStream_t st, const ZCheck* d_checks, uint32_t n_wave, uint32_t n, uint32_t poly,
+                           const uint8_t* input, const uint8_t* scratch, uint32_t* err);
 hipError_t launch_zarr_place(hipStream_t st, const ZChunk* d_chunks, uint32_t nchunks,
                              const ZPlane* d_planes, int32_t max_chunk_y, const uint8_t* scratch,
                              const uint8_t* input);

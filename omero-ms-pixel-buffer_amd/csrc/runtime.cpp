@@ -2324,6 +2324,8 @@ uint32_t rd_le32(const uint8_t* p) {
 struct ZarrPlan {
     std::vector<ZStream> kind[ZS_NKINDS];  // streams by decoder (enum ZS_*)
     std::vector<ZChunk> chunks;
+    std::vector<ZCheck> checks[ZK_NPOLY];  // by polynomial: CRC-32 of decoded gzip chunks (scratch),
+                                           // CRC-32C of crc32c chunks' uploaded bytes (input)
     uint64_t scratch = 0;
     uint64_t skipped = 0;  // blosc blocks left undecoded (deep chunks only)
 };
@@ -2333,6 +2335,73 @@ struct ZarrPlan {
 struct ZarrWant {
     uint32_t slice, plane;
 };
+
+// One RFC 8878 frame in f[0 .. len) that must decode to cb bytes: the header, then the block
+// headers to the frame's end (no block is read).  A frame without a content size passes; the
+// decoder's length check decides.
+int zstd_frame_check(const uint8_t* f, uint64_t len, uint64_t cb, long long i) {
+    if (len < 6) return fail(PBX_E_BADARG, "chunk %lld: short zstd frame", i);
+    const uint32_t magic = rd_le32(f);
+    if ((magic & 0xfffffff0u) == 0x184D2A50u) return fail(PBX_E_BADARG, "chunk %lld: skippable zstd frame", i);
+    if (magic != 0xFD2FB528u) return fail(PBX_E_BADARG, "chunk %lld: not a zstd frame", i);
+    const uint32_t fhd = f[4], fcs_flag = fhd >> 6, single = (fhd >> 5) & 1;
+    if (fhd & 3) return fail(PBX_E_BADARG, "chunk %lld: zstd frame with a dictionary id", i);
+    if (fhd & 8) return fail(PBX_E_BADARG, "chunk %lld: reserved zstd frame header bit", i);
+    uint64_t q = 5 + (single ? 0 : 1);
+    const uint32_t fcs_size = fcs_flag == 0 ? single : 1u << fcs_flag;
+    if (q + fcs_size > len) return fail(PBX_E_BADARG, "chunk %lld: short zstd frame", i);
+    if (fcs_size) {
+        uint64_t fcs = 0;
+        for (uint32_t k = 0; k < fcs_size; k++) fcs |= (uint64_t)f[q + k] << (8 * k);
+        if (fcs_size == 2) fcs += 256;
+        if (fcs != cb)
+            return fail(PBX_E_BADARG, "chunk %lld: zstd content size %llu != chunk bytes %llu", i,
+                        (unsigned long long)fcs, (unsigned long long)cb);
+    }
+    q += fcs_size;
+    for (;;) {
+        if (q + 3 > len) return fail(PBX_E_BADARG, "chunk %lld: truncated zstd frame", i);
+        const uint32_t bh = (uint32_t)f[q] | (uint32_t)f[q + 1] << 8 | (uint32_t)f[q + 2] << 16;
+        const uint32_t type = (bh >> 1) & 3;
+        if (type == 3) return fail(PBX_E_BADARG, "chunk %lld: reserved zstd block type", i);
+        q += 3 + (type == 1 ? 1 : bh >> 3);
+        if (bh & 1) break;
+    }
+    if (fhd & 4) q += 4;  // content checksum
+    if (q > len) return fail(PBX_E_BADARG, "chunk %lld: truncated zstd frame", i);
+    if (q < len) return fail(PBX_E_BADARG, "chunk %lld: %llu bytes after the zstd frame", i, (unsigned long long)(len - q));
+    return PBX_OK;
+}
+
+// One RFC 1952 member in f[0 .. len) that must decode to cb bytes: *body = the first byte of its
+// deflate data, *crc = the trailer's CRC-32.  Whether the deflate data ends at the trailer is the
+// decoder's to say.
+int gzip_member_check(const uint8_t* f, uint64_t len, uint64_t cb, long long i, uint64_t* body, uint32_t* crc) {
+    if (len < 18) return fail(PBX_E_BADARG, "chunk %lld: short gzip member", i);
+    if (f[0] != 0x1f || f[1] != 0x8b) return fail(PBX_E_BADARG, "chunk %lld: not a gzip member", i);
+    if (f[2] != 8) return fail(PBX_E_BADARG, "chunk %lld: gzip compression method %u", i, f[2]);
+    const uint32_t flg = f[3];
+    if (flg & 0xE0) return fail(PBX_E_BADARG, "chunk %lld: reserved gzip FLG bits 0x%02x", i, flg);
+    uint64_t q = 10;
+    const uint64_t end = len - 8;  // the trailer
+    if (flg & 4) {  // FEXTRA
+        if (q + 2 > end) return fail(PBX_E_BADARG, "chunk %lld: truncated gzip header", i);
+        q += 2 + ((uint64_t)f[q] | (uint64_t)f[q + 1] << 8);
+    }
+    for (uint32_t bit : {8u, 16u})  // FNAME, FCOMMENT: zero-terminated
+        if (flg & bit) {
+            while (q < end && f[q]) q++;
+            q++;
+        }
+    if (flg & 2) q += 2;  // FHCRC
+    if (q > end) return fail(PBX_E_BADARG, "chunk %lld: truncated gzip header", i);
+    if (rd_le32(f + len - 4) != cb)
+        return fail(PBX_E_BADARG, "chunk %lld: gzip ISIZE %u != chunk bytes %llu", i, rd_le32(f + len - 4),
+                    (unsigned long long)cb);
+    *body = q;
+    *crc = rd_le32(f + len - 8);
+    return PBX_OK;
+}
 
 // Chunk rows [cy0, cy1) of a plane size_x wide (full width, C order): z->offsets has
 // (cy1 - cy0) * gx + 1 entries and z->data holds those chunks only.  Chunk origins are plane
@@ -2360,7 +2429,8 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
     };
     const uint64_t total = z->offsets[n];
     for (int64_t i = 0; i < n; i++) {
-        const uint64_t o = z->offsets[i], len = z->offsets[i + 1] - o;
+        const uint64_t o = z->offsets[i];
+        uint64_t len = z->offsets[i + 1] - o;
         const uint64_t ob = o + in_base;  // device offset in the launch's upload buffer
         if (z->offsets[i + 1] < o || z->offsets[i + 1] > total)
             return fail(PBX_E_BADARG, "chunk %lld: bad offsets", (long long)i);
@@ -2375,6 +2445,13 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
             emit(c);
             continue;
         }
+        if (z->flags & PBX_ZARR_F_CRC32C) {  // the last codec of the pipeline: checked on the uploaded bytes
+            if (len > 0x7fffffffull) return fail(PBX_E_BADARG, "chunk %lld too large", (long long)i);
+            if (len < 4) return fail(PBX_E_BADARG, "chunk %lld: %llu bytes, no room for its crc32c", (long long)i,
+                                     (unsigned long long)len);
+            len -= 4;
+            P.checks[ZK_CRC32C].push_back(ZCheck{ob, (uint32_t)len, rd_le32(z->data + o + len), ZK_INPUT, ZK_CRC32C});
+        }
         if (z->codec == PBX_ZARR_RAW) {
             if (len < cb) return fail(PBX_E_BADARG, "chunk %lld: %llu bytes < %llu", (long long)i,
                                       (unsigned long long)len, (unsigned long long)cb);
@@ -2384,9 +2461,21 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
             continue;
         }
         const uint64_t dst = P.scratch;
-        if (z->codec == PBX_ZARR_ZLIB) {
+        if (z->codec == PBX_ZARR_ZLIB || z->codec == PBX_ZARR_ZSTD || z->codec == PBX_ZARR_GZIP) {
+            // one stream that decodes to the whole chunk
             if (len > 0xffffffffull) return fail(PBX_E_BADARG, "chunk %lld too large", (long long)i);
-            P.kind[ZS_ZLIB].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)cb, ZS_ZLIB, 0});
+            if (z->codec == PBX_ZARR_ZLIB) {
+                P.kind[ZS_ZLIB].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)cb, ZS_ZLIB, 0});
+            } else if (z->codec == PBX_ZARR_ZSTD) {
+                if (int rc = zstd_frame_check(z->data + o, len, cb, (long long)i)) return rc;
+                P.kind[ZS_ZSTD].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)cb, ZS_ZSTD, 0});
+            } else {
+                uint64_t body = 0;
+                uint32_t crc = 0;
+                if (int rc = gzip_member_check(z->data + o, len, cb, (long long)i, &body, &crc)) return rc;
+                P.kind[ZS_GZIP].push_back(ZStream{ob + body, dst, (uint32_t)(len - body), (uint32_t)cb, ZS_GZIP, 0});
+                P.checks[ZK_CRC32].push_back(ZCheck{dst, (uint32_t)cb, crc, ZK_SCRATCH, ZK_CRC32});
+            }
             c.src = dst;
             emit(c);
             P.scratch += (cb + 255) & ~255ull;
@@ -2464,9 +2553,10 @@ int zarr_plan(int32_t size_x, const pbx_zarr_chunks* z, int bpp, uint64_t in_bas
 
 // pbx_zarr_chunks fields that can be checked without the plane.
 int zarr_chunks_check(const pbx_zarr_chunks* z) {
-    if (!z->offsets || (!z->data && z->codec != PBX_ZARR_RAW)) return fail(PBX_E_BADARG, "null argument");
+    if (!z->offsets || (!z->data && (z->codec != PBX_ZARR_RAW || z->flags))) return fail(PBX_E_BADARG, "null argument");
     if (z->chunk_x <= 0 || z->chunk_y <= 0) return fail(PBX_E_BADARG, "bad chunk shape");
-    if (z->codec < PBX_ZARR_RAW || z->codec > PBX_ZARR_ZLIB) return fail(PBX_E_BADARG, "bad codec %d", z->codec);
+    if (z->codec < PBX_ZARR_RAW || z->codec > PBX_ZARR_GZIP) return fail(PBX_E_BADARG, "bad codec %d", z->codec);
+    if (z->flags & ~PBX_ZARR_F_CRC32C) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)z->flags);
     return PBX_OK;
 }
 
@@ -2509,8 +2599,21 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         nstreams += counts[k];
         all.insert(all.end(), P.kind[k].begin(), P.kind[k].end());
     }
+    // checks by polynomial, short ranges (a wave each) before long ones (a workgroup each)
+    std::vector<ZCheck> checks;
+    uint32_t ck_first[ZK_NPOLY], ck_wave[ZK_NPOLY], ck_n[ZK_NPOLY];
+    for (uint32_t k = 0; k < ZK_NPOLY; k++) {
+        const uint32_t split = zarr_crc_split();
+        ck_first[k] = (uint32_t)checks.size();
+        for (const ZCheck& c : P.checks[k]) if (c.len < split) checks.push_back(c);
+        ck_wave[k] = (uint32_t)checks.size() - ck_first[k];
+        for (const ZCheck& c : P.checks[k]) if (c.len >= split) checks.push_back(c);
+        ck_n[k] = (uint32_t)checks.size() - ck_first[k];
+    }
+    const uint32_t nchecks = (uint32_t)checks.size(), nerr = nstreams + nchecks;
     uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
     ZStream* d_st = nullptr;
+    ZCheck* d_ck = nullptr;
     ZChunk* d_ch = nullptr;
     ZPlane* d_pl = nullptr;
     uint32_t* d_err = nullptr;
@@ -2519,7 +2622,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ch, (void*)d_pl, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2532,9 +2635,10 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (P.scratch) dget(d_scr, P.scratch);
     if (counts[ZS_ZSTD]) dget(d_lit, zstd_scratch_bytes(counts[ZS_ZSTD]));
     if (nstreams) dget(d_st, sizeof(ZStream) * nstreams);
+    if (nchecks) dget(d_ck, sizeof(ZCheck) * nchecks);
     dget(d_ch, sizeof(ZChunk) * P.chunks.size());
     dget(d_pl, sizeof(ZPlane) * zp.size());
-    dget(d_err, sizeof(uint32_t) * (nstreams + 1));
+    dget(d_err, sizeof(uint32_t) * (nerr + 1));
     for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
     if (e != hipSuccess) {
         cleanup();
@@ -2552,30 +2656,48 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess) e = hipMemsetAsync(d_in + in_bytes, 0, 4096, st);
     if (e == hipSuccess && nstreams)
         e = hipMemcpyAsync(d_st, all.data(), sizeof(ZStream) * nstreams, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && nchecks)
+        e = hipMemcpyAsync(d_ck, checks.data(), sizeof(ZCheck) * nchecks, hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(d_ch, P.chunks.data(), sizeof(ZChunk) * P.chunks.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_pl, zp.data(), sizeof(ZPlane) * zp.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nstreams + 1), st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
+    // trailers' read the decoded chunks, before anything is placed
+    auto crc = [&](uint32_t k) {
+        return ck_n[k] ? launch_zarr_crc(st, d_ck + ck_first[k], ck_wave[k], ck_n[k], k, d_in, d_scr,
+                                         d_err + nstreams + ck_first[k])
+                       : hipSuccess;
+    };
+    if (e == hipSuccess) e = crc(ZK_CRC32C);
     if (e == hipSuccess) e = launch_zarr_decode(st, d_st, counts, d_in, d_scr, d_lit, d_err);
+    if (e == hipSuccess) e = crc(ZK_CRC32);
     if (e == hipSuccess) e = hipEventRecord(ev[1], st);
     if (e == hipSuccess) e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    std::vector<uint32_t> err(nstreams + 1, 0);
-    if (e == hipSuccess && nstreams)
-        e = hipMemcpy(err.data(), d_err, sizeof(uint32_t) * nstreams, hipMemcpyDeviceToHost);
+    std::vector<uint32_t> err(nerr + 1, 0);
+    if (e == hipSuccess && nerr)
+        e = hipMemcpy(err.data(), d_err, sizeof(uint32_t) * nerr, hipMemcpyDeviceToHost);
     if (e != hipSuccess) {
         cleanup();
         return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
     }
     for (uint32_t s = 0; s < nstreams; s++)
         if (err[s]) {
-            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd"};
+            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd", "gzip"};
             uint32_t k = 0, first = 0;
             while (s >= first + counts[k]) first += counts[k++];
             cleanup();
             return fail(PBX_E_BADARG, "corrupt chunk stream %u (%s, decoder code %u)", s, names[k], err[s]);
+        }
+    for (uint32_t s = 0; s < nchecks; s++)
+        if (err[nstreams + s]) {
+            const ZCheck c = checks[s];
+            cleanup();
+            return fail(PBX_E_BADARG, "chunk checksum mismatch: the %s of %u bytes is not 0x%08x",
+                        c.poly == ZK_CRC32C ? "crc32c" : "gzip CRC-32", c.len, c.expect);
         }
     if (kernel_ms) {
         float a = 0, b = 0;

@@ -88,7 +88,7 @@ class PbxResidencyStats(ctypes.Structure):
 
 class PbxZarrChunks(ctypes.Structure):
     _fields_ = [("chunk_x", ctypes.c_int32), ("chunk_y", ctypes.c_int32),
-                ("codec", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("codec", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("data", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
                 ("fill_bits", ctypes.c_uint64)]
 
@@ -97,8 +97,12 @@ class PbxZarrSlice(ctypes.Structure):
     _fields_ = [("layer", ctypes.c_uint32), ("slice", ctypes.c_uint32)]
 
 
-ZARR_RAW, ZARR_BLOSC, ZARR_ZLIB = 0, 1, 2
-ZARR_CODECS = {None: ZARR_RAW, "blosc": ZARR_BLOSC, "zlib": ZARR_ZLIB}
+# enum pbx_zarr_codec, keyed by the Zarr v2 compressor id / the v3 bytes-to-bytes codec name;
+# pbx_zarr_chunks.flags (ZARR_F_CRC32C: every chunk ends in the v3 crc32c codec's checksum)
+ZARR_RAW, ZARR_BLOSC, ZARR_ZLIB, ZARR_ZSTD, ZARR_GZIP = 0, 1, 2, 3, 4
+ZARR_F_CRC32C = 1
+ZARR_CODECS = {None: ZARR_RAW, "blosc": ZARR_BLOSC, "zlib": ZARR_ZLIB, "zstd": ZARR_ZSTD,
+               "gzip": ZARR_GZIP}
 _ZARR_DTYPES = {"i1": INT8, "u1": UINT8, "i2": INT16, "u2": UINT16, "i4": INT32, "u4": UINT32,
                 "f4": FLOAT, "f8": DOUBLE}
 
@@ -405,6 +409,218 @@ def zarr_array_meta(array_dir: str) -> dict:
     return meta
 
 
+_ZARR3_DTYPES = {"int8": "i1", "uint8": "u1", "int16": "i2", "uint16": "u2", "int32": "i4",
+                 "uint32": "u4", "float32": "f4", "float64": "f8"}
+_CRC32C_TABLE: List[int] = []
+
+
+def crc32c(data: bytes, crc: int = 0) -> int:
+    """CRC-32C (Castagnoli, reflected 0x82F63B78) of data, table driven: what the Zarr v3 crc32c
+    codec appends, little-endian.  Used on the host for shard indexes only; chunk checksums are
+    checked on the GPU."""
+    if not _CRC32C_TABLE:
+        for n in range(256):
+            c = n
+            for _ in range(8):
+                c = (c >> 1) ^ 0x82F63B78 if c & 1 else c >> 1
+            _CRC32C_TABLE.append(c)
+    t, c = _CRC32C_TABLE, crc ^ 0xFFFFFFFF
+    for b in data:
+        c = t[(c ^ b) & 0xFF] ^ (c >> 8)
+    return c ^ 0xFFFFFFFF
+
+
+def _v3_codec(c) -> Tuple[str, dict]:
+    if not isinstance(c, dict) or not isinstance(c.get("name"), str):
+        raise PbxError(400, "bad codec entry %r" % (c,))
+    return c["name"], c.get("configuration") or {}
+
+
+def _v3_chunk_codecs(codecs, itemsize: int, what: str) -> Tuple[str, Optional[str], bool]:
+    """(byte order '<' / '>' / '|', compressor name or None, crc32c?) of a v3 chunk pipeline:
+    bytes, then at most one of blosc / gzip / zstd, then optionally crc32c."""
+    if not isinstance(codecs, list) or not codecs:
+        raise PbxError(400, "%s: no codecs" % what)
+    name, cfg = _v3_codec(codecs[0])
+    if name != "bytes":
+        raise PbxError(400, "%s: codec %r where \"bytes\" must come first" % (what, name))
+    endian = cfg.get("endian")
+    if endian not in ("little", "big") and not (endian is None and itemsize == 1):
+        raise PbxError(400, "%s: bytes codec endian %r" % (what, endian))
+    order = "|" if itemsize == 1 else "<" if endian == "little" else ">"
+    rest = [_v3_codec(c)[0] for c in codecs[1:]]
+    crc = bool(rest) and rest[-1] == "crc32c"
+    if crc:
+        rest = rest[:-1]
+    if len(rest) > 1 or (rest and rest[0] not in ("blosc", "gzip", "zstd")):
+        raise PbxError(400, "%s: unsupported codecs %r (bytes, then one of blosc / gzip / zstd, then "
+                            "crc32c)" % (what, [_v3_codec(c)[0] for c in codecs]))
+    return order, (rest[0] if rest else None), crc
+
+
+def _v3_fill_bits(fv, dt: str) -> int:
+    """A v3 fill_value (a number, "NaN", "Infinity", "-Infinity" or a "0x..." bit pattern) as
+    the sample's bit pattern."""
+    import numpy as np
+    native = np.dtype("=" + dt)
+    if isinstance(fv, str):
+        if fv[:2] in ("0x", "0X"):
+            try:
+                bits = int(fv, 16)
+            except ValueError:
+                raise PbxError(400, "fill_value %r" % (fv,))
+            if bits >> (8 * native.itemsize):
+                raise PbxError(400, "fill_value %r wider than the data type" % (fv,))
+            return bits
+        if fv not in ("NaN", "Infinity", "-Infinity") or native.kind != "f":
+            raise PbxError(400, "fill_value %r" % (fv,))
+        fv = float({"NaN": "nan", "Infinity": "inf", "-Infinity": "-inf"}[fv])
+    elif isinstance(fv, bool) or not isinstance(fv, (int, float)):
+        raise PbxError(400, "fill_value %r" % (fv,))
+    try:
+        if native.kind != "f" and (fv != int(fv) or not np.iinfo(native).min <= fv <= np.iinfo(native).max):
+            raise ValueError
+        return int(np.array([fv], dtype=native).view("u%d" % native.itemsize)[0])
+    except (ValueError, OverflowError):
+        raise PbxError(400, "fill_value %r outside %s" % (fv, native.name))
+
+
+def zarr3_array_meta(array_dir: str) -> dict:
+    """The zarr.json of a Zarr v3 array directory (NGFF 0.5), checked for what the GPU decode
+    supports and brought to the keys the v2 code works on: shape, chunks (of a sharded array: the
+    INNER chunk shape, which is the chunk grid the C-ABI sees), dtype (v2 spelling, byte order
+    from the bytes codec), compressor ({"id": "blosc" / "gzip" / "zstd"} or None), plus
+    zarr_format = 3, fill_bits, crc32c (the chunks end in the crc32c codec's checksum),
+    key_encoding (prefix, separator) and shard (None, or the shard shape, the index location and
+    whether the index carries a crc32c).  Anything else answers PbxError(400)."""
+    with open(os.path.join(array_dir, "zarr.json")) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or doc.get("zarr_format") != 3 or doc.get("node_type") != "array":
+        raise PbxError(400, "zarr.json is not a Zarr v3 array")
+    dt = _ZARR3_DTYPES.get(doc.get("data_type")) if isinstance(doc.get("data_type"), str) else None
+    if dt is None:
+        raise PbxError(400, "unsupported data_type %r" % (doc.get("data_type"),))
+    itemsize = int(dt[1:])
+    shape = doc.get("shape")
+    grid = doc.get("chunk_grid") or {}
+    if grid.get("name") != "regular":
+        raise PbxError(400, "unsupported chunk_grid %r" % (grid.get("name"),))
+    outer = (grid.get("configuration") or {}).get("chunk_shape")
+    ok_shape = lambda v: isinstance(v, list) and all(isinstance(n, int) and not isinstance(n, bool) for n in v)
+    if not ok_shape(shape) or not ok_shape(outer) or not 2 <= len(shape) <= 5 or len(outer) != len(shape) or \
+            any(n < 1 for n in outer) or any(n < 0 for n in shape):
+        raise PbxError(400, "need shape [..., y, x] and a chunk_shape of the same rank")
+    enc = doc.get("chunk_key_encoding") or {}
+    ecfg = enc.get("configuration") or {}
+    if enc.get("name") == "default":
+        key = ("c", ecfg.get("separator", "/"))
+    elif enc.get("name") == "v2":
+        key = ("", ecfg.get("separator", "."))
+    else:
+        raise PbxError(400, "unsupported chunk_key_encoding %r" % (enc.get("name"),))
+    if key[1] not in ("/", "."):
+        raise PbxError(400, "chunk key separator %r" % (key[1],))
+    if doc.get("storage_transformers"):
+        raise PbxError(400, "storage_transformers are not supported")
+    codecs = doc.get("codecs")
+    shard, chunks = None, outer
+    if isinstance(codecs, list) and any(isinstance(c, dict) and c.get("name") == "sharding_indexed" for c in codecs):
+        if len(codecs) != 1:
+            raise PbxError(400, "sharding_indexed must be the array's only codec")
+        cfg = _v3_codec(codecs[0])[1]
+        chunks = cfg.get("chunk_shape")
+        if not ok_shape(chunks) or len(chunks) != len(outer) or any(n < 1 for n in chunks) or \
+                any(o % n for o, n in zip(outer, chunks)):
+            raise PbxError(400, "inner chunk_shape %r does not divide the shard shape %r" % (chunks, outer))
+        loc = cfg.get("index_location", "end")
+        if loc not in ("end", "start"):
+            raise PbxError(400, "index_location %r" % (loc,))
+        iorder, icomp, icrc = _v3_chunk_codecs(cfg.get("index_codecs"), 8, "index_codecs")
+        if iorder != "<" or icomp is not None:
+            raise PbxError(400, "index_codecs must be little-endian bytes, optionally crc32c")
+        shard = dict(shape=list(outer), index_location=loc, index_crc32c=icrc)
+        codecs = cfg.get("codecs")
+    order, comp, crc = _v3_chunk_codecs(codecs, itemsize, "codecs")
+    if "fill_value" not in doc:
+        raise PbxError(400, "no fill_value")
+    return dict(zarr_format=3, shape=list(shape), chunks=list(chunks), dtype=order + dt,
+                compressor=None if comp is None else {"id": comp}, fill_bits=_v3_fill_bits(doc["fill_value"], dt),
+                fill_value=doc["fill_value"], crc32c=crc, key_encoding=key, shard=shard,
+                attributes=doc.get("attributes") or {})
+
+
+def _array_meta(array_dir: str) -> dict:
+    """The array's metadata: .zarray (v2) when the directory has one, else zarr.json (v3)."""
+    if not os.path.exists(os.path.join(array_dir, ".zarray")) and \
+            os.path.exists(os.path.join(array_dir, "zarr.json")):
+        return zarr3_array_meta(array_dir)
+    return zarr_array_meta(array_dir)
+
+
+def _chunk_key(meta: dict, idx: Sequence[int]) -> str:
+    """The store key of the chunk (of a sharded array: the shard) with grid indices idx."""
+    if meta.get("zarr_format") == 3:
+        prefix, sep = meta["key_encoding"]
+        return sep.join(([prefix] if prefix else []) + [str(v) for v in idx])
+    return meta.get("dimension_separator", ".").join(str(v) for v in idx)
+
+
+def _shard_index(data: bytes, n: int, location: str, has_crc: bool, path: str) -> List[Optional[Tuple[int, int]]]:
+    """The (offset, nbytes) of the n inner chunks of a shard file (None = missing), C order over
+    the shard's inner-chunk grid: n pairs of uint64 LE at the end or the start of the file,
+    followed by their crc32c when the index codecs say so.  Every range must lie inside the file
+    and outside the index."""
+    size = 16 * n + (4 if has_crc else 0)
+    if len(data) < size:
+        raise PbxError(400, "shard %s: %d bytes, shorter than its index" % (path, len(data)))
+    lo = 0 if location == "start" else len(data) - size
+    raw = data[lo:lo + size]
+    if has_crc and crc32c(raw[:-4]) != int.from_bytes(raw[-4:], "little"):
+        raise PbxError(400, "shard %s: index checksum mismatch" % path)
+    out: List[Optional[Tuple[int, int]]] = []
+    none = (1 << 64) - 1
+    for k in range(n):
+        off = int.from_bytes(raw[16 * k:16 * k + 8], "little")
+        nb = int.from_bytes(raw[16 * k + 8:16 * k + 16], "little")
+        if off == none and nb == none:
+            out.append(None)
+            continue
+        if off + nb > len(data) or (off < lo + size and lo < off + nb):
+            raise PbxError(400, "shard %s: inner chunk %d (%d + %d) outside the file or inside its index"
+                           % (path, k, off, nb))
+        out.append((off, nb))
+    return out
+
+
+def _read_chunk(array_dir: str, meta: dict, idx: Sequence[int], shards: dict) -> Optional[bytes]:
+    """The bytes of the chunk with grid indices idx (None = absent).  For a sharded array idx
+    counts inner chunks; `shards` keeps every shard file opened by this call (its bytes and
+    parsed index), so each is read once."""
+    sh = meta.get("shard")
+    if not sh:
+        return _read_chunk_file(os.path.join(array_dir, _chunk_key(meta, idx)))
+    per = [o // c for o, c in zip(sh["shape"], meta["chunks"])]
+    sidx = tuple(v // p for v, p in zip(idx, per))
+    ent = shards.get(sidx)
+    if ent is None:
+        path = os.path.join(array_dir, _chunk_key(meta, sidx))
+        data = _read_chunk_file(path)
+        n = 1
+        for p_ in per:
+            n *= p_
+        ent = shards[sidx] = (data, None if data is None else
+                              _shard_index(data, n, sh["index_location"], sh["index_crc32c"], path))
+    data, index = ent
+    if data is None:
+        return None
+    k = 0
+    for v, p_ in zip(idx, per):
+        k = k * p_ + v % p_
+    if index[k] is None:
+        return None
+    return data[index[k][0]:index[k][0] + index[k][1]]
+
+
 def _lead_axes(ndim: int, axes: Optional[Sequence[str]]) -> List[str]:
     """Names of the leading (non-y/x) axes of an array: the NGFF multiscales "axes" when given
     (0.4: time, then channel, then space), else t, c, z with missing ones dropped from the left."""
@@ -438,7 +654,7 @@ def _zarr_chunk_rows(array_dir: str, z: int, c: int, t: int, meta: Optional[dict
     every chunk, and layer = what names the chunk files (planes of one layer share them); with
     `cache` (a dict the caller keeps for one registration) a layer's files are read once."""
     import numpy as np
-    meta = meta or zarr_array_meta(array_dir)
+    meta = meta or _array_meta(array_dir)
     shape, chunk, dt = meta["shape"], meta["chunks"], meta["dtype"]
     comp = meta.get("compressor")
     names = _lead_axes(len(shape), axes)
@@ -449,7 +665,6 @@ def _zarr_chunk_rows(array_dir: str, z: int, c: int, t: int, meta: Optional[dict
     for v, n in zip(lead, shape[:-2]):
         if not 0 <= v < n:
             raise PbxError(404, "plane (z=%d, c=%d, t=%d) outside the array" % (z, c, t))
-    sep = meta.get("dimension_separator", ".")
     sy, sx, cy, cx = shape[-2], shape[-1], chunk[-2], chunk[-1]
     if y0 is None:
         y0, rows = 0, sy
@@ -462,15 +677,20 @@ def _zarr_chunk_rows(array_dir: str, z: int, c: int, t: int, meta: Optional[dict
     layer = (array_dir, tuple(clead), y0, rows)
     chunks = cache.get(layer) if cache is not None else None
     if chunks is None:
-        chunks = []
+        chunks, shards = [], {}  # (shard files of a sharded v3 array: each opened once)
         for j in range(y0 // cy, -(-(y0 + rows) // cy)):
             for i in range(-(-sx // cx)):
-                chunks.append(_read_chunk_file(os.path.join(array_dir, sep.join(str(v) for v in clead + [j, i]))))
+                chunks.append(_read_chunk(array_dir, meta, clead + [j, i], shards))
         if cache is not None:
             cache[layer] = chunks
     deep = dict(chunk_planes=depth, slice=slc, layer=layer) if depth > 1 else {}
-    native = np.dtype(dt).newbyteorder("=")
-    fill_bits = int(np.array([meta.get("fill_value") or 0], dtype=native).view("u%d" % native.itemsize)[0])
+    if "fill_bits" in meta:  # v3: worked out with the metadata
+        fill_bits = meta["fill_bits"]
+    else:
+        native = np.dtype(dt).newbyteorder("=")
+        fill_bits = int(np.array([meta.get("fill_value") or 0], dtype=native).view("u%d" % native.itemsize)[0])
+    if meta.get("crc32c"):
+        deep["crc32c"] = True
     return dict(pixel_type=_ZARR_DTYPES[dt[1:]], size_x=sx, size_y=sy, chunk_x=cx, chunk_y=cy,
                 codec=None if comp is None else comp.get("id"), chunks=chunks,
                 big_endian=dt[0] != "<", fill_bits=fill_bits, **deep)
@@ -510,16 +730,29 @@ def pack_chunks(chunks: Sequence[Optional[bytes]]):
 
 
 def ngff_multiscales(image_dir: str):
-    """(multiscales[0], image directory) of an NGFF image (.zattrs, NGFF 0.1-0.4); a
-    bioformats2raw container root (attribute "bioformats2raw.layout") resolves to series 0."""
-    import json
-    with open(os.path.join(image_dir, ".zattrs")) as f:
-        attrs = json.load(f)
+    """(multiscales[0], image directory) of an NGFF image: .zattrs (NGFF 0.1-0.4), or without
+    one the "ome" attributes of a Zarr v3 group's zarr.json (NGFF 0.5).  A bioformats2raw
+    container root (attribute "bioformats2raw.layout") resolves to series 0."""
+    if not os.path.exists(os.path.join(image_dir, ".zattrs")) and \
+            os.path.exists(os.path.join(image_dir, "zarr.json")):
+        # NGFF 0.5: a Zarr v3 group whose attributes["ome"] holds what .zattrs held
+        with open(os.path.join(image_dir, "zarr.json")) as f:
+            doc = json.load(f)
+        if not isinstance(doc, dict) or doc.get("zarr_format") != 3 or doc.get("node_type") != "group":
+            raise PbxError(400, "%s/zarr.json is not a Zarr v3 group" % image_dir)
+        attrs = (doc.get("attributes") or {}).get("ome")
+        if not isinstance(attrs, dict):
+            raise PbxError(400, "no \"ome\" attributes in %s/zarr.json" % image_dir)
+        where = "zarr.json"
+    else:
+        with open(os.path.join(image_dir, ".zattrs")) as f:
+            attrs = json.load(f)
+        where = ".zattrs"
     if "multiscales" not in attrs and "bioformats2raw.layout" in attrs:
         return ngff_multiscales(os.path.join(image_dir, "0"))
     ms = attrs.get("multiscales")
     if not ms or not ms[0].get("datasets"):
-        raise PbxError(400, "no multiscales datasets in %s/.zattrs" % image_dir)
+        raise PbxError(400, "no multiscales datasets in %s/%s" % (image_dir, where))
     return ms[0], image_dir
 
 
@@ -642,11 +875,12 @@ class PixelsService:
                             size_x: int, size_y: int, chunk_x: int, chunk_y: int,
                             codec: Optional[str], chunks: Sequence[Optional[bytes]],
                             big_endian: bool = True, fill_bits: int = 0, level: int = 0,
-                            timing: bool = False):
-        """Register a plane from its Zarr v2 chunks (C order over the chunk grid; None or
+                            timing: bool = False, crc32c: bool = False):
+        """Register a plane from its Zarr chunks (C order over the chunk grid; None or
         b"" = missing chunk -> fill; or pack_chunks()' (data, offsets) pair), decoded on the GPU
-        (pbx_plane_register_zarr).  codec is
-        the .zarray compressor id: None, "blosc" or "zlib".  Returns the plane id (and the
+        (pbx_plane_register_zarr).  codec is the .zarray compressor id or the v3 codec name: None,
+        "blosc", "zlib", "zstd" or "gzip"; crc32c: every chunk ends in the v3 crc32c codec's
+        checksum (checked on the GPU).  Returns the plane id (and the
         decode / placement kernels' device ms with timing=True)."""
         if codec not in ZARR_CODECS:
             raise PbxError(400, "unsupported Zarr compressor %r" % (codec,))
@@ -657,6 +891,7 @@ class PixelsService:
         d.byte_order = BIG_ENDIAN if big_endian else LITTLE_ENDIAN
         zc = PbxZarrChunks()
         zc.chunk_x, zc.chunk_y, zc.codec = chunk_x, chunk_y, ZARR_CODECS[codec]
+        zc.flags = ZARR_F_CRC32C if crc32c else 0
         zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, fill_bits
         pid = ctypes.c_uint64()
         ms = (ctypes.c_double * 2)()
@@ -668,7 +903,7 @@ class PixelsService:
         """Several Zarr planes decoded by one set of GPU launches (pbx_planes_register_zarr):
         each dict holds register_zarr_plane's arguments (image_id, z, c, t, pixel_type,
         size_x, size_y, chunk_x, chunk_y, codec, chunks[, big_endian, fill_bits,
-        level]).  All are registered or none.  Returns the plane ids (and the kernels'
+        level, crc32c]).  All are registered or none.  Returns the plane ids (and the kernels'
         device ms with timing=True).  If some dict has chunk_planes > 1 (chunks that hold
         several planes, with its slice; zarr_plane_spec), the planes go through
         register_zarr_planes_deep, those with an equal "layer" sharing one set of chunks."""
@@ -681,7 +916,7 @@ class PixelsService:
                     index[key] = len(layers)
                     layers.append(dict(chunk_x=p["chunk_x"], chunk_y=p["chunk_y"], codec=p["codec"],
                                        chunks=p["chunks"], fill_bits=p.get("fill_bits", 0),
-                                       chunk_planes=p.get("chunk_planes", 1)))
+                                       chunk_planes=p.get("chunk_planes", 1), crc32c=p.get("crc32c", False)))
                 refs.append((index[key], p.get("slice", 0)))
             return self.register_zarr_planes_deep(planes, refs, layers, timing)
         n = len(planes)
@@ -701,6 +936,7 @@ class PixelsService:
             d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
             zc = zcs[k]
             zc.chunk_x, zc.chunk_y, zc.codec = p["chunk_x"], p["chunk_y"], ZARR_CODECS[p["codec"]]
+            zc.flags = ZARR_F_CRC32C if p.get("crc32c") else 0
             zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, p.get("fill_bits", 0)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
@@ -713,7 +949,7 @@ class PixelsService:
         """pbx_planes_register_zarr_deep: planes[k] (image_id, z, c, t, pixel_type, size_x, size_y
         [, big_endian, level]) is slice refs[k][1] of every chunk of layers[refs[k][0]]; a layer
         is a dict of chunk_x, chunk_y, codec, chunks (as register_zarr_plane), chunk_planes
-        [, fill_bits].  Every chunk is uploaded and decoded once.  Returns as
+        [, fill_bits, crc32c].  Every chunk is uploaded and decoded once.  Returns as
         register_zarr_planes."""
         n, nl = len(planes), len(layers)
         descs = (PbxPlaneDesc * n)()
@@ -738,6 +974,7 @@ class PixelsService:
             keep += [offsets, data]
             zc = zcs[k]
             zc.chunk_x, zc.chunk_y, zc.codec = l["chunk_x"], l["chunk_y"], ZARR_CODECS[l["codec"]]
+            zc.flags = ZARR_F_CRC32C if l.get("crc32c") else 0
             zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, l.get("fill_bits", 0)
             depths[k] = l.get("chunk_planes", 1)
         ids = (ctypes.c_uint64 * n)()
@@ -748,7 +985,8 @@ class PixelsService:
 
     def register_zarr_array(self, array_dir: str, image_id: int, z: int, c: int, t: int,
                             level: int = 0) -> int:
-        """One (t, c, z) plane of an NGFF multiscale dataset (a Zarr v2 array directory with
+        """One (t, c, z) plane of an NGFF multiscale dataset (a Zarr v2 array directory, or a v3
+        one: zarr.json and no .zarray, chunks or shards, zarr3_array_meta; with
         shape [..., y, x], NGFF order t, c, z, y, x) — what ZarrPixelBuffer reads through
         JZarr (omero-zarr-pixel-buffer 0.6.1, build.gradle:57).  Chunks of the plane are read
         from disk here and decoded on the GPU."""
@@ -767,7 +1005,7 @@ class PixelsService:
                                    level: int = 0, axes=None) -> Dict[Tuple[int, int, int], int]:
         """Every (z, c, t) plane of an NGFF array (or the given ones) decoded by ONE set of GPU
         launches (pbx_planes_register_zarr).  Returns {(z, c, t): plane id}."""
-        meta = zarr_array_meta(array_dir)
+        meta = _array_meta(array_dir)
         if planes is None:
             planes = self._array_planes(meta, axes)
         cache: dict = {}  # planes of one deep chunk share its files: read once, decoded once
@@ -780,7 +1018,8 @@ class PixelsService:
                             ) -> Dict[int, Dict[Tuple[int, int, int], int]]:
         """A whole NGFF multiscale image -- what ZarrPixelsService opens for an image
         (omero-zarr-pixel-buffer 0.6.1, build.gradle:57; PixelBufferVerticle.java:29,56) -- in
-        ONE set of GPU launches: .zattrs "multiscales"[0] lists the datasets from full
+        ONE set of GPU launches: "multiscales"[0] (.zattrs, or the "ome" attributes of an NGFF 0.5
+        group's zarr.json; ngff_multiscales) lists the datasets from full
         resolution down; dataset k becomes stored level k of every (z, c, t) plane (or of the
         given ones).  A bioformats2raw container (root .zattrs with "bioformats2raw.layout")
         is opened at its series 0.  Requests then select levels with OMERO's numbering:
@@ -791,7 +1030,7 @@ class PixelsService:
         specs, keys, cache = [], [], {}
         for k, ds in enumerate(ms["datasets"]):
             adir = os.path.join(root, ds["path"])
-            meta = zarr_array_meta(adir)
+            meta = _array_meta(adir)
             for z, c, t in (planes if planes is not None else self._array_planes(meta, axes)):
                 specs.append(zarr_plane_spec(adir, image_id, z, c, t, k, meta, axes, cache))
                 keys.append((k, (z, c, t)))
@@ -903,11 +1142,11 @@ class PixelsService:
 
     def band_write_zarr(self, plane_id: int, y0: int, rows: int, chunk_x: int, chunk_y: int,
                         codec: Optional[str], chunks: Sequence[Optional[bytes]], fill_bits: int = 0,
-                        timing: bool = False, chunk_planes: int = 1, slice: int = 0):
+                        timing: bool = False, chunk_planes: int = 1, slice: int = 0, crc32c: bool = False):
         """pbx_band_write_zarr: rows [y0, y0 + rows) of one band, decoded on the GPU from the
         Zarr chunk rows y0 // chunk_y .. ceil((y0 + rows) / chunk_y) - 1 that cover them (each
         full width, C order; None or b"" = missing chunk -> fill; or pack_chunks()' (data,
-        offsets) pair).  codec as register_zarr_plane.  With timing=True returns the decode /
+        offsets) pair).  codec and crc32c as register_zarr_plane.  With timing=True returns the decode /
         placement kernels' device ms.  chunk_planes > 1: the chunks hold that many planes and
         the rows are those of slice `slice` of each (pbx_band_write_zarr_deep)."""
         if codec not in ZARR_CODECS:
@@ -915,6 +1154,7 @@ class PixelsService:
         data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
         zc = PbxZarrChunks()
         zc.chunk_x, zc.chunk_y, zc.codec = chunk_x, chunk_y, ZARR_CODECS[codec]
+        zc.flags = ZARR_F_CRC32C if crc32c else 0
         zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, fill_bits
         ms = (ctypes.c_double * 2)()
         if chunk_planes == 1 and slice == 0:
@@ -1063,7 +1303,7 @@ class PixelsService:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
                                                      chunk_planes=sp.get("chunk_planes", 1),
-                                                     slice=sp.get("slice", 0))
+                                                     slice=sp.get("slice", 0), crc32c=sp.get("crc32c", False))
                             else:
                                 self.band_write(pid, r0, r1 - r0,
                                                 source.read_rows(pixels, z, c, t, level, r0, r1 - r0))
@@ -1429,7 +1669,7 @@ class NgffSource(PixelSource):
             if ent is None:
                 ms, root = ngff_multiscales(self.images[image_id])
                 dirs = [os.path.join(root, ds["path"]) for ds in ms["datasets"]]
-                ent = self._opened[image_id] = (ms.get("axes"), [(d, zarr_array_meta(d)) for d in dirs])
+                ent = self._opened[image_id] = (ms.get("axes"), [(d, _array_meta(d)) for d in dirs])
             return ent
 
     def get_pixels(self, image_id: int) -> Optional[Pixels]:
