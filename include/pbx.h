@@ -354,6 +354,47 @@ int pbx_planes_register_zarr_deep(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc
 int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                              const pbx_zarr_chunks* chunks, int32_t chunk_planes, int32_t slice,
                              double* kernel_ms);
+/* TIFF / OME-TIFF planes.  For an image without an NGFF fileset the reference's
+ * ZarrPixelsService (config.yaml:18) falls back to the ordinary OMERO PixelsService: Bio-Formats
+ * pixel buffers over the original files, whose getTileDirect decompresses strips or tiles on the
+ * CPU for every request (TileRequestHandler.java:201-211 getPixelBuffer, :107-109).  Here the
+ * caller reads the file's IFD and hands over the plane's segments as they lie in the file; they
+ * are decoded ONCE on the GPU into a resident plane, which then serves tiles like any other:
+ *   NONE     segments copied (k_zarr_copy);
+ *   LZW      TIFF 6.0 section 13 (MSB-first codes, "early change"), k_tiff_lzw, one wave a segment;
+ *   DEFLATE  zlib streams (compression 8, and 32946 which the caller maps to 8), k_zarr_inflate2,
+ *            Adler-32 checked;
+ * then Predictor = 2 (horizontal differencing over whole samples in the file's byte order) is
+ * undone per segment row (k_tiff_unpred) and k_zarr_place puts the segments into the plane.
+ * Not supported (400 by the caller or here): SamplesPerPixel != 1, Predictor 3, FillOrder 2,
+ * pre-6.0 (LSB-first) LZW streams, JPEG / PackBits / other compressions.
+ * The JNI shim does not wrap these calls (as the deep Zarr calls). */
+enum pbx_tiff_compression { PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8 };
+typedef struct pbx_tiff_segments {
+    int32_t seg_w, seg_h;       /* tiles: TileWidth x TileLength (edge tiles are full, padded);
+                                   strips: ImageWidth x RowsPerStrip (the last strip holds only
+                                   the rows left) */
+    int32_t tiled;              /* 0 strips, else tiles */
+    int32_t compression;        /* enum pbx_tiff_compression */
+    int32_t predictor;          /* 1 none, 2 horizontal differencing (integer samples only) */
+    int32_t flags;              /* 0 */
+    const uint8_t* data;        /* the segments' bytes, concatenated in C order over the grid */
+    const uint64_t* offsets;    /* gx * gy + 1 offsets into data (as pbx_zarr_chunks); a strip
+                                   image has gx = 1 */
+} pbx_tiff_segments;            /* 40 bytes */
+/* n planes from their TIFF segments in ONE set of launches, as pbx_planes_register_zarr: keys,
+ * statuses, pinned staging and all-or-none are the same.  descs[k].byte_order is the FILE's byte
+ * order (II little, MM big): the plane keeps it, nothing is swapped at load time.
+ * 400 on the host for: null pointers, offsets that decrease, an empty segment (TIFF has no missing
+ * chunk), seg_w / seg_h < 1, tiles whose width or length is not a multiple of 16 (TIFF 6.0
+ * section 15), a strip width != size_x, a compression outside {1, 5, 8}, a predictor outside
+ * {1, 2} or predictor 2 on float / double, flags != 0, an uncompressed segment whose length is not
+ * its rows' bytes, an old-style LZW stream (first byte 0 and bit 0 of the second set: libtiff's
+ * test).  A stream the device rejects (bad LZW code, fewer bytes than the segment holds, bad
+ * deflate data or Adler-32) is 400 and nothing is registered.  A missing LZW EOI is accepted, as
+ * libtiff accepts it.  kernel_ms (may be NULL): [0] decoders + un-predictor, [1] placement. */
+int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
+                             const pbx_tiff_segments* segs, uint64_t* plane_ids, double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -610,6 +651,13 @@ int pbx_test_batch_lz77(pbx_ctx* ctx, pbx_batch* b, uint32_t* hist, uint32_t* mr
 int pbx_test_zarr_plan(const pbx_zarr_chunks* chunks, int32_t size_x, int32_t size_y, int32_t bpp,
                        int32_t chunk_planes, const int32_t* slices, int32_t nslices, int32_t y0,
                        int32_t rows, uint64_t out[4]);
+
+/* Test hook: the host planner of pbx_planes_register_tiff alone (no context, no device call) for
+ * a plane of size_x x size_y samples of bpp bytes.  out: streams planned, the sum of their decoded
+ * lengths (every segment's own rows: a short last strip counts its rows, an edge tile is full),
+ * scratch bytes, 1 if the un-predictor launch is needed.  400 as the real call. */
+int pbx_test_tiff_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
+                       uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,242 @@
+// kernels_tiff_src.hip — planes loaded from TIFF / OME-TIFF segments (strips or tiles), the step
+// before getTileDirect when the reference's pixels service falls back from ZarrPixelsService to
+// the Bio-Formats pixel buffers over the original files (config.yaml:18).
+//
+//   k_tiff_lzw      one wave per strip or tile: TIFF 6.0 §13 LZW (MSB-first codes, Clear = 256,
+//                   EOI = 257, first free code 258, "early change" code widths)
+//   k_tiff_unpred   one wave per segment row: the inverse of Predictor = 2 (a prefix sum over
+//                   the row's samples in the file's byte order, modulo 2^bits)
+//
+// Deflate segments go through k_zarr_inflate2 and stored ones through k_zarr_copy; every kind
+// is placed by k_zarr_place (kernels_zarr.hip).
+//
+// LZW as LZ77 sequences.  Between two Clear codes the position of every code in the stream is
+// known without decoding: code j (j = 0 right after the Clear) is 9 + [j >= 254] + [j >= 766] +
+// [j >= 1790] bits wide, so lane k of a round fetches code j0 + k directly and one ballot cuts
+// the round at the first Clear / EOI.  A code < 256 is a literal; a code c >= 258 names table
+// entry e = c - 258 = (string of code e) + (first byte of code e + 1), whose bytes are already
+// in the output at pos[e]: a match of pos[e + 1] - pos[e] + 1 bytes from there (e = j - 1, the
+// KwKwK case, is the overlapping copy).  The dictionary is the array pos[] of output offsets of
+// the codes since the last Clear, in LDS.  A code of the round may name an entry made earlier
+// in the same round: those lengths are resolved by a scalar walk (readlane + add), and the
+// round's sequences go to seq_batch (zarr_dev.h).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dev_util.h"
+#include "pbx_common.h"
+#include "pbx_kernels.h"
+#include "zarr_dev.h"
+
+namespace pbx {
+
+constexpr uint32_t LZW_JMAX = 3838;   // codes between two Clears: code values end at 4095 = 257 + 3838
+constexpr uint32_t LZW_WAVES = 2;     // streams (waves) per workgroup
+constexpr uint32_t LZW_POS = ZR_LZ4 + ZWIN + 64 + 128;            // pos[]: 3840 words
+constexpr uint32_t LZW_BYTES = LZW_POS + 4 * 3840 + 320;          // per wave (20.5 KiB: three workgroups, 6 waves, a CU)
+static_assert(LZW_BYTES % 256 == 0, "the ring of every wave is 256-byte aligned");
+static_assert(LZW_WAVES * LZW_BYTES <= 64 * 1024, "default dynamic LDS limit");
+
+// bits of the codes 0 .. j - 1 after a Clear
+__device__ __forceinline__ uint32_t lzw_bits_before(uint32_t j) {
+    return 9 * j + (j > 254 ? j - 254 : 0u) + (j > 766 ? j - 766 : 0u) + (j > 1790 ? j - 1790 : 0u);
+}
+
+// err[]: 0, or 1 fewer bytes than dlen, 2 a code beyond the next free one, 3 a string past
+// dlen (or a match before the stream's start), 4 no Clear before the table is full.
+__global__ __launch_bounds__(64 * LZW_WAVES) void k_tiff_lzw(const ZStream* __restrict__ st, uint32_t n,
+                                                             const uint8_t* __restrict__ src,
+                                                             uint8_t* __restrict__ dst, uint32_t* __restrict__ err) {
+    const uint32_t lane = threadIdx.x & 63, w = rfl(threadIdx.x >> 6);  // wave-uniform (SGPR) state
+    const uint32_t si = blockIdx.x * LZW_WAVES + w;
+    if (si >= n) return;
+    const ZStream t = st[si];
+    const uint64_t ibits = (uint64_t)rfl(t.csize) * 8;
+    const uint32_t wb = w * LZW_BYTES;
+    InWin win{src + t.src_off, wb + ZR_LZ4, 0, lane};
+    win.load(0);
+    OutRing<ZR_LZ4> o{wb, dst + t.dst_off, 0, 0, t.dlen, lane, wb + ZR_LZ4 + ZWIN};
+    const uint32_t FLAG = wb + ZR_LZ4 + ZWIN + 64, POS = wb + LZW_POS;
+    uint32_t q0 = 0, b0 = 0;  // byte and bit (0..7, from the MSB) of code j0
+    uint32_t j0 = 0, bad = 0;
+    if (lane == 0) lds32(POS) = 0;  // (a stream need not begin with a Clear)
+    for (;;) {
+        q0 = rfl(q0); b0 = rfl(b0); j0 = rfl(j0); o.op = rfl(o.op); o.flushed = rfl(o.flushed);
+        const uint32_t op0 = o.op;
+        if (op0 >= o.olen) break;
+        // the window holds the round's 64 codes (<= 96 bytes) and the last one's dword
+        if (q0 < win.base || q0 + 104 > win.base + ZWIN) win.load(q0);
+        const uint32_t j = j0 + lane;
+        const uint32_t wd = 9 + (j >= 254) + (j >= 766) + (j >= 1790);
+        const uint32_t rel = b0 + lzw_bits_before(j) - lzw_bits_before(j0);  // < 8 + 64 * 12
+        const bool inside = (uint64_t)q0 * 8 + rel + wd <= ibits;
+        const uint32_t at = q0 - win.base + (rel >> 3);
+        const uint32_t be = __builtin_bswap32(ld_u32_unaligned(zlds + win.wo + (at < ZWIN - 4 ? at : ZWIN - 4)));
+        const uint32_t c = (be >> (32 - (rel & 7) - wd)) & ((1u << wd) - 1);
+        // the round ends at the first Clear, EOI, end of input (taken as EOI, like a missing
+        // one) or full table
+        const bool full = j >= LZW_JMAX && c != 256;
+        const uint64_t E = __ballot(!inside || c == 256 || c == 257 || full);
+        const uint32_t f = E ? (uint32_t)__builtin_ctzll(E) : 64u;
+        const bool act = lane < f;
+        const uint32_t e = c - 258;  // (c >= 258) the table entry
+        const bool lit = c < 256;
+        const bool wrong = act && !lit && e >= j;  // not yet defined
+        const bool mt = act && !lit && !wrong;
+        // lengths: 1, or pos[e + 1] - pos[e] + 1; pos[e + 1] of an entry of this round is not
+        // known yet: length of the code that made it + 1
+        const uint32_t ec = mt ? e : 0u;
+        const uint32_t pe = lds32(POS + 4 * ec), pe1 = lds32(POS + 4 * ec + 4);
+        const bool dep = mt && e >= j0;
+        uint32_t len = !act ? 0u : (mt && !dep) ? pe1 - pe + 1 : 1u;
+        const uint32_t r = dep ? e - j0 : 0u;  // < lane
+        uint64_t D = __ballot(dep);
+        while (D) {
+            const uint32_t k = (uint32_t)__builtin_ctzll(D);
+            const uint32_t L = rdl(len, rdl(r, k)) + 1;
+            len = lane == k ? L : len;
+            D &= D - 1;
+        }
+        const uint32_t end = wave_incl_add(len, lane), st0 = end - len;
+        // the codes up to the one that completes dlen (what follows it is not read: padding,
+        // or a stream without EOI)
+        const uint32_t rem = o.olen - op0;
+        const uint64_t G = __ballot(act && end >= rem);
+        const uint32_t nc = G ? (uint32_t)__builtin_ctzll(G) + 1 : f;
+        if (__ballot(wrong && lane < nc)) { bad = 2; break; }
+        if (nc) {
+            // (the shuffle by every lane: inside the ?: only the dep lanes would run it, and it
+            // reads nothing from a lane that does not)
+            const uint32_t sr = (uint32_t)__shfl((int)st0, (int)r, 64);
+            const uint32_t sp = dep ? op0 + sr : pe;  // the entry's bytes
+            const uint32_t boff = mt ? op0 + st0 - sp : 0u;
+            // the next codes' starts (pos[j0] is there already)
+            lds32(lane < nc ? POS + 4 * (j + 1) : FLAG + 64) = op0 + end;
+            if (!seq_batch(o, FLAG, lane, nc, lit ? 1u : 0u, mt ? len : 0u, boff, c,
+                           [](uint32_t v, uint32_t, bool) -> uint32_t { return v; })) {
+                bad = 3;
+                break;
+            }
+        }
+        if (rfl(o.op) >= o.olen) break;  // dlen is out: what follows (padding, no EOI) is not read
+        if (f == 64) {  // a whole round of codes
+            j0 += 64;
+            const uint32_t adv = b0 + lzw_bits_before(j0) - lzw_bits_before(j0 - 64);
+            q0 += adv >> 3;
+            b0 = adv & 7;
+            continue;
+        }
+        // lane f ended the round
+        const uint32_t cf = rdl(c, f), inf = rdl((uint32_t)inside, f), fullf = rdl((uint32_t)full, f);
+        if (!inf || cf == 257) break;          // EOI: op < olen is the error below
+        if (fullf) { bad = 4; break; }
+        const uint32_t adv = rdl(rel, f) + rdl(wd, f);  // past the Clear
+        q0 += adv >> 3;
+        b0 = adv & 7;
+        j0 = 0;
+        if (lane == 0) lds32(POS) = o.op;
+    }
+    if (!bad && o.op != o.olen) bad = 1;
+    o.finish();
+    if (lane == 0) err[si] = bad;
+}
+
+// ------------------------------------------------------------------------ un-predictor
+// One wave per row of a decoded segment, UP_ROWS rows per workgroup wave: 16 bytes (16 / bpp
+// samples) a lane a step, a running sum inside the lane, a wave scan of the lanes' totals and a
+// carry from step to step.  Rows are the segment's own (a tile's padded width), so no carry
+// crosses a tile.  Sums are taken on the samples' values (byte-swapped in and out for a
+// big-endian file) and wrap modulo 2^bits.
+constexpr uint32_t UP_WAVES = 4, UP_ROWS = 16;  // rows per workgroup
+
+template <uint32_t BPP>
+__device__ __forceinline__ void unpred_row(uint8_t* row, uint32_t rb, bool be, uint32_t lane) {
+    constexpr uint32_t NS = 16 / BPP;
+    constexpr uint32_t MASK = BPP == 4 ? 0xffffffffu : (1u << (8 * (BPP & 3))) - 1;
+    uint32_t carry = 0;
+    for (uint32_t k0 = 0; k0 < rb; k0 += 1024) {
+        const uint32_t off = k0 + 16 * lane;
+        const uint32_t have = off >= rb ? 0u : rb - off < 16 ? rb - off : 16u;  // a multiple of BPP
+        uint32_t wv[4] = {0, 0, 0, 0};
+        if (have == 16) {
+            __builtin_memcpy(wv, row + off, 16);
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 16; b++)
+                if (b < have) wv[b >> 2] |= (uint32_t)row[off + b] << (8 * (b & 3));
+        }
+        uint32_t s[NS];
+        uint32_t run = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < NS; i++) {
+            uint32_t v;
+            if (BPP == 4) {
+                v = wv[i];
+                v = be ? __builtin_bswap32(v) : v;
+            } else if (BPP == 2) {
+                v = (wv[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+                v = be ? ((v >> 8) | (v << 8)) & 0xffffu : v;
+            } else {
+                v = (wv[i >> 2] >> (8 * (i & 3))) & 0xffu;
+            }
+            run += v;
+            s[i] = run;
+        }
+        const uint32_t inc = wave_incl_add(run, lane);
+        const uint32_t base = carry + inc - run;
+        carry += rdl(inc, 63);
+        uint32_t ov[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (uint32_t i = 0; i < NS; i++) {
+            uint32_t v = (s[i] + base) & MASK;
+            if (BPP == 4) {
+                ov[i] = be ? __builtin_bswap32(v) : v;
+            } else if (BPP == 2) {
+                v = be ? ((v >> 8) | (v << 8)) & 0xffffu : v;
+                ov[i >> 1] |= v << (16 * (i & 1));
+            } else {
+                ov[i >> 2] |= v << (8 * (i & 3));
+            }
+        }
+        if (have == 16) {
+            __builtin_memcpy(row + off, ov, 16);
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 16; b++)
+                if (b < have) row[off + b] = (uint8_t)(ov[b >> 2] >> (8 * (b & 3)));
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * UP_WAVES) void k_tiff_unpred(const TUnpred* __restrict__ sg,
+                                                               uint8_t* __restrict__ scratch) {
+    const uint32_t lane = threadIdx.x & 63, w = rfl(threadIdx.x >> 6);
+    const TUnpred u = sg[blockIdx.x];
+    const uint32_t rows = rfl(u.rows), rb = rfl(u.row_bytes), bpp = rfl(u.bpp);
+    const bool be = rfl(u.big_endian) != 0;
+    const uint32_t r1 = blockIdx.y * UP_ROWS + UP_ROWS < rows ? blockIdx.y * UP_ROWS + UP_ROWS : rows;
+    for (uint32_t r = blockIdx.y * UP_ROWS + w; r < r1; r += UP_WAVES) {
+        uint8_t* row = scratch + u.off + (uint64_t)r * rb;
+        if (bpp == 1) unpred_row<1>(row, rb, false, lane);
+        else if (bpp == 2) unpred_row<2>(row, rb, be, lane);
+        else unpred_row<4>(row, rb, be, lane);
+    }
+}
+
+hipError_t launch_tiff_lzw(hipStream_t st, const ZStream* d_streams, uint32_t n, const uint8_t* src,
+                           uint8_t* scratch, uint32_t* err) {
+    if (!n) return hipSuccess;
+    hipLaunchKernelGGL(k_tiff_lzw, dim3((n + LZW_WAVES - 1) / LZW_WAVES), dim3(64 * LZW_WAVES),
+                       LZW_WAVES * LZW_BYTES, st, d_streams, n, src, scratch, err);
+    return hipGetLastError();
+}
+
+hipError_t launch_tiff_unpred(hipStream_t st, const TUnpred* d_segs, uint32_t n, uint32_t max_rows,
+                              uint8_t* scratch) {
+    if (!n || !max_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tiff_unpred, dim3(n, (max_rows + UP_ROWS - 1) / UP_ROWS), dim3(64 * UP_WAVES), 0, st,
+                       d_segs, scratch);
+    return hipGetLastError();
+}
+
+}  // namespace pbx

@@ -1484,7 +1484,7 @@ hipError_t launch_zarr_crc(hipStream_t st, const ZCheck* d_checks, uint32_t n_wa
 
 hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const uint32_t* counts,
                               const uint8_t* src, uint8_t* scratch, uint8_t* zstd_lit, uint32_t* err) {
-    // streams are ordered by kind: lz4, inflate, copy, blosclz, zstd, gzip
+    // streams are ordered by kind: lz4, inflate, copy, blosclz, zstd, gzip, lzw
     uint32_t first = 0;
     for (uint32_t k = 0; k < ZS_NKINDS; k++) {
         const uint32_t n = counts[k];
@@ -1512,6 +1512,11 @@ hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const ui
             break;
         case ZS_COPY: hipLaunchKernelGGL(k_zarr_copy, g, b, 0, st, s, n, src, scratch, e); break;
         case ZS_BLOSCLZ: hipLaunchKernelGGL(k_zarr_blosclz, g, b, ZWAVES * ZL_BYTES, st, s, n, src, scratch, e); break;
+        case ZS_LZW: {
+            hipError_t r = launch_tiff_lzw(st, s, n, src, scratch, e);
+            if (r != hipSuccess) return r;
+            break;
+        }
         default: {
             hipError_t r = launch_zarr_zstd(st, s, n, src, scratch, zstd_lit, e);
             if (r != hipSuccess) return r;

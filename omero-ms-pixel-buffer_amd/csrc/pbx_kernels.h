@@ -114,7 +114,8 @@ hipError_t launch_huffman(hipStream_t st, uint32_t nblk, BlkInfo* blk, SegInfo* 
 // ZS_GZIP: a raw deflate body followed by the 8 trailer bytes of its RFC 1952 member (the host
 // has parsed the header); k_zarr_inflate2 takes no zlib header and no Adler-32 for it and
 // requires the deflate data to end exactly 8 bytes before the stream's end.
-enum : uint32_t { ZS_LZ4 = 0, ZS_ZLIB = 1, ZS_COPY = 2, ZS_BLOSCLZ = 3, ZS_ZSTD = 4, ZS_GZIP = 5, ZS_NKINDS = 6 };
+// ZS_LZW: a TIFF 6.0 LZW strip or tile (kernels_tiff_src.hip).
+enum : uint32_t { ZS_LZ4 = 0, ZS_ZLIB = 1, ZS_COPY = 2, ZS_BLOSCLZ = 3, ZS_ZSTD = 4, ZS_GZIP = 5, ZS_LZW = 6, ZS_NKINDS = 7 };
 struct ZStream {
     uint64_t src_off;  // compressed bytes in the uploaded chunk buffer
     uint64_t dst_off;  // decoded bytes in the scratch buffer
@@ -140,7 +141,7 @@ struct ZPlane {                           // a destination plane of one decode l
     uint64_t fill;                        // fill bytes in stored order (missing chunks)
     int32_t y_lo, y_hi;                   // plane rows k_zarr_place may write: [y_lo, y_hi)
 };
-// Streams ordered by kind (ZS_LZ4 | ZS_ZLIB | ZS_COPY | ZS_BLOSCLZ | ZS_ZSTD | ZS_GZIP), counts[k] of
+// Streams ordered by kind (ZS_LZ4 | ZS_ZLIB | ZS_COPY | ZS_BLOSCLZ | ZS_ZSTD | ZS_GZIP | ZS_LZW), counts[k] of
 // kind k; err[i] = 0 or a decoder error code per stream.
 // zstd_lit: zstd_scratch_bytes(counts[ZS_ZSTD]) bytes (a block's literals per zstd frame).
 hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const uint32_t* counts,
@@ -169,5 +170,19 @@ hipError_t launch_zarr_crc(hipStream_t st, const ZCheck* d_checks, uint32_t n_wa
 hipError_t launch_zarr_place(hipStream_t st, const ZChunk* d_chunks, uint32_t nchunks,
                              const ZPlane* d_planes, int32_t max_chunk_y, const uint8_t* scratch,
                              const uint8_t* input);
+
+// TIFF segments (kernels_tiff_src.hip).  k_tiff_lzw: one wave per ZS_LZW stream, err[] as the
+// Zarr decoders'.  k_tiff_unpred: the inverse of Predictor = 2 in place on decoded segments in
+// scratch: `rows` rows of row_bytes bytes (a multiple of bpp = 1, 2 or 4) from `off`; max_rows =
+// the tallest segment of the launch.
+struct TUnpred {
+    uint64_t off;
+    uint32_t row_bytes, rows, bpp, big_endian;
+};
+static_assert(sizeof(TUnpred) == 24, "TUnpred is uploaded as is");
+hipError_t launch_tiff_lzw(hipStream_t st, const ZStream* d_streams, uint32_t n, const uint8_t* src,
+                           uint8_t* scratch, uint32_t* err);
+hipError_t launch_tiff_unpred(hipStream_t st, const TUnpred* d_segs, uint32_t n, uint32_t max_rows,
+                              uint8_t* scratch);
 
 }  // namespace pbx

@@ -2328,6 +2328,8 @@ struct ZarrPlan {
                                            // CRC-32C of crc32c chunks' uploaded bytes (input)
     uint64_t scratch = 0;
     uint64_t skipped = 0;  // blosc blocks left undecoded (deep chunks only)
+    std::vector<TUnpred> unpred;  // TIFF segments whose rows are horizontally differenced
+    uint32_t unpred_rows = 0;     // the tallest of them
 };
 
 // A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
@@ -2589,7 +2591,8 @@ struct ZarrInput {
 // decoders of P's streams and places P's chunks into the destinations `zp` (plane or band
 // bases and their row windows), then waits for it all.  The launch scratch (input, decoded
 // chunks, tables) comes from the context's device pool and goes back to it.  400 for a stream
-// a decoder rejects; rows already placed are then the caller's to discard.
+// a decoder rejects; rows already placed are then the caller's to discard.  P.unpred (TIFF
+// segments stored with Predictor = 2) is undone in scratch between the decoders and the placement.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms) {
     uint32_t counts[ZS_NKINDS], nstreams = 0;
@@ -2616,13 +2619,14 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     ZCheck* d_ck = nullptr;
     ZChunk* d_ch = nullptr;
     ZPlane* d_pl = nullptr;
+    TUnpred* d_up = nullptr;
     uint32_t* d_err = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto cleanup = [&] {
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2638,6 +2642,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (nchecks) dget(d_ck, sizeof(ZCheck) * nchecks);
     dget(d_ch, sizeof(ZChunk) * P.chunks.size());
     dget(d_pl, sizeof(ZPlane) * zp.size());
+    if (!P.unpred.empty()) dget(d_up, sizeof(TUnpred) * P.unpred.size());
     dget(d_err, sizeof(uint32_t) * (nerr + 1));
     for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
     if (e != hipSuccess) {
@@ -2661,6 +2666,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess)
         e = hipMemcpyAsync(d_ch, P.chunks.data(), sizeof(ZChunk) * P.chunks.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_pl, zp.data(), sizeof(ZPlane) * zp.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_up)
+        e = hipMemcpyAsync(d_up, P.unpred.data(), sizeof(TUnpred) * P.unpred.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
     // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
@@ -2673,6 +2680,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess) e = crc(ZK_CRC32C);
     if (e == hipSuccess) e = launch_zarr_decode(st, d_st, counts, d_in, d_scr, d_lit, d_err);
     if (e == hipSuccess) e = crc(ZK_CRC32);
+    if (e == hipSuccess && d_up) e = launch_tiff_unpred(st, d_up, (uint32_t)P.unpred.size(), P.unpred_rows, d_scr);
     if (e == hipSuccess) e = hipEventRecord(ev[1], st);
     if (e == hipSuccess) e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
@@ -2686,7 +2694,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     }
     for (uint32_t s = 0; s < nstreams; s++)
         if (err[s]) {
-            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd", "gzip"};
+            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd", "gzip", "lzw"};
             uint32_t k = 0, first = 0;
             while (s >= first + counts[k]) first += counts[k++];
             cleanup();
@@ -2738,20 +2746,98 @@ int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     });
 }
 
+// ------------------------------------------------------------------ TIFF / OME-TIFF planes
+static_assert(sizeof(pbx_tiff_segments) == 40, "pbx_tiff_segments is part of the C-ABI (ctypes mirror PbxTiffSegments)");
+// pbx_tiff_segments fields that can be checked without the plane.
+int tiff_segments_check(const pbx_tiff_segments* s) {
+    if (!s->data || !s->offsets) return fail(PBX_E_BADARG, "null argument");
+    if (s->seg_w < 1 || s->seg_h < 1) return fail(PBX_E_BADARG, "bad segment shape %d x %d", s->seg_w, s->seg_h);
+    if (s->tiled && ((s->seg_w | s->seg_h) & 15))
+        return fail(PBX_E_BADARG, "tile %d x %d: TileWidth and TileLength must be multiples of 16 (TIFF 6.0 section 15)",
+                    s->seg_w, s->seg_h);
+    if (s->compression != PBX_TIFF_NONE && s->compression != PBX_TIFF_LZW && s->compression != PBX_TIFF_DEFLATE)
+        return fail(PBX_E_BADARG, "bad compression %d (1 none, 5 LZW, 8 deflate)", s->compression);
+    if (s->predictor != 1 && s->predictor != 2) return fail(PBX_E_BADARG, "bad predictor %d (1 or 2)", s->predictor);
+    if (s->flags) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
+    return PBX_OK;
+}
+
+// Host plan of one plane's strips or tiles: one stream per segment (its own row count: the last
+// strip holds only the rows left), one ZChunk to place it, and for Predictor = 2 its rows for
+// k_tiff_unpred.  No byte of segment data is decoded here.
+int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pbx_tiff_segments* s,
+              uint64_t in_base, uint32_t plane, ZarrPlan& P, uint64_t* dlen_sum) {
+    if (!s->tiled && s->seg_w != size_x)
+        return fail(PBX_E_BADARG, "strip width %d != plane width %d", s->seg_w, size_x);
+    if (s->predictor == 2 && bpp == 8) return fail(PBX_E_BADARG, "predictor 2 on floating-point samples");
+    const int64_t gx = s->tiled ? ((int64_t)size_x + s->seg_w - 1) / s->seg_w : 1;
+    const int64_t gy = ((int64_t)size_y + s->seg_h - 1) / s->seg_h, n = gx * gy;
+    const uint64_t total = s->offsets[n];
+    for (int64_t i = 0; i < n; i++) {
+        const uint64_t o = s->offsets[i], len = s->offsets[i + 1] - o;
+        if (s->offsets[i + 1] < o || s->offsets[i + 1] > total)
+            return fail(PBX_E_BADARG, "segment %lld: bad offsets", (long long)i);
+        if (len == 0) return fail(PBX_E_BADARG, "segment %lld is empty", (long long)i);
+        const int32_t x0 = (int32_t)((i % gx) * s->seg_w), y0 = (int32_t)((i / gx) * s->seg_h);
+        const int32_t rows = s->tiled ? s->seg_h : std::min(s->seg_h, size_y - y0);
+        const uint64_t dlen = (uint64_t)s->seg_w * (uint64_t)rows * (uint64_t)bpp;
+        if (dlen > 0x7fffffffull || len > 0x7fffffffull || rows > (65535 << 4))
+            return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
+        const uint64_t ob = o + in_base, dst = P.scratch;
+        uint32_t kind = ZS_COPY;
+        if (s->compression == PBX_TIFF_NONE) {
+            if (len != dlen)
+                return fail(PBX_E_BADARG, "uncompressed segment %lld: %llu bytes, not %llu", (long long)i,
+                            (unsigned long long)len, (unsigned long long)dlen);
+        } else if (s->compression == PBX_TIFF_LZW) {
+            // libtiff's test for the pre-6.0 bit order (LSB first, which begins 00 01 for Clear)
+            if (len >= 2 && s->data[o] == 0 && (s->data[o + 1] & 1))
+                return fail(PBX_E_BADARG, "segment %lld: old-style (pre-6.0, LSB-first) LZW", (long long)i);
+            kind = ZS_LZW;
+        } else {
+            kind = ZS_ZLIB;
+        }
+        P.kind[kind].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)dlen, kind, 0});
+        ZChunk c{};
+        c.src = dst;
+        c.nbytes = c.blocksize = (uint32_t)dlen;
+        c.typesize = 1;
+        c.x0 = x0;
+        c.y0 = y0;
+        c.plane = plane;
+        P.chunks.push_back(c);
+        if (s->predictor == 2) {
+            P.unpred.push_back(TUnpred{dst, (uint32_t)s->seg_w * (uint32_t)bpp, (uint32_t)rows, (uint32_t)bpp,
+                                       big_endian ? 1u : 0u});
+            P.unpred_rows = std::max(P.unpred_rows, (uint32_t)rows);
+        }
+        if (dlen_sum) *dlen_sum += dlen;
+        P.scratch += (dlen + 255) & ~255ull;
+    }
+    return PBX_OK;
+}
+
 // pbx_planes_register_zarr (layer k = plane k, one plane per chunk) and its deep form: plane k
 // is slice refs[k].slice of the chunks of layer zs[refs[k].layer], which hold depths[layer]
 // planes each.  A layer's chunks are planned, uploaded and decoded once; its planes follow one
-// another in the ZChunk table.
+// another in the ZChunk table.  With `ts` the layers are TIFF segments instead (zs unused, one
+// plane per layer): pbx_planes_register_tiff shares the keys, the all-or-none registration, the
+// staging and the launches.
 int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
                          uint64_t n_layers, const pbx_zarr_chunks* zs, const int32_t* depths,
-                         uint64_t* plane_ids, double* kernel_ms) {
+                         uint64_t* plane_ids, double* kernel_ms, const pbx_tiff_segments* ts = nullptr) {
     std::vector<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t>> keys;
     std::vector<std::vector<ZarrWant>> want(n_layers);
     for (uint64_t k = 0; k < n; k++) {
         const pbx_plane_desc* d = &ds[k];
         if (refs[k].layer >= n_layers) return fail(PBX_E_BADARG, "plane %llu: no layer %u", (unsigned long long)k, refs[k].layer);
-        const pbx_zarr_chunks* z = &zs[refs[k].layer];
-        if (int rc = zarr_chunks_check(z)) return rc;
+        if (ts) {
+            if (int rc = tiff_segments_check(&ts[refs[k].layer])) return rc;
+            if (ts[refs[k].layer].predictor == 2 && (d->pixel_type == PBX_FLOAT || d->pixel_type == PBX_DOUBLE))
+                return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)k);
+        } else {
+            if (int rc = zarr_chunks_check(&zs[refs[k].layer])) return rc;
+        }
         if (int rc = zarr_slice_check(depths[refs[k].layer], refs[k].slice)) return rc;
         want[refs[k].layer].push_back(ZarrWant{refs[k].slice, (uint32_t)k});
         if (!bpp_of(d->pixel_type)) return fail(PBX_E_BADARG, "bad pixel type %d", d->pixel_type);
@@ -2798,6 +2884,18 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
     int32_t max_cy = 0;
     for (uint64_t l = 0; l < n_layers; l++) {
         const pbx_plane_desc* d = &ds[want[l][0].plane];
+        if (ts) {
+            const pbx_tiff_segments* s = &ts[l];
+            if (int rc = tiff_plan(d->size_x, d->size_y, bpp_of(d->pixel_type), d->byte_order != PBX_LITTLE_ENDIAN, s,
+                                   in_base[l], want[l][0].plane, P, nullptr))
+                return rc;
+            const int64_t gx = s->tiled ? ((int64_t)d->size_x + s->seg_w - 1) / s->seg_w : 1;
+            const int64_t gy = ((int64_t)d->size_y + s->seg_h - 1) / s->seg_h;
+            in_base[l + 1] = in_base[l] + ((s->offsets[gx * gy] + 15) & ~15ull);
+            in[l] = ZarrInput{s->data, s->offsets[gx * gy], in_base[l], in_base[l + 1] - in_base[l]};
+            max_cy = std::max(max_cy, std::min(s->seg_h, d->size_y));
+            continue;
+        }
         const pbx_zarr_chunks* z = &zs[l];
         const int64_t gx = (d->size_x + z->chunk_x - 1) / z->chunk_x, gy = (d->size_y + z->chunk_y - 1) / z->chunk_y;
         if (int rc = zarr_plan(d->size_x, z, bpp_of(d->pixel_type), in_base[l], 0, gy, depths[l], want[l], 0,
@@ -2820,6 +2918,11 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
         p.pitch = ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255;
         p.bytes = (size_t)p.pitch * d->size_y + 256;
         p.band_rows = d->size_y;
+        if (ts) {
+            const pbx_tiff_segments& s = ts[refs[k].layer];
+            zp[k] = ZPlane{nullptr, p.pitch, d->size_x, d->size_y, s.seg_w, s.seg_h, (uint32_t)bpp, 0, 0, 0, d->size_y};
+            continue;
+        }
         const pbx_zarr_chunks& z = zs[refs[k].layer];
         zp[k] = ZPlane{nullptr, p.pitch, d->size_x, d->size_y, z.chunk_x, z.chunk_y,
                        (uint32_t)bpp, 0, zarr_fill(z.fill_bits, bpp, p.little_endian), 0, d->size_y};
@@ -2900,6 +3003,32 @@ int pbx_test_zarr_plan(const pbx_zarr_chunks* z, int32_t size_x, int32_t size_y,
     }
     out[2] = P.skipped;
     out[3] = P.scratch;
+    return PBX_OK;
+}
+
+int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_tiff_segments* segs,
+                             uint64_t* plane_ids, double* kernel_ms) {
+    if (!ctx || !ds || !segs || !plane_ids || n == 0) return fail(PBX_E_BADARG, "null argument");
+    if (n > 0xffffffffull) return fail(PBX_E_BADARG, "too many planes");
+    std::vector<pbx_zarr_slice> refs(n);
+    for (uint64_t k = 0; k < n; k++) refs[k] = pbx_zarr_slice{(uint32_t)k, 0};
+    const std::vector<int32_t> depths(n, 1);
+    return register_zarr_layers(ctx, n, ds, refs.data(), n, nullptr, depths.data(), plane_ids, kernel_ms, segs);
+}
+
+int pbx_test_tiff_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t bpp, uint64_t out[4]) {
+    if (!s || !out) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = tiff_segments_check(s)) return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    if (bpp != 1 && bpp != 2 && bpp != 4 && bpp != 8) return fail(PBX_E_BADARG, "bad sample size %d", bpp);
+    ZarrPlan P;
+    uint64_t sum = 0;
+    if (int rc = tiff_plan(size_x, size_y, bpp, true, s, 0, 0, P, &sum)) return rc;
+    out[0] = 0;
+    for (const auto& k : P.kind) out[0] += k.size();
+    out[1] = sum;
+    out[2] = P.scratch;
+    out[3] = P.unpred.empty() ? 0 : 1;
     return PBX_OK;
 }
 

@@ -93,6 +93,12 @@ class PbxZarrChunks(ctypes.Structure):
                 ("fill_bits", ctypes.c_uint64)]
 
 
+class PbxTiffSegments(ctypes.Structure):
+    _fields_ = [("seg_w", ctypes.c_int32), ("seg_h", ctypes.c_int32), ("tiled", ctypes.c_int32),
+                ("compression", ctypes.c_int32), ("predictor", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("data", ctypes.c_void_p), ("offsets", ctypes.c_void_p)]
+
+
 class PbxZarrSlice(ctypes.Structure):
     _fields_ = [("layer", ctypes.c_uint32), ("slice", ctypes.c_uint32)]
 
@@ -156,7 +162,7 @@ EXPORTS = [
     "pbx_set_deflate_strategy", "pbx_get_deflate_strategy", "pbx_batch_lz_modes",
     "pbx_set_tiff_predictor", "pbx_get_tiff_predictor", "pbx_batch_pred_tiles",
     "pbx_band_write_zarr", "pbx_planes_register_zarr_deep", "pbx_band_write_zarr_deep",
-    "pbx_test_zarr_plan",
+    "pbx_test_zarr_plan", "pbx_planes_register_tiff", "pbx_test_tiff_plan",
 ]
 
 _lib = None
@@ -248,6 +254,10 @@ def lib() -> ctypes.CDLL:
                                            ctypes.POINTER(ctypes.c_double)]
     L.pbx_test_zarr_plan.argtypes = [ctypes.POINTER(PbxZarrChunks), i32, i32, i32, i32,
                                      ctypes.POINTER(i32), i32, i32, i32, ctypes.POINTER(u64)]
+    L.pbx_planes_register_tiff.argtypes = [vp, u64, ctypes.POINTER(PbxPlaneDesc),
+                                           ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(u64),
+                                           ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_tiff_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, ctypes.POINTER(u64)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -729,6 +739,282 @@ def pack_chunks(chunks: Sequence[Optional[bytes]]):
     return data, offsets
 
 
+# ----------------------------------------------------------------- TIFF / OME-TIFF files
+# The reference's pixels service falls back from NGFF to the Bio-Formats pixel buffers over the
+# original files (config.yaml:18), which for most installations are TIFF and OME-TIFF.  This is a
+# dependency-free reader of the container (classic TIFF and BigTIFF, II and MM); every byte of
+# pixel data is decoded on the GPU (pbx_planes_register_tiff).
+
+TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
+_TIFF_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4,
+                   16: 8, 17: 8, 18: 8}
+_TIFF_INT_FMT = {1: "B", 3: "H", 4: "I", 13: "I", 16: "Q", 18: "Q", 6: "b", 8: "h", 9: "i", 17: "q"}
+_TIFF_TAGS = {256: "width", 257: "length", 258: "bits", 259: "compression", 266: "fillorder",
+              270: "description", 273: "strip_offsets", 274: "orientation", 277: "spp",
+              278: "rows_per_strip", 279: "strip_counts", 317: "predictor", 322: "tile_w",
+              323: "tile_h", 324: "tile_offsets", 325: "tile_counts", 330: "subifd_offsets",
+              339: "sampleformat"}
+_TIFF_MAX_IFDS = 1 << 16
+_TIFF_PIXEL_TYPES = {(1, 8): UINT8, (2, 8): INT8, (1, 16): UINT16, (2, 16): INT16, (1, 32): UINT32,
+                     (2, 32): INT32, (3, 32): FLOAT, (3, 64): DOUBLE}
+
+
+def tiff_ifds(path: str) -> List[dict]:
+    """The IFD chain of a classic TIFF or BigTIFF file (II or MM), SubIFDs (tag 330) included,
+    without any pixel data.  One dict per main IFD: width, length, bits (BitsPerSample),
+    sampleformat, spp (SamplesPerPixel), compression, predictor, fillorder, orientation, tiled,
+    seg_w x seg_h (TileWidth x TileLength, or ImageWidth x RowsPerStrip capped at the length),
+    offsets / counts of the segments, description (ImageDescription or None), byteorder ("<" or
+    ">"), bigtiff, subifds (such dicts).  Every offset and count is checked against the file
+    size and IFD loops are refused: PbxError 400."""
+    import struct
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        def read(off: int, n: int, what: str) -> bytes:
+            if off < 0 or n < 0 or off + n > size:
+                raise PbxError(400, "%s: %s at offset %d (%d bytes) lies past the end of the file (%d bytes)"
+                               % (path, what, off, n, size))
+            f.seek(off)
+            return f.read(n)
+
+        head = read(0, 8, "header")
+        if head[:2] not in (b"II", b"MM"):
+            raise PbxError(400, "%s: not a TIFF file" % path)
+        bo = "<" if head[:2] == b"II" else ">"
+        magic = struct.unpack(bo + "H", head[2:4])[0]
+        if magic == 42:
+            big, first = False, struct.unpack(bo + "I", head[4:8])[0]
+        elif magic == 43:
+            h2 = read(0, 16, "BigTIFF header")
+            osz, zero, first = struct.unpack(bo + "HHQ", h2[4:16])
+            if osz != 8 or zero != 0:
+                raise PbxError(400, "%s: bad BigTIFF header" % path)
+            big = True
+        else:
+            raise PbxError(400, "%s: not a TIFF file (magic %d)" % (path, magic))
+        cnt_fmt, cnt_sz, ent_sz, inline, off_fmt = ("Q", 8, 20, 8, "Q") if big else ("H", 2, 12, 4, "I")
+        seen: set = set()
+
+        def ifd_at(off: int):
+            if off in seen:
+                raise PbxError(400, "%s: IFD loop at offset %d" % (path, off))
+            if len(seen) >= _TIFF_MAX_IFDS:
+                raise PbxError(400, "%s: more than %d IFDs" % (path, _TIFF_MAX_IFDS))
+            seen.add(off)
+            n = struct.unpack(bo + cnt_fmt, read(off, cnt_sz, "IFD"))[0]
+            if n > 4096:
+                raise PbxError(400, "%s: IFD at offset %d with %d entries" % (path, off, n))
+            body = read(off + cnt_sz, n * ent_sz + inline, "IFD entries")
+            d: dict = {}
+            for k in range(n):
+                e = body[k * ent_sz:(k + 1) * ent_sz]
+                tag, typ = struct.unpack(bo + "HH", e[:4])
+                count = struct.unpack(bo + off_fmt, e[4:4 + inline])[0]
+                name = _TIFF_TAGS.get(tag)
+                if name is None:
+                    continue
+                tsz = _TIFF_TYPE_SIZE.get(typ)
+                if tsz is None or (typ != 2 and typ not in _TIFF_INT_FMT):
+                    raise PbxError(400, "%s: tag %d has field type %d" % (path, tag, typ))
+                nbytes = tsz * count
+                raw = e[4 + inline:4 + inline + nbytes] if nbytes <= inline else \
+                    read(struct.unpack(bo + off_fmt, e[4 + inline:])[0], nbytes, "the value of tag %d" % tag)
+                if typ == 2:
+                    d[name] = raw.split(b"\0", 1)[0].decode("utf-8", errors="replace")
+                else:
+                    d[name] = list(struct.unpack(bo + _TIFF_INT_FMT[typ] * count, raw))
+            nxt = struct.unpack(bo + off_fmt, body[n * ent_sz:])[0]
+            return d, nxt
+
+        def finish(d: dict) -> dict:
+            def one(name, default=None):
+                v = d.get(name)
+                if v is None:
+                    if default is None:
+                        raise PbxError(400, "%s: an IFD lacks the %s tag" % (path, name))
+                    return default
+                if isinstance(v, list):
+                    if not v:
+                        raise PbxError(400, "%s: empty %s tag" % (path, name))
+                    if any(x != v[0] for x in v):  # BitsPerSample / SampleFormat per sample
+                        raise PbxError(400, "%s: samples differ in %s: %r" % (path, name, v))
+                    return v[0]
+                return v
+            out = dict(width=one("width"), length=one("length"), bits=one("bits", 1),
+                       sampleformat=one("sampleformat", 1), spp=one("spp", 1),
+                       compression=one("compression", 1), predictor=one("predictor", 1),
+                       fillorder=one("fillorder", 1), orientation=one("orientation", 1),
+                       description=d.get("description"), byteorder=bo, bigtiff=big)
+            if out["width"] < 1 or out["length"] < 1:
+                raise PbxError(400, "%s: image of %d x %d" % (path, out["width"], out["length"]))
+            if "tile_offsets" in d:
+                out.update(tiled=True, seg_w=one("tile_w"), seg_h=one("tile_h"),
+                           offsets=d["tile_offsets"], counts=d.get("tile_counts"))
+            else:
+                out.update(tiled=False, seg_w=out["width"],
+                           seg_h=min(one("rows_per_strip", 0xFFFFFFFF), out["length"]),
+                           offsets=d.get("strip_offsets"), counts=d.get("strip_counts"))
+            if out["seg_w"] < 1 or out["seg_h"] < 1:
+                raise PbxError(400, "%s: segments of %d x %d" % (path, out["seg_w"], out["seg_h"]))
+            if out["offsets"] is None or out["counts"] is None or len(out["offsets"]) != len(out["counts"]):
+                raise PbxError(400, "%s: an IFD lacks segment offsets or byte counts" % path)
+            for o, c in zip(out["offsets"], out["counts"]):
+                if o + c > size:
+                    raise PbxError(400, "%s: a segment at offset %d (%d bytes) lies past the end of the file "
+                                   "(%d bytes)" % (path, o, c, size))
+            out["subifds"] = []
+            for so in d.get("subifd_offsets", []):
+                sd, _ = ifd_at(so)
+                out["subifds"].append(finish(sd))
+            return out
+
+        ifds, off = [], first
+        if off == 0:
+            raise PbxError(400, "%s: no IFD" % path)
+        while off:
+            d, off = ifd_at(off)
+            ifds.append(finish(d))
+        return ifds
+
+
+def _tiff_pixel_type(path: str, ifd: dict) -> int:
+    """The pixel type of an IFD this library can load, else PbxError 400 with the reason."""
+    if ifd["spp"] != 1:
+        raise PbxError(400, "%s: SamplesPerPixel %d (only 1 is supported)" % (path, ifd["spp"]))
+    if ifd["bits"] not in (8, 16, 32, 64):
+        raise PbxError(400, "%s: BitsPerSample %d (8, 16, 32 or 64)" % (path, ifd["bits"]))
+    pt = _TIFF_PIXEL_TYPES.get((ifd["sampleformat"], ifd["bits"]))
+    if pt is None:
+        raise PbxError(400, "%s: SampleFormat %d with %d bits is none of the pixel types"
+                       % (path, ifd["sampleformat"], ifd["bits"]))
+    if ifd["compression"] not in (1, 5, 8, 32946):
+        raise PbxError(400, "%s: Compression %d (1 none, 5 LZW, 8 / 32946 deflate)" % (path, ifd["compression"]))
+    if ifd["predictor"] not in (1, 2):
+        raise PbxError(400, "%s: Predictor %d (1 or 2; the floating-point predictor 3 is not supported)"
+                       % (path, ifd["predictor"]))
+    if ifd["predictor"] == 2 and pt in (FLOAT, DOUBLE):
+        raise PbxError(400, "%s: Predictor 2 on floating-point samples" % path)
+    if ifd["fillorder"] != 1:
+        raise PbxError(400, "%s: FillOrder %d (only 1 is supported)" % (path, ifd["fillorder"]))
+    if ifd["orientation"] != 1:
+        raise PbxError(400, "%s: Orientation %d (only 1, top left, is supported)" % (path, ifd["orientation"]))
+    return pt
+
+
+def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int, level: int = 0) -> dict:
+    """register_tiff_planes() arguments for the plane one IFD (a tiff_ifds() dict, main or
+    SubIFD) holds: its segments are read from the file as they are, nothing is decoded here.
+    PbxError 400 names what is not supported."""
+    import numpy as np
+    pt = _tiff_pixel_type(path, ifd)
+    gx = -(-ifd["width"] // ifd["seg_w"]) if ifd["tiled"] else 1
+    gy = -(-ifd["length"] // ifd["seg_h"])
+    if len(ifd["offsets"]) != gx * gy:
+        raise PbxError(400, "%s: %d segments for a grid of %d x %d" % (path, len(ifd["offsets"]), gx, gy))
+    offsets = np.zeros(gx * gy + 1, dtype=np.uint64)
+    np.cumsum(np.array(ifd["counts"], dtype=np.uint64), out=offsets[1:])
+    data = np.empty(max(int(offsets[-1]), 1), dtype=np.uint8)
+    with open(path, "rb") as f:
+        for k, (o, n) in enumerate(zip(ifd["offsets"], ifd["counts"])):
+            f.seek(o)
+            if f.readinto(memoryview(data)[int(offsets[k]):int(offsets[k]) + n]) != n:
+                raise PbxError(400, "%s: segment %d is truncated" % (path, k))
+    return dict(image_id=image_id, z=z, c=c, t=t, level=level, pixel_type=pt, size_x=ifd["width"],
+                size_y=ifd["length"], big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"],
+                seg_h=ifd["seg_h"], tiled=ifd["tiled"],
+                compression=TIFF_DEFLATE if ifd["compression"] == 32946 else ifd["compression"],
+                predictor=ifd["predictor"], segments=(data, offsets))
+
+
+def _ome_layout(path: str, xml: str) -> Optional[dict]:
+    """SizeZ/C/T, DimensionOrder and Type of the first Image of an OME-XML ImageDescription (None
+    if the description is not OME-XML).  400 for what register_tiff_image cannot follow."""
+    if "<OME" not in xml[:4096]:
+        return None
+    import xml.etree.ElementTree as ET
+    try:
+        root = ET.fromstring(xml)
+    except ET.ParseError as e:
+        raise PbxError(400, "%s: OME-XML does not parse: %s" % (path, e))
+
+    def local(el):
+        return el.tag.rsplit("}", 1)[-1]
+    images = [el for el in root if local(el) == "Image"]
+    if len(images) != 1:
+        raise PbxError(400, "%s: OME-XML with %d Image elements (only one is supported)" % (path, len(images)))
+    px = [el for el in images[0] if local(el) == "Pixels"]
+    if len(px) != 1:
+        raise PbxError(400, "%s: OME-XML Image without Pixels" % path)
+    a = px[0].attrib
+    try:
+        sz, sc, st = int(a["SizeZ"]), int(a["SizeC"]), int(a["SizeT"])
+        order, typ = a["DimensionOrder"], a["Type"]
+        sxy = (int(a["SizeX"]), int(a["SizeY"]))
+    except (KeyError, ValueError) as e:
+        raise PbxError(400, "%s: OME-XML Pixels attribute %s" % (path, e))
+    if len(order) != 5 or order[:2] != "XY" or sorted(order[2:]) != ["C", "T", "Z"]:
+        raise PbxError(400, "%s: OME-XML DimensionOrder %r" % (path, order))
+    if typ not in PIXEL_TYPES:
+        raise PbxError(400, "%s: OME-XML pixel Type %r" % (path, typ))
+    if min(sz, sc, st) < 1:
+        raise PbxError(400, "%s: OME-XML SizeZ/C/T %d/%d/%d" % (path, sz, sc, st))
+    ext = {"Z": sz, "C": sc, "T": st}
+    planes = []
+    for k in range(sz * sc * st):
+        idx, r = {}, k
+        for ax in order[2:]:
+            idx[ax] = r % ext[ax]
+            r //= ext[ax]
+        planes.append((idx["Z"], idx["C"], idx["T"]))
+    at = {p: k for k, p in enumerate(planes)}
+    for td in (el for el in px[0] if local(el) == "TiffData"):
+        for u in (el for el in td if local(el) == "UUID"):
+            fn = u.attrib.get("FileName")
+            if fn is not None and os.path.basename(fn) != os.path.basename(path):
+                raise PbxError(400, "%s: OME-XML TiffData names another file, %r (multi-file OME-TIFF is not "
+                               "supported)" % (path, fn))
+        ta = td.attrib
+        try:
+            first = (int(ta.get("FirstZ", 0)), int(ta.get("FirstC", 0)), int(ta.get("FirstT", 0)))
+            ifd0 = int(ta.get("IFD", 0))
+        except ValueError as e:
+            raise PbxError(400, "%s: OME-XML TiffData attribute %s" % (path, e))
+        if at.get(first) != ifd0:  # only the DimensionOrder's own layout: IFD k is plane k
+            raise PbxError(400, "%s: OME-XML TiffData puts plane z=%d c=%d t=%d in IFD %d, not in "
+                           "DimensionOrder %s" % ((path,) + first + (ifd0, order)))
+    return dict(size_z=sz, size_c=sc, size_t=st, planes=planes, pixel_type=PIXEL_TYPES.index(typ), size_xy=sxy)
+
+
+def tiff_image_layout(path: str) -> dict:
+    """What register_tiff_image and TiffSource make of a file: ifds (tiff_ifds), planes = the
+    (z, c, t) of main IFD k, size_z / size_c / size_t, pixel_type, levels (1 + SubIFDs per main
+    IFD).  OME-TIFF: the first Image's SizeZ/C/T and DimensionOrder, IFD k = plane k in that
+    order.  Any other multi-page TIFF: page k is t = k (Bio-Formats' BaseTiffReader puts the
+    pages of a plain TIFF on the time axis)."""
+    ifds = tiff_ifds(path)
+    pt = _tiff_pixel_type(path, ifds[0])
+    ome = _ome_layout(path, ifds[0]["description"]) if ifds[0]["description"] else None
+    if ome is not None:
+        n = len(ome["planes"])
+        if len(ifds) < n:
+            raise PbxError(400, "%s: OME-XML names %d planes, the file has %d IFDs" % (path, n, len(ifds)))
+        if ome["pixel_type"] != pt or ome["size_xy"] != (ifds[0]["width"], ifds[0]["length"]):
+            raise PbxError(400, "%s: OME-XML Pixels disagree with the first IFD on type or size" % path)
+        out = dict(ome, ifds=ifds[:n])
+    else:
+        out = dict(size_z=1, size_c=1, size_t=len(ifds), planes=[(0, 0, k) for k in range(len(ifds))],
+                   pixel_type=pt, ifds=ifds)
+    first = out["ifds"][0]
+    for k, d in enumerate(out["ifds"]):
+        if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d) != pt:
+            raise PbxError(400, "%s: IFD %d differs from the first in size or pixel type" % (path, k))
+        if len(d["subifds"]) != len(first["subifds"]):
+            raise PbxError(400, "%s: IFD %d has %d SubIFDs, the first has %d" % (path, k, len(d["subifds"]),
+                                                                                len(first["subifds"])))
+    out["levels"] = 1 + len(first["subifds"])
+    return out
+
+
 def ngff_multiscales(image_dir: str):
     """(multiscales[0], image directory) of an NGFF image: .zattrs (NGFF 0.1-0.4), or without
     one the "ome" attributes of a Zarr v3 group's zarr.json (NGFF 0.5).  A bioformats2raw
@@ -1040,6 +1326,54 @@ class PixelsService:
             out.setdefault(k, {})[p] = pid
         return out
 
+    def register_tiff_planes(self, planes: Sequence[dict], timing: bool = False):
+        """Planes from TIFF strips or tiles, decoded by one set of GPU launches
+        (pbx_planes_register_tiff): each dict (tiff_plane_spec) holds image_id, z, c, t,
+        pixel_type, size_x, size_y, seg_w, seg_h, tiled, compression (1 none, 5 LZW, 8 deflate),
+        predictor (1 or 2), segments (a sequence of bytes in C order over the grid, or
+        pack_chunks()' (data, offsets) pair) [, big_endian = the FILE's byte order, level].  All are
+        registered or none.  Returns the plane ids (and the kernels' device ms with timing=True)."""
+        n = len(planes)
+        descs = (PbxPlaneDesc * n)()
+        sgs = (PbxTiffSegments * n)()
+        keep = []
+        for k, p in enumerate(planes):
+            seg = p["segments"]
+            data, offsets = seg if isinstance(seg, tuple) else pack_chunks(seg)
+            keep += [offsets, data]
+            d = descs[k]
+            d.image_id, d.z, d.c, d.t = p["image_id"], p["z"], p["c"], p["t"]
+            d.resolution = p.get("level", 0)
+            d.pixel_type, d.size_x, d.size_y = p["pixel_type"], p["size_x"], p["size_y"]
+            d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
+            s = sgs[k]
+            s.seg_w, s.seg_h, s.tiled = p["seg_w"], p["seg_h"], 1 if p["tiled"] else 0
+            s.compression, s.predictor, s.flags = p["compression"], p.get("predictor", 1), p.get("flags", 0)
+            s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
+        ids = (ctypes.c_uint64 * n)()
+        ms = (ctypes.c_double * 2)()
+        _check(lib().pbx_planes_register_tiff(self._h, n, descs, sgs, ids, ms))
+        del keep
+        return (list(ids), (ms[0], ms[1])) if timing else list(ids)
+
+    def register_tiff_image(self, path: str, image_id: int) -> Dict[int, Dict[Tuple[int, int, int], int]]:
+        """A whole TIFF / OME-TIFF file -- what the ordinary PixelsService opens through
+        Bio-Formats for an image without an NGFF fileset (config.yaml:18) -- in ONE set of GPU
+        launches: every plane of every level (tiff_image_layout: OME-XML axes, or page k = t;
+        each main IFD's SubIFDs are stored levels 1, 2, ... of its plane).  All are registered,
+        or none.  Returns {level: {(z, c, t): plane id}}, as register_ngff_image."""
+        lay = tiff_image_layout(path)
+        specs, keys = [], []
+        for (z, c, t), ifd in zip(lay["planes"], lay["ifds"]):
+            for k, d in enumerate([ifd] + ifd["subifds"]):
+                specs.append(tiff_plane_spec(path, d, image_id, z, c, t, k))
+                keys.append((k, (z, c, t)))
+        ids = self.register_tiff_planes(specs)
+        out: Dict[int, Dict[Tuple[int, int, int], int]] = {}
+        for (k, p), pid in zip(keys, ids):
+            out.setdefault(k, {})[p] = pid
+        return out
+
     def release_plane(self, plane_id: int) -> None:
         _check(lib().pbx_plane_release(self._h, plane_id))
 
@@ -1226,6 +1560,16 @@ class PixelsService:
             found = self.lookup_plane(*key)
             if found is not None and found[1] == PS_READY:
                 return found[0]
+            segments = getattr(source, "plane_segments", None)
+            sp = segments(pixels, z, c, t, level) if segments is not None and band is None else None
+            if sp is not None:  # a TIFF plane: its strips or tiles, decoded on the GPU
+                try:
+                    return self.register_tiff_planes([sp])[0]
+                except PbxError as e:
+                    if e.status != E_EXISTS:
+                        raise
+                    found = self.lookup_plane(*key)  # another context user registered it
+                    return found[0] if found is not None else 0
             sx, sy = source.level_size(pixels, level)
             y0, rows = band if band is not None else (0, sy)
             try:
@@ -1649,6 +1993,12 @@ class PixelSource:
         geometry only and must read no chunk.  None (the default): no chunk-level access."""
         return None
 
+    def plane_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Optional[dict]:
+        """Optional, for storage that is TIFF: the whole plane at that level as tiff_plane_spec
+        returns it; load_plane then registers it from its strips or tiles, decoded on the GPU
+        (register_tiff_planes), instead of calling read_rows.  None (the default): rows only."""
+        return None
+
 
 class NgffSource(PixelSource):
     """NGFF multiscale images on disk, {image_id: image directory} -- what ZarrPixelsService
@@ -1696,6 +2046,52 @@ class NgffSource(PixelSource):
                   rows: int) -> bytes:
         raise PbxError(E_BADARG, "NgffSource hands over Zarr chunks, not rows: serve it from a "
                        "PixelsService with sparse_band_rows (whole planes: register_ngff_image)")
+
+
+class TiffSource(PixelSource):
+    """TIFF / OME-TIFF files on disk, {image_id: path} -- the original files the ordinary OMERO
+    PixelsService opens through Bio-Formats when an image has no NGFF fileset (config.yaml:18).
+    A plane the context does not hold is registered whole from its IFD's strips or tiles, decoded
+    on the GPU (plane_segments -> PixelsService.load_plane -> register_tiff_planes); loading by
+    bands is not implemented, so it needs a service without sparse_band_rows."""
+
+    def __init__(self, images: Mapping[int, str]):
+        import threading
+        self.images = dict(images)
+        self._opened: Dict[int, dict] = {}
+        self._lock = threading.Lock()
+
+    def _open(self, image_id: int) -> dict:
+        with self._lock:
+            lay = self._opened.get(image_id)
+            if lay is None:
+                lay = self._opened[image_id] = tiff_image_layout(self.images[image_id])
+            return lay
+
+    def get_pixels(self, image_id: int) -> Optional[Pixels]:
+        if image_id not in self.images:
+            return None
+        lay = self._open(image_id)
+        return Pixels(image_id, lay["pixel_type"], lay["ifds"][0]["width"], lay["ifds"][0]["length"],
+                      lay["size_z"], lay["size_c"], lay["size_t"], levels=lay["levels"])
+
+    def _ifd(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> dict:
+        lay = self._open(pixels.image_id)
+        ifd = lay["ifds"][lay["planes"].index((z, c, t))]
+        return ifd if level == 0 else ifd["subifds"][level - 1]
+
+    def level_size(self, pixels: Pixels, level: int) -> Tuple[int, int]:
+        d = self._ifd(pixels, 0, 0, 0, level)
+        return d["width"], d["length"]
+
+    def plane_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Optional[dict]:
+        return tiff_plane_spec(self.images[pixels.image_id], self._ifd(pixels, z, c, t, level),
+                               pixels.image_id, z, c, t, level)
+
+    def read_rows(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
+                  rows: int) -> bytes:
+        raise PbxError(E_BADARG, "TiffSource hands over TIFF segments, not rows: serve it from a "
+                       "PixelsService without sparse_band_rows and without a band")
 
 
 # ----------------------------------------------------------------- TileRequestHandler
