@@ -366,6 +366,7 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  *            Adler-32 checked;
  * then Predictor = 2 (horizontal differencing over whole samples in the file's byte order) is
  * undone per segment row (k_tiff_unpred) and k_zarr_place puts the segments into the plane.
+ * pbx_band_write_tiff loads a sparse plane band by band from the segment rows a band covers.
  * Not supported (400 by the caller or here): SamplesPerPixel != 1, Predictor 3, FillOrder 2,
  * pre-6.0 (LSB-first) LZW streams, JPEG / PackBits / other compressions.
  * The JNI shim does not wrap these calls (as the deep Zarr calls). */
@@ -395,6 +396,30 @@ typedef struct pbx_tiff_segments {
  * libtiff accepts it.  kernel_ms (may be NULL): [0] decoders + un-predictor, [1] placement. */
 int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
                              const pbx_tiff_segments* segs, uint64_t* plane_ids, double* kernel_ms);
+/* Rows [y0, y0 + rows) of ONE band of a sparse plane, decoded on the GPU from the TIFF strips or
+ * tile rows that cover them: pbx_band_write_zarr for a plane stored as TIFF, so a cold tile of a
+ * whole slide costs the segments of its bands and not the plane's (the Bio-Formats buffers decode
+ * only the strips or tiles a region touches, TileRequestHandler.java:102-109).  `segs` is as for
+ * pbx_planes_register_tiff except that data / offsets hold only segment rows sr0 = y0 / seg_h up
+ * to (not including) sr1 = ceil((y0 + rows) / seg_h), each full width (gx segments; gx = 1 for
+ * strips) in C order: (sr1 - sr0) * gx + 1 offsets.  A strip's row count follows the plane: the
+ * last strip holds size_y - its first row.  Rows of those segments outside [y0, y0 + rows) are
+ * decoded (LZW and deflate are serial) but neither un-predicted nor written, so band_rows need
+ * not be a multiple of seg_h, a band may be written in pieces at any rows, and a segment row that
+ * straddles two bands is decoded once for each.  The bytes land in the plane's stored byte order:
+ * create the sparse plane with source PBX_SRC_HOST and the FILE's byte order; predictor sums use
+ * that order, as at registration.  Stored segments are read where they were uploaded (no copy, no
+ * scratch); with Predictor = 2 one kernel (k_tiff_unpred_place) undoes the differencing on the way
+ * from the decoded segment into the band.  Band states, statuses (400 rows outside one band or a
+ * plane that is not sparse, 409 resident band, 507 no room) and failure handling are
+ * pbx_band_write's, and pieces written by any of the three band calls may be mixed in one band.
+ * Every host-side refusal of pbx_planes_register_tiff applies to the covered segments (segment
+ * numbers count from the first one handed over): 400, and the band is left as it was.  A stream
+ * the device rejects is 400 and fails the band's load like a failed upload.  Upload, decode and
+ * placement run on the upload stream.  kernel_ms (may be NULL): [0] device ms of the decoders
+ * (about 0 for stored segments, which launch none), [1] of the placement. */
+int pbx_band_write_tiff(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                        const pbx_tiff_segments* segs, double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -618,8 +643,8 @@ int pbx_test_fail_batch(pbx_ctx* ctx, uint64_t ahead);
  * queue behind it on the device, as behind a wedged one.  Callers of pbx_get_tile get 500 at
  * their deadline (pbx_config.request_timeout_us).  0 releases the stall and disarms. */
 int pbx_test_stall_batch(pbx_ctx* ctx, uint64_t ahead);
-/* Upload failure injection (test hook): the `ahead`-th pbx_band_write or
- * pbx_band_write_zarr from now on fails after joining its band's load, as a failed
+/* Upload failure injection (test hook): the `ahead`-th pbx_band_write, pbx_band_write_zarr or
+ * pbx_band_write_tiff from now on fails after joining its band's load, as a failed
  * host-to-device copy would.  0 disables. */
 int pbx_test_fail_band_write(pbx_ctx* ctx, uint64_t ahead);
 
@@ -658,6 +683,15 @@ int pbx_test_zarr_plan(const pbx_zarr_chunks* chunks, int32_t size_x, int32_t si
  * scratch bytes, 1 if the un-predictor launch is needed.  400 as the real call. */
 int pbx_test_tiff_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
                        uint64_t out[4]);
+
+/* Test hook: the host planner of pbx_band_write_tiff alone (no context, no device call) for rows
+ * [y0, y0 + rows) of a plane of size_x x size_y samples of bpp bytes; segs holds the covering
+ * segment rows only.  out: streams handed to a decoder (LZW and deflate; stored segments count
+ * 0), the sum of the decoded lengths of every covered segment, scratch bytes, 1 if the fused
+ * un-predict-and-place kernel is launched.  400 as the real call, and for rows < 1 or rows
+ * outside the plane. */
+int pbx_test_tiff_band_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
+                            int32_t y0, int32_t rows, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

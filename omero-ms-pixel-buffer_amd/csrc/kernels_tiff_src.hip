@@ -6,9 +6,13 @@
 //                   EOI = 257, first free code 258, "early change" code widths)
 //   k_tiff_unpred   one wave per segment row: the inverse of Predictor = 2 (a prefix sum over
 //                   the row's samples in the file's byte order, modulo 2^bits)
+//   k_tiff_unpred_place   the same sums taken on the way from the decoded segment into a band of
+//                   a sparse plane (pbx_band_write_tiff): read once, stored once
 //
 // Deflate segments go through k_zarr_inflate2 and stored ones through k_zarr_copy; every kind
-// is placed by k_zarr_place (kernels_zarr.hip).
+// is placed by k_zarr_place (kernels_zarr.hip).  A band write reads stored segments where they
+// were uploaded, and with Predictor = 2 k_tiff_unpred_place stands in for k_tiff_unpred +
+// k_zarr_place.
 //
 // LZW as LZ77 sequences.  Between two Clear codes the position of every code in the stream is
 // known without decoding: code j (j = 0 right after the Clear) is 9 + [j >= 254] + [j >= 766] +
@@ -149,55 +153,69 @@ __global__ __launch_bounds__(64 * LZW_WAVES) void k_tiff_lzw(const ZStream* __re
 // big-endian file) and wrap modulo 2^bits.
 constexpr uint32_t UP_WAVES = 4, UP_ROWS = 16;  // rows per workgroup
 
+// One step of a row: the lane's 16 bytes wv (bytes past the row's end zero) become their running
+// sums ov, continued from `carry` (the sum of the steps before, updated for the next one).
 template <uint32_t BPP>
-__device__ __forceinline__ void unpred_row(uint8_t* row, uint32_t rb, bool be, uint32_t lane) {
+__device__ __forceinline__ void unpred_group(const uint32_t (&wv)[4], bool be, uint32_t lane, uint32_t& carry,
+                                             uint32_t (&ov)[4]) {
     constexpr uint32_t NS = 16 / BPP;
     constexpr uint32_t MASK = BPP == 4 ? 0xffffffffu : (1u << (8 * (BPP & 3))) - 1;
+    uint32_t s[NS];
+    uint32_t run = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < NS; i++) {
+        uint32_t v;
+        if (BPP == 4) {
+            v = wv[i];
+            v = be ? __builtin_bswap32(v) : v;
+        } else if (BPP == 2) {
+            v = (wv[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+            v = be ? ((v >> 8) | (v << 8)) & 0xffffu : v;
+        } else {
+            v = (wv[i >> 2] >> (8 * (i & 3))) & 0xffu;
+        }
+        run += v;
+        s[i] = run;
+    }
+    const uint32_t inc = wave_incl_add(run, lane);
+    const uint32_t base = carry + inc - run;
+    carry += rdl(inc, 63);
+    ov[0] = ov[1] = ov[2] = ov[3] = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < NS; i++) {
+        uint32_t v = (s[i] + base) & MASK;
+        if (BPP == 4) {
+            ov[i] = be ? __builtin_bswap32(v) : v;
+        } else if (BPP == 2) {
+            v = be ? ((v >> 8) | (v << 8)) & 0xffffu : v;
+            ov[i >> 1] |= v << (16 * (i & 1));
+        } else {
+            ov[i >> 2] |= v << (8 * (i & 3));
+        }
+    }
+}
+
+// the lane's `have` (0 .. 16) bytes at p, the rest zero
+__device__ __forceinline__ void unpred_load(const uint8_t* p, uint32_t have, uint32_t (&wv)[4]) {
+    wv[0] = wv[1] = wv[2] = wv[3] = 0;
+    if (have == 16) {
+        __builtin_memcpy(wv, p, 16);
+    } else {
+#pragma unroll
+        for (uint32_t b = 0; b < 16; b++)
+            if (b < have) wv[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
+    }
+}
+
+template <uint32_t BPP>
+__device__ __forceinline__ void unpred_row(uint8_t* row, uint32_t rb, bool be, uint32_t lane) {
     uint32_t carry = 0;
     for (uint32_t k0 = 0; k0 < rb; k0 += 1024) {
         const uint32_t off = k0 + 16 * lane;
         const uint32_t have = off >= rb ? 0u : rb - off < 16 ? rb - off : 16u;  // a multiple of BPP
-        uint32_t wv[4] = {0, 0, 0, 0};
-        if (have == 16) {
-            __builtin_memcpy(wv, row + off, 16);
-        } else {
-#pragma unroll
-            for (uint32_t b = 0; b < 16; b++)
-                if (b < have) wv[b >> 2] |= (uint32_t)row[off + b] << (8 * (b & 3));
-        }
-        uint32_t s[NS];
-        uint32_t run = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < NS; i++) {
-            uint32_t v;
-            if (BPP == 4) {
-                v = wv[i];
-                v = be ? __builtin_bswap32(v) : v;
-            } else if (BPP == 2) {
-                v = (wv[i >> 1] >> (16 * (i & 1))) & 0xffffu;
-                v = be ? ((v >> 8) | (v << 8)) & 0xffffu : v;
-            } else {
-                v = (wv[i >> 2] >> (8 * (i & 3))) & 0xffu;
-            }
-            run += v;
-            s[i] = run;
-        }
-        const uint32_t inc = wave_incl_add(run, lane);
-        const uint32_t base = carry + inc - run;
-        carry += rdl(inc, 63);
-        uint32_t ov[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (uint32_t i = 0; i < NS; i++) {
-            uint32_t v = (s[i] + base) & MASK;
-            if (BPP == 4) {
-                ov[i] = be ? __builtin_bswap32(v) : v;
-            } else if (BPP == 2) {
-                v = be ? ((v >> 8) | (v << 8)) & 0xffffu : v;
-                ov[i >> 1] |= v << (16 * (i & 1));
-            } else {
-                ov[i >> 2] |= v << (8 * (i & 3));
-            }
-        }
+        uint32_t wv[4], ov[4];
+        unpred_load(row + off, have, wv);
+        unpred_group<BPP>(wv, be, lane, carry, ov);
         if (have == 16) {
             __builtin_memcpy(row + off, ov, 16);
         } else {
@@ -223,6 +241,70 @@ __global__ __launch_bounds__(64 * UP_WAVES) void k_tiff_unpred(const TUnpred* __
     }
 }
 
+// ------------------------------------------------------------- un-predict and place (bands)
+// pbx_band_write_tiff with Predictor = 2: k_tiff_unpred's geometry (a workgroup per segment and
+// run of UP_ROWS segment rows, a wave per row at a time), but a row is read once at the
+// segment's own pitch -- from scratch, or from the upload buffer for a stored segment -- summed
+// in registers and stored straight into the plane.  The row loop is clipped, the same for the
+// whole workgroup, to the run, the destination's window [y_lo, y_hi) and the plane: rows a band
+// write decodes but does not keep are neither read nor summed.  Only the segment's visible width
+// min(seg_w, size_x - x0) is walked: an edge tile's padding is never stored, and the sums stop
+// where the plane does.  The plane's base and pitch are 256-byte aligned and a tile's x0 * bpp is
+// a multiple of 16 (TileWidth is one), so every whole group is one aligned 16-byte store; the
+// row's last, partial group goes byte by byte.
+template <uint32_t BPP>
+__device__ __forceinline__ void unpred_place_row(const uint8_t* __restrict__ row, uint8_t* __restrict__ out,
+                                                 uint32_t vis, bool be, uint32_t lane) {
+    uint32_t carry = 0;
+    for (uint32_t k0 = 0; k0 < vis; k0 += 1024) {
+        const uint32_t off = k0 + 16 * lane;
+        const uint32_t have = off >= vis ? 0u : vis - off < 16 ? vis - off : 16u;  // a multiple of BPP
+        uint32_t wv[4], ov[4];
+        unpred_load(row + off, have, wv);
+        unpred_group<BPP>(wv, be, lane, carry, ov);
+        if (have == 16) {
+            *(uint4*)(out + off) = make_uint4(ov[0], ov[1], ov[2], ov[3]);
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 16; b++)
+                if (b < have) out[off + b] = (uint8_t)(ov[b >> 2] >> (8 * (b & 3)));
+        }
+    }
+}
+
+template <uint32_t BPP>
+__device__ __forceinline__ void unpred_place_rows(const uint8_t* __restrict__ s, uint32_t rb, uint8_t* __restrict__ o,
+                                                  int64_t pitch, int32_t r0, int32_t r1, uint32_t vis, bool be,
+                                                  uint32_t lane, uint32_t w) {
+    for (int32_t r = r0 + (int32_t)w; r < r1; r += (int32_t)UP_WAVES)
+        unpred_place_row<BPP>(s + (uint64_t)r * rb, o + (int64_t)r * pitch, vis, be, lane);
+}
+
+__global__ __launch_bounds__(64 * UP_WAVES) void k_tiff_unpred_place(const TPlace* __restrict__ sg, TPlaceDst d,
+                                                                     const uint8_t* __restrict__ scratch,
+                                                                     const uint8_t* __restrict__ input) {
+    const uint32_t lane = threadIdx.x & 63, w = rfl(threadIdx.x >> 6);
+    const TPlace u = sg[blockIdx.x];
+    const int32_t x0 = (int32_t)rfl((uint32_t)u.x0), y0 = (int32_t)rfl((uint32_t)u.y0);
+    const int32_t rows = (int32_t)rfl(u.rows);
+    const uint32_t rb = rfl(u.row_bytes);
+    // segment rows of this run that lie in the window and in the plane
+    int32_t r0 = (int32_t)(blockIdx.y * UP_ROWS), r1 = r0 + (int32_t)UP_ROWS;
+    const int32_t top = d.y_lo > 0 ? d.y_lo : 0, bottom = d.y_hi < d.sy ? d.y_hi : d.sy;
+    r1 = r1 < rows ? r1 : rows;
+    r0 = r0 > top - y0 ? r0 : top - y0;
+    r1 = r1 < bottom - y0 ? r1 : bottom - y0;
+    if (r0 >= r1 || x0 >= d.sx) return;
+    const uint32_t wvis = (uint32_t)(d.sx - x0) * d.bpp;
+    const uint32_t vis = wvis < rb ? wvis : rb;
+    const uint8_t* s = (rfl(u.from_input) ? input : scratch) + u.src;
+    uint8_t* o = d.dev + (int64_t)y0 * d.pitch + (int64_t)x0 * d.bpp;
+    const bool be = d.big_endian != 0;
+    if (d.bpp == 1) unpred_place_rows<1>(s, rb, o, d.pitch, r0, r1, vis, false, lane, w);
+    else if (d.bpp == 2) unpred_place_rows<2>(s, rb, o, d.pitch, r0, r1, vis, be, lane, w);
+    else unpred_place_rows<4>(s, rb, o, d.pitch, r0, r1, vis, be, lane, w);
+}
+
 hipError_t launch_tiff_lzw(hipStream_t st, const ZStream* d_streams, uint32_t n, const uint8_t* src,
                            uint8_t* scratch, uint32_t* err) {
     if (!n) return hipSuccess;
@@ -236,6 +318,14 @@ hipError_t launch_tiff_unpred(hipStream_t st, const TUnpred* d_segs, uint32_t n,
     if (!n || !max_rows) return hipSuccess;
     hipLaunchKernelGGL(k_tiff_unpred, dim3(n, (max_rows + UP_ROWS - 1) / UP_ROWS), dim3(64 * UP_WAVES), 0, st,
                        d_segs, scratch);
+    return hipGetLastError();
+}
+
+hipError_t launch_tiff_unpred_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
+                                    const TPlaceDst& dst, const uint8_t* scratch, const uint8_t* input) {
+    if (!n || !max_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tiff_unpred_place, dim3(n, (max_rows + UP_ROWS - 1) / UP_ROWS), dim3(64 * UP_WAVES), 0, st,
+                       d_segs, dst, scratch, input);
     return hipGetLastError();
 }
 

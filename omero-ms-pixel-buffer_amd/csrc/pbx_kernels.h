@@ -184,5 +184,27 @@ hipError_t launch_tiff_lzw(hipStream_t st, const ZStream* d_streams, uint32_t n,
                            uint8_t* scratch, uint32_t* err);
 hipError_t launch_tiff_unpred(hipStream_t st, const TUnpred* d_segs, uint32_t n, uint32_t max_rows,
                               uint8_t* scratch);
+// k_tiff_unpred_place (pbx_band_write_tiff, Predictor = 2): the inverse of the predictor and the
+// placement in one pass.  Rows [y_lo, y_hi) of the destination that a segment holds are read at
+// the segment's own pitch (from scratch, or from the upload buffer for a stored segment),
+// summed in registers and stored into the pitched plane; its other rows are not touched.
+struct TPlace {
+    uint64_t src;        // the segment's decoded bytes: scratch offset (input offset with from_input)
+    uint32_t row_bytes;  // seg_w * bpp, the segment's own pitch
+    uint32_t rows;       // rows it holds (a short last strip: the rows left)
+    int32_t x0, y0;      // its origin in the plane
+    uint32_t from_input, pad;
+};
+static_assert(sizeof(TPlace) == 32, "TPlace is uploaded as is");
+struct TPlaceDst {       // passed by value
+    uint8_t* dev;        // row 0 of the plane (a band: its virtual base), 256-byte aligned
+    int64_t pitch;       // a multiple of 256
+    int32_t sx, sy;      // plane size in samples
+    int32_t y_lo, y_hi;  // plane rows that may be written
+    uint32_t bpp;        // 1, 2 or 4
+    uint32_t big_endian;
+};
+hipError_t launch_tiff_unpred_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
+                                    const TPlaceDst& dst, const uint8_t* scratch, const uint8_t* input);
 
 }  // namespace pbx

@@ -2330,6 +2330,11 @@ struct ZarrPlan {
     uint64_t skipped = 0;  // blosc blocks left undecoded (deep chunks only)
     std::vector<TUnpred> unpred;  // TIFF segments whose rows are horizontally differenced
     uint32_t unpred_rows = 0;     // the tallest of them
+    // pbx_band_write_tiff with Predictor = 2: the segments k_tiff_unpred_place un-predicts and
+    // places into the launch's one destination (then no `unpred` and no `chunks`)
+    std::vector<TPlace> uplace;
+    uint32_t uplace_rows = 0;     // the tallest of them
+    bool uplace_big_endian = false;
 };
 
 // A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
@@ -2592,7 +2597,9 @@ struct ZarrInput {
 // bases and their row windows), then waits for it all.  The launch scratch (input, decoded
 // chunks, tables) comes from the context's device pool and goes back to it.  400 for a stream
 // a decoder rejects; rows already placed are then the caller's to discard.  P.unpred (TIFF
-// segments stored with Predictor = 2) is undone in scratch between the decoders and the placement.
+// segments stored with Predictor = 2) is undone in scratch between the decoders and the placement;
+// P.uplace (the same for a band write) is un-predicted and placed into zp[0] by one kernel after
+// the decoders, and k_zarr_place is launched only if P has chunks.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms) {
     uint32_t counts[ZS_NKINDS], nstreams = 0;
@@ -2620,13 +2627,14 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     ZChunk* d_ch = nullptr;
     ZPlane* d_pl = nullptr;
     TUnpred* d_up = nullptr;
+    TPlace* d_tp = nullptr;
     uint32_t* d_err = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto cleanup = [&] {
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2643,6 +2651,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     dget(d_ch, sizeof(ZChunk) * P.chunks.size());
     dget(d_pl, sizeof(ZPlane) * zp.size());
     if (!P.unpred.empty()) dget(d_up, sizeof(TUnpred) * P.unpred.size());
+    if (!P.uplace.empty()) dget(d_tp, sizeof(TPlace) * P.uplace.size());
     dget(d_err, sizeof(uint32_t) * (nerr + 1));
     for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
     if (e != hipSuccess) {
@@ -2663,11 +2672,13 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = hipMemcpyAsync(d_st, all.data(), sizeof(ZStream) * nstreams, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && nchecks)
         e = hipMemcpyAsync(d_ck, checks.data(), sizeof(ZCheck) * nchecks, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
+    if (e == hipSuccess && !P.chunks.empty())
         e = hipMemcpyAsync(d_ch, P.chunks.data(), sizeof(ZChunk) * P.chunks.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(d_pl, zp.data(), sizeof(ZPlane) * zp.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_up)
         e = hipMemcpyAsync(d_up, P.unpred.data(), sizeof(TUnpred) * P.unpred.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_tp)
+        e = hipMemcpyAsync(d_tp, P.uplace.data(), sizeof(TPlace) * P.uplace.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
     // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
@@ -2682,7 +2693,15 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess) e = crc(ZK_CRC32);
     if (e == hipSuccess && d_up) e = launch_tiff_unpred(st, d_up, (uint32_t)P.unpred.size(), P.unpred_rows, d_scr);
     if (e == hipSuccess) e = hipEventRecord(ev[1], st);
-    if (e == hipSuccess) e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
+    if (e == hipSuccess && !P.chunks.empty())
+        e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
+    if (e == hipSuccess && d_tp) {
+        const ZPlane& z = zp[0];
+        e = launch_tiff_unpred_place(st, d_tp, (uint32_t)P.uplace.size(), P.uplace_rows,
+                                     TPlaceDst{z.dev, z.pitch, z.sx, z.sy, z.y_lo, z.y_hi, z.bpp,
+                                               P.uplace_big_endian ? 1u : 0u},
+                                     d_scr, d_in);
+    }
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     std::vector<uint32_t> err(nerr + 1, 0);
@@ -2765,25 +2784,35 @@ int tiff_segments_check(const pbx_tiff_segments* s) {
 // Host plan of one plane's strips or tiles: one stream per segment (its own row count: the last
 // strip holds only the rows left), one ZChunk to place it, and for Predictor = 2 its rows for
 // k_tiff_unpred.  No byte of segment data is decoded here.
+// With `band` (pbx_band_write_tiff) s->data / s->offsets hold segment rows [sr0, sr1) only, and
+// nothing is copied or rewritten in scratch: a stored segment is read where it was uploaded
+// (ZC_INPUT, no stream, no scratch), and with Predictor = 2 every segment goes into P.uplace for
+// k_tiff_unpred_place instead of P.unpred and P.chunks.  Segment numbers in messages count from
+// the first segment handed over.
 int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pbx_tiff_segments* s,
-              uint64_t in_base, uint32_t plane, ZarrPlan& P, uint64_t* dlen_sum) {
+              uint64_t in_base, uint32_t plane, ZarrPlan& P, uint64_t* dlen_sum, bool band = false,
+              int64_t sr0 = 0, int64_t sr1 = -1) {
     if (!s->tiled && s->seg_w != size_x)
         return fail(PBX_E_BADARG, "strip width %d != plane width %d", s->seg_w, size_x);
     if (s->predictor == 2 && bpp == 8) return fail(PBX_E_BADARG, "predictor 2 on floating-point samples");
     const int64_t gx = s->tiled ? ((int64_t)size_x + s->seg_w - 1) / s->seg_w : 1;
-    const int64_t gy = ((int64_t)size_y + s->seg_h - 1) / s->seg_h, n = gx * gy;
+    const int64_t gy = ((int64_t)size_y + s->seg_h - 1) / s->seg_h;
+    if (sr1 < 0) sr1 = gy;
+    const int64_t n = gx * (sr1 - sr0);
     const uint64_t total = s->offsets[n];
     for (int64_t i = 0; i < n; i++) {
         const uint64_t o = s->offsets[i], len = s->offsets[i + 1] - o;
         if (s->offsets[i + 1] < o || s->offsets[i + 1] > total)
             return fail(PBX_E_BADARG, "segment %lld: bad offsets", (long long)i);
         if (len == 0) return fail(PBX_E_BADARG, "segment %lld is empty", (long long)i);
-        const int32_t x0 = (int32_t)((i % gx) * s->seg_w), y0 = (int32_t)((i / gx) * s->seg_h);
+        const int32_t x0 = (int32_t)((i % gx) * s->seg_w), y0 = (int32_t)((sr0 + i / gx) * s->seg_h);
         const int32_t rows = s->tiled ? s->seg_h : std::min(s->seg_h, size_y - y0);
         const uint64_t dlen = (uint64_t)s->seg_w * (uint64_t)rows * (uint64_t)bpp;
         if (dlen > 0x7fffffffull || len > 0x7fffffffull || rows > (65535 << 4))
             return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
-        const uint64_t ob = o + in_base, dst = P.scratch;
+        const uint64_t ob = o + in_base;
+        const bool in_place = band && s->compression == PBX_TIFF_NONE;  // read from the upload buffer
+        const uint64_t dst = in_place ? ob : P.scratch;
         uint32_t kind = ZS_COPY;
         if (s->compression == PBX_TIFF_NONE) {
             if (len != dlen)
@@ -2797,11 +2826,21 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
         } else {
             kind = ZS_ZLIB;
         }
-        P.kind[kind].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)dlen, kind, 0});
+        if (!in_place) P.kind[kind].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)dlen, kind, 0});
+        if (dlen_sum) *dlen_sum += dlen;
+        if (!in_place) P.scratch += (dlen + 255) & ~255ull;
+        if (band && s->predictor == 2) {
+            P.uplace.push_back(TPlace{dst, (uint32_t)s->seg_w * (uint32_t)bpp, (uint32_t)rows, x0, y0,
+                                      in_place ? 1u : 0u, 0});
+            P.uplace_rows = std::max(P.uplace_rows, (uint32_t)rows);
+            P.uplace_big_endian = big_endian;
+            continue;
+        }
         ZChunk c{};
         c.src = dst;
         c.nbytes = c.blocksize = (uint32_t)dlen;
         c.typesize = 1;
+        c.flags = in_place ? ZC_INPUT : 0u;
         c.x0 = x0;
         c.y0 = y0;
         c.plane = plane;
@@ -2811,10 +2850,34 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
                                        big_endian ? 1u : 0u});
             P.unpred_rows = std::max(P.unpred_rows, (uint32_t)rows);
         }
-        if (dlen_sum) *dlen_sum += dlen;
-        P.scratch += (dlen + 255) & ~255ull;
     }
     return PBX_OK;
+}
+
+// pbx_band_write_tiff: pbx_band_write_zarr for segment rows.  The piece's covering segment rows
+// are planned on the host first (a malformed piece never joins the band's load), then uploaded,
+// decoded and placed under the band state machine of band_load_rows.
+int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
+                    double* kernel_ms) {
+    int32_t k = 0;
+    if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
+    if (int rc = tiff_segments_check(s)) return rc;
+    if (s->predictor == 2 && (q->pixel_type == PBX_FLOAT || q->pixel_type == PBX_DOUBLE))
+        return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)q->id);
+    const int bpp = bpp_of(q->pixel_type);
+    const int64_t gx = s->tiled ? ((int64_t)q->size_x + s->seg_w - 1) / s->seg_w : 1;
+    const int64_t sr0 = y0 / s->seg_h, sr1 = ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h;
+    ZarrPlan P;
+    if (int rc = tiff_plan(q->size_x, q->size_y, bpp, !q->little_endian, s, 0, 0, P, nullptr, true, sr0, sr1))
+        return rc;
+    const uint64_t used = s->offsets[gx * (sr1 - sr0)], len = (used + 15) & ~15ull;
+    const std::vector<ZarrInput> in{ZarrInput{s->data, used, 0, len}};
+    return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
+        // rows keep their plane index: the destination is the band's virtual base
+        const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
+                                            q->size_y, s->seg_w, s->seg_h, (uint32_t)bpp, 0, 0, y0, y0 + rows}};
+        return zarr_decode_place(ctx, ctx->upload_stream, P, zp, in, len, std::min(s->seg_h, q->size_y), kernel_ms);
+    });
 }
 
 // pbx_planes_register_zarr (layer k = plane k, one plane per chunk) and its deep form: plane k
@@ -3053,6 +3116,40 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows
 int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
                         double* kernel_ms) {
     return pbx_band_write_zarr_deep(ctx, id, y0, rows, z, 1, 0, kernel_ms);
+}
+
+int pbx_band_write_tiff(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
+                        double* kernel_ms) {
+    if (!ctx || !s) return fail(PBX_E_BADARG, "null argument");
+    int rc;
+    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
+    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
+    rc = band_write_tiff(ctx, q, y0, rows, s, kernel_ms);
+    const std::string msg = g_err;
+    unpin_one(ctx, q);
+    g_err = msg;
+    return rc;
+}
+
+int pbx_test_tiff_band_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t bpp, int32_t y0,
+                            int32_t rows, uint64_t out[4]) {
+    if (!s || !out) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = tiff_segments_check(s)) return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    if (bpp != 1 && bpp != 2 && bpp != 4 && bpp != 8) return fail(PBX_E_BADARG, "bad sample size %d", bpp);
+    if (rows < 1 || y0 < 0 || (int64_t)y0 + rows > size_y)
+        return fail(PBX_E_BADARG, "rows %d+%d outside the plane (%d rows)", y0, rows, size_y);
+    ZarrPlan P;
+    uint64_t sum = 0;
+    if (int rc = tiff_plan(size_x, size_y, bpp, true, s, 0, 0, P, &sum, true, y0 / s->seg_h,
+                           ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h))
+        return rc;
+    out[0] = 0;
+    for (const auto& k : P.kind) out[0] += k.size();
+    out[1] = sum;
+    out[2] = P.scratch;
+    out[3] = P.uplace.empty() ? 0 : 1;
+    return PBX_OK;
 }
 
 int pbx_plane_release(pbx_ctx* ctx, uint64_t id) {

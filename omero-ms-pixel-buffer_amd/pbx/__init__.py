@@ -163,6 +163,7 @@ EXPORTS = [
     "pbx_set_tiff_predictor", "pbx_get_tiff_predictor", "pbx_batch_pred_tiles",
     "pbx_band_write_zarr", "pbx_planes_register_zarr_deep", "pbx_band_write_zarr_deep",
     "pbx_test_zarr_plan", "pbx_planes_register_tiff", "pbx_test_tiff_plan",
+    "pbx_band_write_tiff", "pbx_test_tiff_band_plan",
 ]
 
 _lib = None
@@ -258,6 +259,10 @@ def lib() -> ctypes.CDLL:
                                            ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(u64),
                                            ctypes.POINTER(ctypes.c_double)]
     L.pbx_test_tiff_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, ctypes.POINTER(u64)]
+    L.pbx_band_write_tiff.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxTiffSegments),
+                                      ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_tiff_band_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, i32,
+                                          ctypes.POINTER(u64)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -905,25 +910,51 @@ def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int,
     """register_tiff_planes() arguments for the plane one IFD (a tiff_ifds() dict, main or
     SubIFD) holds: its segments are read from the file as they are, nothing is decoded here.
     PbxError 400 names what is not supported."""
+    return dict(_tiff_segment_rows(path, ifd, 0, None), image_id=image_id, z=z, c=c, t=t, level=level)
+
+
+def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int]) -> dict:
+    """What tiff_plane_spec and tiff_band_spec share: the IFD's pixel type, geometry and byte
+    order, and segments = (data, offsets) of its segment rows [sr0, sr1) (sr1 None: to the last;
+    sr1 == sr0: none, segments is None and the file is not opened), each full width, read from
+    the file as they are."""
     import numpy as np
     pt = _tiff_pixel_type(path, ifd)
     gx = -(-ifd["width"] // ifd["seg_w"]) if ifd["tiled"] else 1
     gy = -(-ifd["length"] // ifd["seg_h"])
     if len(ifd["offsets"]) != gx * gy:
         raise PbxError(400, "%s: %d segments for a grid of %d x %d" % (path, len(ifd["offsets"]), gx, gy))
-    offsets = np.zeros(gx * gy + 1, dtype=np.uint64)
-    np.cumsum(np.array(ifd["counts"], dtype=np.uint64), out=offsets[1:])
-    data = np.empty(max(int(offsets[-1]), 1), dtype=np.uint8)
-    with open(path, "rb") as f:
-        for k, (o, n) in enumerate(zip(ifd["offsets"], ifd["counts"])):
-            f.seek(o)
-            if f.readinto(memoryview(data)[int(offsets[k]):int(offsets[k]) + n]) != n:
-                raise PbxError(400, "%s: segment %d is truncated" % (path, k))
-    return dict(image_id=image_id, z=z, c=c, t=t, level=level, pixel_type=pt, size_x=ifd["width"],
-                size_y=ifd["length"], big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"],
-                seg_h=ifd["seg_h"], tiled=ifd["tiled"],
+    k0, k1 = sr0 * gx, (gy if sr1 is None else sr1) * gx
+    segments = None
+    if k1 > k0:
+        offsets = np.zeros(k1 - k0 + 1, dtype=np.uint64)
+        np.cumsum(np.array(ifd["counts"][k0:k1], dtype=np.uint64), out=offsets[1:])
+        data = np.empty(max(int(offsets[-1]), 1), dtype=np.uint8)
+        with open(path, "rb") as f:
+            for k, (o, n) in enumerate(zip(ifd["offsets"][k0:k1], ifd["counts"][k0:k1])):
+                f.seek(o)
+                if f.readinto(memoryview(data)[int(offsets[k]):int(offsets[k]) + n]) != n:
+                    raise PbxError(400, "%s: segment %d is truncated" % (path, k0 + k))
+        segments = (data, offsets)
+    return dict(pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
+                big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"], seg_h=ifd["seg_h"],
+                tiled=ifd["tiled"],
                 compression=TIFF_DEFLATE if ifd["compression"] == 32946 else ifd["compression"],
-                predictor=ifd["predictor"], segments=(data, offsets))
+                predictor=ifd["predictor"], segments=segments)
+
+
+def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int) -> dict:
+    """band_write_tiff() arguments for rows [y0, y0 + rows) of the plane one IFD (a tiff_ifds()
+    dict, main or SubIFD) holds: pixel_type, size_x, size_y, big_endian (the file's byte order),
+    seg_w, seg_h, tiled, compression, predictor and segments = (data, offsets) of the segment
+    rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 only, each full width; exactly those byte
+    ranges of the file are read.  rows == 0 reads nothing (segments is None): the geometry and
+    byte order alone.  PbxError 400 as tiff_plane_spec, and for rows outside the plane."""
+    if rows < 0 or y0 < 0 or y0 + rows > ifd["length"]:
+        raise PbxError(400, "%s: rows %d+%d outside the image (%d rows)" % (path, y0, rows, ifd["length"]))
+    sr0 = y0 // ifd["seg_h"]
+    sr1 = -(-(y0 + rows) // ifd["seg_h"]) if rows else sr0
+    return dict(_tiff_segment_rows(path, ifd, sr0, sr1), y0=y0, rows=rows)
 
 
 def _ome_layout(path: str, xml: str) -> Optional[dict]:
@@ -1498,6 +1529,23 @@ class PixelsService:
                                                   chunk_planes, slice, ms))
         return (ms[0], ms[1]) if timing else None
 
+    def band_write_tiff(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
+                        compression: int, predictor: int, segments, timing: bool = False):
+        """pbx_band_write_tiff: rows [y0, y0 + rows) of one band, decoded on the GPU from the TIFF
+        segment rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 that cover them (strips, or
+        rows of tiles at full width, C order: a sequence of bytes, or pack_chunks()' (data,
+        offsets) pair, as tiff_band_spec returns).  compression and predictor as
+        register_tiff_planes; the sparse plane must have been created in the file's byte order.
+        With timing=True returns the decoders' and the placement's device ms."""
+        data, offsets = segments if isinstance(segments, tuple) else pack_chunks(segments)
+        s = PbxTiffSegments()
+        s.seg_w, s.seg_h, s.tiled = seg_w, seg_h, 1 if tiled else 0
+        s.compression, s.predictor, s.flags = compression, predictor, 0
+        s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
+        ms = (ctypes.c_double * 2)()
+        _check(lib().pbx_band_write_tiff(self._h, plane_id, y0, rows, ctypes.byref(s), ms))
+        return [ms[0], ms[1]] if timing else None
+
     def band_abort(self, plane_id: int, y0: int) -> None:
         """pbx_band_abort: give back the band holding row y0 when its load is abandoned."""
         _check(lib().pbx_band_abort(self._h, plane_id, y0))
@@ -1604,17 +1652,21 @@ class PixelsService:
         the bands that rows [y, y + h) cover, each read from `source` once; bands another
         caller is loading are waited for.  A source with chunk-level access
         (PixelSource.band_chunks) hands over the Zarr chunk rows covering each band, which are
-        decoded on the GPU (band_write_zarr); any other source is read with read_rows.  Returns
-        the plane id."""
+        decoded on the GPU (band_write_zarr); one with segment-level access
+        (PixelSource.band_segments) the TIFF strips or tile rows (band_write_tiff); any other
+        source is read with read_rows.  Returns the plane id."""
         self.declare_image(pixels)
         key = (pixels.image_id, z, c, t, level)
         sx, sy = source.level_size(pixels, level)
         band_chunks = getattr(source, "band_chunks", None)
+        band_segments = getattr(source, "band_segments", None)
         with self._exclusive(key):
             found = self.lookup_plane(*key)
             if found is None or found[1] == PS_EVICTED:
                 # chunks stay in the array's byte order (no rows: nothing is read for this)
                 sp = band_chunks(pixels, z, c, t, level, 0, 0) if band_chunks is not None else None
+                if sp is None and band_segments is not None:  # segments stay in the file's byte order
+                    sp = band_segments(pixels, z, c, t, level, 0, 0)
                 try:
                     pid = self.create_sparse_plane(pixels.image_id, z, c, t, pixels.pixel_type, sx, sy,
                                                    self.sparse_band_rows, level, own=own,
@@ -1643,7 +1695,13 @@ class PixelsService:
                         try:
                             sp = (band_chunks(pixels, z, c, t, level, r0, r1 - r0)
                                   if band_chunks is not None else None)
-                            if sp is not None:
+                            tsp = (band_segments(pixels, z, c, t, level, r0, r1 - r0)
+                                   if sp is None and band_segments is not None else None)
+                            if tsp is not None:
+                                self.band_write_tiff(pid, r0, r1 - r0, tsp["seg_w"], tsp["seg_h"],
+                                                     tsp["tiled"], tsp["compression"], tsp["predictor"],
+                                                     tsp["segments"])
+                            elif sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
                                                      chunk_planes=sp.get("chunk_planes", 1),
@@ -1999,6 +2057,16 @@ class PixelSource:
         (register_tiff_planes), instead of calling read_rows.  None (the default): rows only."""
         return None
 
+    def band_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
+                      rows: int) -> Optional[dict]:
+        """Optional, for storage that is TIFF: the strips or tile rows covering rows
+        [y0, y0 + rows) of the plane at that level, as tiff_band_spec returns them (seg_w,
+        seg_h, tiled, compression, predictor, segments, big_endian = the file's byte order);
+        load_bands then has them decoded on the GPU (band_write_tiff) instead of calling
+        read_rows.  rows == 0 asks for the byte order and geometry only and must read no
+        segment.  None (the default): no segment-level access."""
+        return None
+
 
 class NgffSource(PixelSource):
     """NGFF multiscale images on disk, {image_id: image directory} -- what ZarrPixelsService
@@ -2051,9 +2119,11 @@ class NgffSource(PixelSource):
 class TiffSource(PixelSource):
     """TIFF / OME-TIFF files on disk, {image_id: path} -- the original files the ordinary OMERO
     PixelsService opens through Bio-Formats when an image has no NGFF fileset (config.yaml:18).
-    A plane the context does not hold is registered whole from its IFD's strips or tiles, decoded
-    on the GPU (plane_segments -> PixelsService.load_plane -> register_tiff_planes); loading by
-    bands is not implemented, so it needs a service without sparse_band_rows."""
+    On a service without sparse_band_rows a plane the context does not hold is registered whole
+    from its IFD's strips or tiles (plane_segments -> PixelsService.load_plane ->
+    register_tiff_planes); with sparse_band_rows only the bands a request's rows cover are
+    loaded, each from the strips or tile rows that cover it (band_segments -> load_bands ->
+    band_write_tiff).  Either way every byte of pixel data is decoded on the GPU."""
 
     def __init__(self, images: Mapping[int, str]):
         import threading
@@ -2088,10 +2158,15 @@ class TiffSource(PixelSource):
         return tiff_plane_spec(self.images[pixels.image_id], self._ifd(pixels, z, c, t, level),
                                pixels.image_id, z, c, t, level)
 
+    def band_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
+                      rows: int) -> Optional[dict]:
+        return tiff_band_spec(self.images[pixels.image_id], self._ifd(pixels, z, c, t, level), y0, rows)
+
     def read_rows(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
                   rows: int) -> bytes:
-        raise PbxError(E_BADARG, "TiffSource hands over TIFF segments, not rows: serve it from a "
-                       "PixelsService without sparse_band_rows and without a band")
+        raise PbxError(E_BADARG, "TiffSource hands over TIFF segments, not rows: whole planes go "
+                       "through plane_segments and bands of a sparse plane through band_segments, "
+                       "so serve it without a whole-row band")
 
 
 # ----------------------------------------------------------------- TileRequestHandler
