@@ -367,8 +367,13 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * then Predictor = 2 (horizontal differencing over whole samples in the file's byte order) is
  * undone per segment row (k_tiff_unpred) and k_zarr_place puts the segments into the plane.
  * pbx_band_write_tiff loads a sparse plane band by band from the segment rows a band covers.
- * Not supported (400 by the caller or here): SamplesPerPixel != 1, Predictor 3, FillOrder 2,
- * pre-6.0 (LSB-first) LZW streams, JPEG / PackBits / other compressions.
+ * Files with 2 .. 4 samples per pixel (RGB, RGBA) give one plane per sample: chunky segments
+ * (PlanarConfiguration 1) through pbx_planes_register_tiff_samples / pbx_band_write_tiff_sample,
+ * which split them on the GPU (k_tiff_split_place); planar ones (PlanarConfiguration 2) are
+ * single-sample segments already and go through the calls below.
+ * Not supported (400 by the caller or here): SamplesPerPixel > 4, Predictor 3, FillOrder 2,
+ * pre-6.0 (LSB-first) LZW streams, JPEG / PackBits / other compressions, YCbCr / CMYK / palette
+ * colour, sub-byte or 12-bit samples.
  * The JNI shim does not wrap these calls (as the deep Zarr calls). */
 enum pbx_tiff_compression { PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8 };
 typedef struct pbx_tiff_segments {
@@ -420,6 +425,32 @@ int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* des
  * (about 0 for stored segments, which launch none), [1] of the placement. */
 int pbx_band_write_tiff(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                         const pbx_tiff_segments* segs, double* kernel_ms);
+/* Chunky multi-sample segments (SamplesPerPixel S = 2 .. 4, PlanarConfiguration 1: RGB, RGBA and
+ * the like), one plane per sample, modelled on the deep-Zarr pair.  Plane k (descs[k]) is sample
+ * refs[k].slice of layers[refs[k].layer], whose segments hold samples_per_pixel[layer]
+ * interleaved samples per pixel: a segment row is seg_w * S samples and an uncompressed segment
+ * seg_w * rows * bpp * S bytes.  Each layer is uploaded and decoded ONCE; k_tiff_split_place then
+ * undoes Predictor = 2 with a stride of S samples (every sample is differenced against the same
+ * component of the pixel before, TIFF 6.0 section 14) and scatters the components into their
+ * planes in one pass.  Keys, all-or-none registration, statuses, staging and every segment
+ * refusal are pbx_planes_register_tiff's, and with every samples_per_pixel == 1 the call is that
+ * call.  400 also for: samples_per_pixel outside 1 .. 4, a sample >= S, S > 1 on 64-bit samples
+ * (double), a layer no plane names, two planes naming the same sample of a layer, planes of one
+ * layer that disagree on size, type or byte order.  Not every sample of a layer need be named:
+ * the others are decoded (they are interleaved) but stored nowhere. */
+int pbx_planes_register_tiff_samples(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
+                                     const pbx_zarr_slice* refs, uint64_t n_layers,
+                                     const pbx_tiff_segments* layers, const int32_t* samples_per_pixel,
+                                     uint64_t* plane_ids, double* kernel_ms);
+/* pbx_band_write_tiff for chunky segments of samples_per_pixel samples per pixel: the covering
+ * segment rows are decoded for this call and only sample `sample` is written, into the band of
+ * `plane_id` (one plane per call, as pbx_band_write_zarr_deep: a cold region of all S channels
+ * decodes its segments S times).  Stored segments are read where they were uploaded.  With
+ * samples_per_pixel == 1 (sample 0) this is pbx_band_write_tiff.  400 as that call and as
+ * pbx_planes_register_tiff_samples. */
+int pbx_band_write_tiff_sample(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                               const pbx_tiff_segments* segs, int32_t samples_per_pixel, int32_t sample,
+                               double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -692,6 +723,18 @@ int pbx_test_tiff_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t si
  * outside the plane. */
 int pbx_test_tiff_band_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
                             int32_t y0, int32_t rows, uint64_t out[4]);
+
+/* Test hook: the host planner of pbx_planes_register_tiff_samples (rows == 0: the whole plane) or
+ * pbx_band_write_tiff_sample (rows >= 1: rows [y0, y0 + rows), segs holding the covering segment
+ * rows only) alone, no context and no device call, for a plane of size_x x size_y pixels of bpp
+ * bytes a sample and segments of samples_per_pixel samples per pixel.  out: streams handed to a
+ * decoder (stored multi-sample segments count 0: they are read where they were uploaded), the sum
+ * of the decoded lengths of every segment planned (samples_per_pixel times the single-sample
+ * figure), scratch bytes, and the number of segments handed to k_tiff_split_place (for
+ * samples_per_pixel == 1: out[3] of pbx_test_tiff_plan / pbx_test_tiff_band_plan).  400 as the real
+ * calls. */
+int pbx_test_tiff_plan_samples(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
+                               int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[4]);
 
 #ifdef __cplusplus
 }

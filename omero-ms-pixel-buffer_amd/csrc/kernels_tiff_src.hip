@@ -8,6 +8,9 @@
 //                   the row's samples in the file's byte order, modulo 2^bits)
 //   k_tiff_unpred_place   the same sums taken on the way from the decoded segment into a band of
 //                   a sparse plane (pbx_band_write_tiff): read once, stored once
+//   k_tiff_split_place    chunky segments of 2 .. 4 samples per pixel (RGB, RGBA): the sums with
+//                   a stride of S samples and the S interleaved components scattered into S
+//                   pitched planes, in one pass (registration and band writes alike)
 //
 // Deflate segments go through k_zarr_inflate2 and stored ones through k_zarr_copy; every kind
 // is placed by k_zarr_place (kernels_zarr.hip).  A band write reads stored segments where they
@@ -305,6 +308,113 @@ __global__ __launch_bounds__(64 * UP_WAVES) void k_tiff_unpred_place(const TPlac
     else unpred_place_rows<4>(s, rb, o, d.pitch, r0, r1, vis, be, lane, w);
 }
 
+// ------------------------------------------------- split and place (SamplesPerPixel 2 .. 4)
+// Chunky segments (PlanarConfiguration = 1): a row is seg_w pixels of S interleaved samples, and
+// OMERO stores every sample as a channel of its own, so component s of every pixel goes to plane
+// dev[s].  k_tiff_unpred_place's geometry and clipping; a lane owns 16 / BPP pixels a step: S
+// consecutive 16-byte groups of the chunky row (loaded with unpred_load's guards: strips are
+// unaligned and the row's tail is partial), de-interleaved in registers into S groups of 16
+// bytes, one per component.  Predictor = 2 differences a sample against the same component of
+// the pixel before (TIFF 6.0 section 14), so every component is a row of its own: unpred_group
+// with that component's carry, S wave scans a step.  Every wanted component is then stored as
+// k_tiff_unpred_place stores its one: whole groups as aligned 16-byte stores, the row's last,
+// partial group byte by byte.  A step is 1024 / BPP pixels.
+template <uint32_t BPP, uint32_t S>
+__device__ __forceinline__ void split_place_row(const uint8_t* __restrict__ row, uint8_t* const (&out)[S],
+                                                uint32_t wanted, uint32_t vis, bool pred, bool be,
+                                                uint32_t lane) {
+    constexpr uint32_t NP = 16 / BPP;  // pixels a lane a step
+    constexpr uint32_t MASK = BPP == 4 ? 0xffffffffu : (1u << (8 * (BPP & 3))) - 1;
+    uint32_t carry[S];
+#pragma unroll
+    for (uint32_t s = 0; s < S; s++) carry[s] = 0;
+    for (uint32_t k0 = 0; k0 < vis; k0 += 1024) {
+        const uint32_t off = k0 + 16 * lane;  // in a component's row
+        const uint32_t have = off >= vis ? 0u : vis - off < 16 ? vis - off : 16u;  // a multiple of BPP
+        const uint32_t hin = have * S;        // whole pixels of the chunky row
+        uint32_t in[4 * S];
+#pragma unroll
+        for (uint32_t g = 0; g < S; g++) {
+            uint32_t wv[4];
+            const uint32_t hg = hin <= 16 * g ? 0u : hin - 16 * g < 16 ? hin - 16 * g : 16u;
+            unpred_load(row + (uint64_t)off * S + 16 * g, hg, wv);
+            in[4 * g] = wv[0]; in[4 * g + 1] = wv[1]; in[4 * g + 2] = wv[2]; in[4 * g + 3] = wv[3];
+        }
+#pragma unroll
+        for (uint32_t s = 0; s < S; s++) {
+            uint32_t cv[4] = {0, 0, 0, 0}, ov[4];
+#pragma unroll
+            for (uint32_t i = 0; i < NP; i++) {
+                const uint32_t b = (i * S + s) * BPP;  // the sample's byte in the lane's chunky bytes
+                const uint32_t v = BPP == 4 ? in[b >> 2] : (in[b >> 2] >> (8 * (b & 3))) & MASK;
+                cv[(i * BPP) >> 2] |= v << (8 * ((i * BPP) & 3));
+            }
+            if (pred) {
+                unpred_group<BPP>(cv, be, lane, carry[s], ov);
+            } else {
+                ov[0] = cv[0]; ov[1] = cv[1]; ov[2] = cv[2]; ov[3] = cv[3];
+            }
+            if (!((wanted >> s) & 1)) continue;
+            uint8_t* o = out[s];
+            if (have == 16) {
+                *(uint4*)(o + off) = make_uint4(ov[0], ov[1], ov[2], ov[3]);
+            } else {
+#pragma unroll
+                for (uint32_t b = 0; b < 16; b++)
+                    if (b < have) o[off + b] = (uint8_t)(ov[b >> 2] >> (8 * (b & 3)));
+            }
+        }
+    }
+}
+
+template <uint32_t BPP, uint32_t S>
+__device__ __forceinline__ void split_place_rows(const uint8_t* __restrict__ s, uint32_t rb, const TSplitDst& d,
+                                                 int32_t x0, int32_t y0, int32_t r0, int32_t r1, uint32_t vis,
+                                                 uint32_t lane, uint32_t w) {
+    uint32_t wanted = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < S; c++) wanted |= d.dev[c] ? 1u << c : 0u;
+    wanted = rfl(wanted);
+    const bool pred = d.predictor == 2, be = BPP > 1 && d.big_endian != 0;
+    for (int32_t r = r0 + (int32_t)w; r < r1; r += (int32_t)UP_WAVES) {
+        uint8_t* out[S];
+#pragma unroll
+        for (uint32_t c = 0; c < S; c++) out[c] = d.dev[c] + (int64_t)(y0 + r) * d.pitch + (int64_t)x0 * BPP;
+        split_place_row<BPP, S>(s + (uint64_t)r * rb, out, wanted, vis, pred, be, lane);
+    }
+}
+
+__global__ __launch_bounds__(64 * UP_WAVES) void k_tiff_split_place(const TPlace* __restrict__ sg,
+                                                                    const TSplitDst* __restrict__ dt,
+                                                                    const uint8_t* __restrict__ scratch,
+                                                                    const uint8_t* __restrict__ input) {
+    const uint32_t lane = threadIdx.x & 63, w = rfl(threadIdx.x >> 6);
+    const TPlace u = sg[blockIdx.x];
+    const TSplitDst d = dt[rfl(u.pad)];
+    const int32_t x0 = (int32_t)rfl((uint32_t)u.x0), y0 = (int32_t)rfl((uint32_t)u.y0);
+    const int32_t rows = (int32_t)rfl(u.rows);
+    const uint32_t rb = rfl(u.row_bytes), bpp = rfl(d.bpp), spp = rfl(d.spp);
+    // segment rows of this run that lie in the window and in the plane
+    int32_t r0 = (int32_t)(blockIdx.y * UP_ROWS), r1 = r0 + (int32_t)UP_ROWS;
+    const int32_t top = d.y_lo > 0 ? d.y_lo : 0, bottom = d.y_hi < d.sy ? d.y_hi : d.sy;
+    r1 = r1 < rows ? r1 : rows;
+    r0 = r0 > top - y0 ? r0 : top - y0;
+    r1 = r1 < bottom - y0 ? r1 : bottom - y0;
+    if (r0 >= r1 || x0 >= d.sx || spp < 2 || spp > 4) return;
+    // a component's visible bytes of a row: the plane's edge or the segment's
+    const uint32_t wvis = (uint32_t)(d.sx - x0) * bpp, segb = rb / spp;
+    const uint32_t vis = wvis < segb ? wvis : segb;
+    const uint8_t* s = (rfl(u.from_input) ? input : scratch) + u.src;
+    switch (bpp * 8 + spp) {  // once per workgroup
+#define PBX_SPLIT(B, S) case B * 8 + S: split_place_rows<B, S>(s, rb, d, x0, y0, r0, r1, vis, lane, w); break;
+        PBX_SPLIT(1, 2) PBX_SPLIT(1, 3) PBX_SPLIT(1, 4)
+        PBX_SPLIT(2, 2) PBX_SPLIT(2, 3) PBX_SPLIT(2, 4)
+        PBX_SPLIT(4, 2) PBX_SPLIT(4, 3) PBX_SPLIT(4, 4)
+#undef PBX_SPLIT
+        default: break;
+    }
+}
+
 hipError_t launch_tiff_lzw(hipStream_t st, const ZStream* d_streams, uint32_t n, const uint8_t* src,
                            uint8_t* scratch, uint32_t* err) {
     if (!n) return hipSuccess;
@@ -326,6 +436,14 @@ hipError_t launch_tiff_unpred_place(hipStream_t st, const TPlace* d_segs, uint32
     if (!n || !max_rows) return hipSuccess;
     hipLaunchKernelGGL(k_tiff_unpred_place, dim3(n, (max_rows + UP_ROWS - 1) / UP_ROWS), dim3(64 * UP_WAVES), 0, st,
                        d_segs, dst, scratch, input);
+    return hipGetLastError();
+}
+
+hipError_t launch_tiff_split_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
+                                   const TSplitDst* d_dst, const uint8_t* scratch, const uint8_t* input) {
+    if (!n || !max_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tiff_split_place, dim3(n, (max_rows + UP_ROWS - 1) / UP_ROWS), dim3(64 * UP_WAVES), 0, st,
+                       d_segs, d_dst, scratch, input);
     return hipGetLastError();
 }
 

@@ -193,7 +193,8 @@ struct TPlace {
     uint32_t row_bytes;  // seg_w * bpp, the segment's own pitch
     uint32_t rows;       // rows it holds (a short last strip: the rows left)
     int32_t x0, y0;      // its origin in the plane
-    uint32_t from_input, pad;
+    uint32_t from_input;
+    uint32_t pad;        // k_tiff_split_place: the segment's entry in the launch's TSplitDst table
 };
 static_assert(sizeof(TPlace) == 32, "TPlace is uploaded as is");
 struct TPlaceDst {       // passed by value
@@ -206,5 +207,23 @@ struct TPlaceDst {       // passed by value
 };
 hipError_t launch_tiff_unpred_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
                                     const TPlaceDst& dst, const uint8_t* scratch, const uint8_t* input);
+// k_tiff_split_place (SamplesPerPixel 2 .. 4, PlanarConfiguration 1): a segment row holds spp
+// interleaved samples per pixel (TPlace::row_bytes = seg_w * bpp * spp).  The kernel undoes
+// Predictor = 2 with a stride of spp samples and stores component s of every pixel into plane
+// dev[s]; a null dev[s] is a component nobody wants (a band write stores one).  One table entry
+// per layer (TPlace::pad), so one launch serves every layer of a registration.
+struct TSplitDst {
+    uint8_t* dev[4];     // row 0 of component s's plane (a band: its virtual base), 256-byte aligned
+    int64_t pitch;       // of every plane of the entry, a multiple of 256
+    int32_t sx, sy;      // plane size in pixels
+    int32_t y_lo, y_hi;  // plane rows that may be written
+    uint32_t bpp;        // bytes per sample: 1, 2 or 4
+    uint32_t big_endian;
+    uint32_t spp;        // 2, 3 or 4
+    uint32_t predictor;  // 1 or 2
+};
+static_assert(sizeof(TSplitDst) == 72, "TSplitDst is uploaded as is");
+hipError_t launch_tiff_split_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
+                                   const TSplitDst* d_dst, const uint8_t* scratch, const uint8_t* input);
 
 }  // namespace pbx

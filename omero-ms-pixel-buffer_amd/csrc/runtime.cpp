@@ -2335,6 +2335,11 @@ struct ZarrPlan {
     std::vector<TPlace> uplace;
     uint32_t uplace_rows = 0;     // the tallest of them
     bool uplace_big_endian = false;
+    // chunky TIFF segments of 2 .. 4 samples per pixel: every segment, whatever its predictor, for
+    // k_tiff_split_place (then no `unpred`, no `uplace` and no `chunks`); TPlace::pad names the
+    // segment's entry in the launch's TSplitDst table
+    std::vector<TPlace> split;
+    uint32_t split_rows = 0;      // the tallest of them
 };
 
 // A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
@@ -2599,9 +2604,13 @@ struct ZarrInput {
 // a decoder rejects; rows already placed are then the caller's to discard.  P.unpred (TIFF
 // segments stored with Predictor = 2) is undone in scratch between the decoders and the placement;
 // P.uplace (the same for a band write) is un-predicted and placed into zp[0] by one kernel after
-// the decoders, and k_zarr_place is launched only if P has chunks.
+// the decoders, and k_zarr_place is launched only if P has chunks.  P.split (multi-sample TIFF
+// segments) is un-predicted and split into the planes of `sd` by k_tiff_split_place.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
-                      const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms) {
+                      const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms,
+                      const std::vector<TSplitDst>* sd = nullptr) {
+    if (!P.split.empty() && (!sd || sd->empty()))
+        return fail(PBX_E_INTERNAL, "zarr decode: split segments without destinations");
     uint32_t counts[ZS_NKINDS], nstreams = 0;
     std::vector<ZStream> all;
     for (uint32_t k = 0; k < ZS_NKINDS; k++) {
@@ -2628,13 +2637,15 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     ZPlane* d_pl = nullptr;
     TUnpred* d_up = nullptr;
     TPlace* d_tp = nullptr;
+    TPlace* d_sp = nullptr;
+    TSplitDst* d_sd = nullptr;
     uint32_t* d_err = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto cleanup = [&] {
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2652,6 +2663,10 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     dget(d_pl, sizeof(ZPlane) * zp.size());
     if (!P.unpred.empty()) dget(d_up, sizeof(TUnpred) * P.unpred.size());
     if (!P.uplace.empty()) dget(d_tp, sizeof(TPlace) * P.uplace.size());
+    if (!P.split.empty()) {
+        dget(d_sp, sizeof(TPlace) * P.split.size());
+        dget(d_sd, sizeof(TSplitDst) * sd->size());
+    }
     dget(d_err, sizeof(uint32_t) * (nerr + 1));
     for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
     if (e != hipSuccess) {
@@ -2679,6 +2694,10 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = hipMemcpyAsync(d_up, P.unpred.data(), sizeof(TUnpred) * P.unpred.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_tp)
         e = hipMemcpyAsync(d_tp, P.uplace.data(), sizeof(TPlace) * P.uplace.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_sp)
+        e = hipMemcpyAsync(d_sp, P.split.data(), sizeof(TPlace) * P.split.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_sd)
+        e = hipMemcpyAsync(d_sd, sd->data(), sizeof(TSplitDst) * sd->size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
     // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
@@ -2702,6 +2721,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
                                                P.uplace_big_endian ? 1u : 0u},
                                      d_scr, d_in);
     }
+    if (e == hipSuccess && d_sp)
+        e = launch_tiff_split_place(st, d_sp, (uint32_t)P.split.size(), P.split_rows, d_sd, d_scr, d_in);
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     std::vector<uint32_t> err(nerr + 1, 0);
@@ -2781,6 +2802,15 @@ int tiff_segments_check(const pbx_tiff_segments* s) {
     return PBX_OK;
 }
 
+// A sample of chunky segments that hold spp samples per pixel, on a plane of bpp bytes a sample.
+int tiff_samples_check(int32_t spp, int64_t sample, int bpp) {
+    if (spp < 1 || spp > 4) return fail(PBX_E_BADARG, "samples_per_pixel %d outside 1 .. 4", spp);
+    if (sample < 0 || sample >= spp)
+        return fail(PBX_E_BADARG, "sample %lld outside segments of %d samples per pixel", (long long)sample, spp);
+    if (spp > 1 && bpp == 8) return fail(PBX_E_BADARG, "samples_per_pixel %d on 64-bit samples", spp);
+    return PBX_OK;
+}
+
 // Host plan of one plane's strips or tiles: one stream per segment (its own row count: the last
 // strip holds only the rows left), one ZChunk to place it, and for Predictor = 2 its rows for
 // k_tiff_unpred.  No byte of segment data is decoded here.
@@ -2789,9 +2819,13 @@ int tiff_segments_check(const pbx_tiff_segments* s) {
 // (ZC_INPUT, no stream, no scratch), and with Predictor = 2 every segment goes into P.uplace for
 // k_tiff_unpred_place instead of P.unpred and P.chunks.  Segment numbers in messages count from
 // the first segment handed over.
+// With spp > 1 (chunky samples) a segment row holds spp samples per pixel, and registration and
+// band writes are planned alike: a stored segment is read where it was uploaded, and every
+// segment, whatever the predictor, goes into P.split for k_tiff_split_place with `dst` as its
+// entry in the launch's TSplitDst table.
 int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pbx_tiff_segments* s,
               uint64_t in_base, uint32_t plane, ZarrPlan& P, uint64_t* dlen_sum, bool band = false,
-              int64_t sr0 = 0, int64_t sr1 = -1) {
+              int64_t sr0 = 0, int64_t sr1 = -1, int spp = 1, uint32_t split_dst = 0) {
     if (!s->tiled && s->seg_w != size_x)
         return fail(PBX_E_BADARG, "strip width %d != plane width %d", s->seg_w, size_x);
     if (s->predictor == 2 && bpp == 8) return fail(PBX_E_BADARG, "predictor 2 on floating-point samples");
@@ -2807,11 +2841,11 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
         if (len == 0) return fail(PBX_E_BADARG, "segment %lld is empty", (long long)i);
         const int32_t x0 = (int32_t)((i % gx) * s->seg_w), y0 = (int32_t)((sr0 + i / gx) * s->seg_h);
         const int32_t rows = s->tiled ? s->seg_h : std::min(s->seg_h, size_y - y0);
-        const uint64_t dlen = (uint64_t)s->seg_w * (uint64_t)rows * (uint64_t)bpp;
+        const uint64_t dlen = (uint64_t)s->seg_w * (uint64_t)rows * (uint64_t)bpp * (uint64_t)spp;
         if (dlen > 0x7fffffffull || len > 0x7fffffffull || rows > (65535 << 4))
             return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
         const uint64_t ob = o + in_base;
-        const bool in_place = band && s->compression == PBX_TIFF_NONE;  // read from the upload buffer
+        const bool in_place = (band || spp > 1) && s->compression == PBX_TIFF_NONE;  // read from the upload buffer
         const uint64_t dst = in_place ? ob : P.scratch;
         uint32_t kind = ZS_COPY;
         if (s->compression == PBX_TIFF_NONE) {
@@ -2829,6 +2863,12 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
         if (!in_place) P.kind[kind].push_back(ZStream{ob, dst, (uint32_t)len, (uint32_t)dlen, kind, 0});
         if (dlen_sum) *dlen_sum += dlen;
         if (!in_place) P.scratch += (dlen + 255) & ~255ull;
+        if (spp > 1) {
+            P.split.push_back(TPlace{dst, (uint32_t)s->seg_w * (uint32_t)bpp * (uint32_t)spp, (uint32_t)rows, x0, y0,
+                                     in_place ? 1u : 0u, split_dst});
+            P.split_rows = std::max(P.split_rows, (uint32_t)rows);
+            continue;
+        }
         if (band && s->predictor == 2) {
             P.uplace.push_back(TPlace{dst, (uint32_t)s->seg_w * (uint32_t)bpp, (uint32_t)rows, x0, y0,
                                       in_place ? 1u : 0u, 0});
@@ -2857,18 +2897,21 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
 // pbx_band_write_tiff: pbx_band_write_zarr for segment rows.  The piece's covering segment rows
 // are planned on the host first (a malformed piece never joins the band's load), then uploaded,
 // decoded and placed under the band state machine of band_load_rows.
+// With spp > 1 the segments are chunky and only component `sample` is written (the others'
+// destinations are null).
 int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
-                    double* kernel_ms) {
+                    int32_t spp, int32_t sample, double* kernel_ms) {
     int32_t k = 0;
     if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
     if (int rc = tiff_segments_check(s)) return rc;
+    if (int rc = tiff_samples_check(spp, sample, bpp_of(q->pixel_type))) return rc;
     if (s->predictor == 2 && (q->pixel_type == PBX_FLOAT || q->pixel_type == PBX_DOUBLE))
         return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)q->id);
     const int bpp = bpp_of(q->pixel_type);
     const int64_t gx = s->tiled ? ((int64_t)q->size_x + s->seg_w - 1) / s->seg_w : 1;
     const int64_t sr0 = y0 / s->seg_h, sr1 = ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h;
     ZarrPlan P;
-    if (int rc = tiff_plan(q->size_x, q->size_y, bpp, !q->little_endian, s, 0, 0, P, nullptr, true, sr0, sr1))
+    if (int rc = tiff_plan(q->size_x, q->size_y, bpp, !q->little_endian, s, 0, 0, P, nullptr, true, sr0, sr1, spp, 0))
         return rc;
     const uint64_t used = s->offsets[gx * (sr1 - sr0)], len = (used + 15) & ~15ull;
     const std::vector<ZarrInput> in{ZarrInput{s->data, used, 0, len}};
@@ -2876,7 +2919,14 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
         // rows keep their plane index: the destination is the band's virtual base
         const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
                                             q->size_y, s->seg_w, s->seg_h, (uint32_t)bpp, 0, 0, y0, y0 + rows}};
-        return zarr_decode_place(ctx, ctx->upload_stream, P, zp, in, len, std::min(s->seg_h, q->size_y), kernel_ms);
+        std::vector<TSplitDst> sd;
+        if (spp > 1) {
+            sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, q->pitch, q->size_x, q->size_y, y0, y0 + rows,
+                                   (uint32_t)bpp, q->little_endian ? 0u : 1u, (uint32_t)spp, (uint32_t)s->predictor});
+            sd[0].dev[sample] = zp[0].dev;
+        }
+        return zarr_decode_place(ctx, ctx->upload_stream, P, zp, in, len, std::min(s->seg_h, q->size_y), kernel_ms,
+                                 &sd);
     });
 }
 
@@ -2885,7 +2935,9 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
 // planes each.  A layer's chunks are planned, uploaded and decoded once; its planes follow one
 // another in the ZChunk table.  With `ts` the layers are TIFF segments instead (zs unused, one
 // plane per layer): pbx_planes_register_tiff shares the keys, the all-or-none registration, the
-// staging and the launches.
+// staging and the launches.  A TIFF layer with depths[layer] = S > 1 holds chunky segments of S
+// samples per pixel (pbx_planes_register_tiff_samples): its planes are the samples refs[k].slice,
+// each at most once, all split out of the one decode by k_tiff_split_place.
 int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
                          uint64_t n_layers, const pbx_zarr_chunks* zs, const int32_t* depths,
                          uint64_t* plane_ids, double* kernel_ms, const pbx_tiff_segments* ts = nullptr) {
@@ -2898,10 +2950,15 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
             if (int rc = tiff_segments_check(&ts[refs[k].layer])) return rc;
             if (ts[refs[k].layer].predictor == 2 && (d->pixel_type == PBX_FLOAT || d->pixel_type == PBX_DOUBLE))
                 return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)k);
+            if (int rc = tiff_samples_check(depths[refs[k].layer], refs[k].slice, bpp_of(d->pixel_type))) return rc;
+            for (const ZarrWant& w : want[refs[k].layer])
+                if (w.slice == refs[k].slice)
+                    return fail(PBX_E_BADARG, "planes %u and %llu both name sample %u of layer %u", w.plane,
+                                (unsigned long long)k, refs[k].slice, refs[k].layer);
         } else {
             if (int rc = zarr_chunks_check(&zs[refs[k].layer])) return rc;
+            if (int rc = zarr_slice_check(depths[refs[k].layer], refs[k].slice)) return rc;
         }
-        if (int rc = zarr_slice_check(depths[refs[k].layer], refs[k].slice)) return rc;
         want[refs[k].layer].push_back(ZarrWant{refs[k].slice, (uint32_t)k});
         if (!bpp_of(d->pixel_type)) return fail(PBX_E_BADARG, "bad pixel type %d", d->pixel_type);
         if (d->size_x <= 0 || d->size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
@@ -2945,13 +3002,23 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
     std::vector<uint64_t> in_base(n_layers + 1, 0);
     std::vector<ZarrInput> in(n_layers);
     int32_t max_cy = 0;
+    std::vector<TSplitDst> sd;        // one per multi-sample TIFF layer ...
+    std::vector<uint64_t> sd_layer;   // ... and which layer that is
     for (uint64_t l = 0; l < n_layers; l++) {
         const pbx_plane_desc* d = &ds[want[l][0].plane];
         if (ts) {
             const pbx_tiff_segments* s = &ts[l];
-            if (int rc = tiff_plan(d->size_x, d->size_y, bpp_of(d->pixel_type), d->byte_order != PBX_LITTLE_ENDIAN, s,
-                                   in_base[l], want[l][0].plane, P, nullptr))
+            const int bpp = bpp_of(d->pixel_type);
+            const bool big = d->byte_order != PBX_LITTLE_ENDIAN;
+            if (int rc = tiff_plan(d->size_x, d->size_y, bpp, big, s, in_base[l], want[l][0].plane, P, nullptr, false,
+                                   0, -1, depths[l], (uint32_t)sd.size()))
                 return rc;
+            if (depths[l] > 1) {
+                sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255,
+                                       d->size_x, d->size_y, 0, d->size_y, (uint32_t)bpp, big && bpp > 1 ? 1u : 0u,
+                                       (uint32_t)depths[l], (uint32_t)s->predictor});
+                sd_layer.push_back(l);
+            }
             const int64_t gx = s->tiled ? ((int64_t)d->size_x + s->seg_w - 1) / s->seg_w : 1;
             const int64_t gy = ((int64_t)d->size_y + s->seg_h - 1) / s->seg_h;
             in_base[l + 1] = in_base[l] + ((s->offsets[gx * gy] + 15) & ~15ull);
@@ -2999,10 +3066,12 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
         }
         zp[k].dev = ps[k].dev;
     }
+    for (size_t i = 0; i < sd.size(); i++)
+        for (const ZarrWant& w : want[sd_layer[i]]) sd[i].dev[w.slice] = ps[w.plane].dev;
     hipError_t e = hipSuccess;
     for (uint64_t k = 0; k < n && e == hipSuccess; k++)  // over-read slack after the last row
         e = hipMemsetAsync(ps[k].dev + (size_t)ps[k].pitch * ps[k].size_y, 0, 256, ctx->stream);
-    int rc = e == hipSuccess ? zarr_decode_place(ctx, ctx->stream, P, zp, in, in_base[n_layers], max_cy, kernel_ms)
+    int rc = e == hipSuccess ? zarr_decode_place(ctx, ctx->stream, P, zp, in, in_base[n_layers], max_cy, kernel_ms, &sd)
                              : fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
     if (rc) {
         const std::string msg = g_err;
@@ -3079,6 +3148,15 @@ int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     return register_zarr_layers(ctx, n, ds, refs.data(), n, nullptr, depths.data(), plane_ids, kernel_ms, segs);
 }
 
+int pbx_planes_register_tiff_samples(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
+                                     uint64_t n_layers, const pbx_tiff_segments* layers,
+                                     const int32_t* samples_per_pixel, uint64_t* plane_ids, double* kernel_ms) {
+    if (!ctx || !ds || !refs || !layers || !samples_per_pixel || !plane_ids || n == 0 || n_layers == 0)
+        return fail(PBX_E_BADARG, "null argument");
+    if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms, layers);
+}
+
 int pbx_test_tiff_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t bpp, uint64_t out[4]) {
     if (!s || !out) return fail(PBX_E_BADARG, "null argument");
     if (int rc = tiff_segments_check(s)) return rc;
@@ -3118,17 +3196,45 @@ int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, con
     return pbx_band_write_zarr_deep(ctx, id, y0, rows, z, 1, 0, kernel_ms);
 }
 
-int pbx_band_write_tiff(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
-                        double* kernel_ms) {
+int pbx_band_write_tiff_sample(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
+                               int32_t samples_per_pixel, int32_t sample, double* kernel_ms) {
     if (!ctx || !s) return fail(PBX_E_BADARG, "null argument");
     int rc;
     Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
     if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
-    rc = band_write_tiff(ctx, q, y0, rows, s, kernel_ms);
+    rc = band_write_tiff(ctx, q, y0, rows, s, samples_per_pixel, sample, kernel_ms);
     const std::string msg = g_err;
     unpin_one(ctx, q);
     g_err = msg;
     return rc;
+}
+
+int pbx_band_write_tiff(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
+                        double* kernel_ms) {
+    return pbx_band_write_tiff_sample(ctx, id, y0, rows, s, 1, 0, kernel_ms);
+}
+
+int pbx_test_tiff_plan_samples(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t bpp,
+                               int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[4]) {
+    if (!s || !out) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = tiff_segments_check(s)) return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    if (bpp != 1 && bpp != 2 && bpp != 4 && bpp != 8) return fail(PBX_E_BADARG, "bad sample size %d", bpp);
+    if (int rc = tiff_samples_check(samples_per_pixel, 0, bpp)) return rc;
+    if (rows < 0 || y0 < 0 || (int64_t)y0 + rows > size_y)
+        return fail(PBX_E_BADARG, "rows %d+%d outside the plane (%d rows)", y0, rows, size_y);
+    ZarrPlan P;
+    uint64_t sum = 0;
+    const bool band = rows > 0;
+    if (int rc = tiff_plan(size_x, size_y, bpp, true, s, 0, 0, P, &sum, band, band ? y0 / s->seg_h : 0,
+                           band ? ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h : -1, samples_per_pixel, 0))
+        return rc;
+    out[0] = 0;
+    for (const auto& k : P.kind) out[0] += k.size();
+    out[1] = sum;
+    out[2] = P.scratch;
+    out[3] = samples_per_pixel > 1 ? P.split.size() : (band ? P.uplace.empty() : P.unpred.empty()) ? 0 : 1;
+    return PBX_OK;
 }
 
 int pbx_test_tiff_band_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t bpp, int32_t y0,

@@ -163,7 +163,8 @@ EXPORTS = [
     "pbx_set_tiff_predictor", "pbx_get_tiff_predictor", "pbx_batch_pred_tiles",
     "pbx_band_write_zarr", "pbx_planes_register_zarr_deep", "pbx_band_write_zarr_deep",
     "pbx_test_zarr_plan", "pbx_planes_register_tiff", "pbx_test_tiff_plan",
-    "pbx_band_write_tiff", "pbx_test_tiff_band_plan",
+    "pbx_band_write_tiff", "pbx_test_tiff_band_plan", "pbx_planes_register_tiff_samples",
+    "pbx_band_write_tiff_sample", "pbx_test_tiff_plan_samples",
 ]
 
 _lib = None
@@ -263,6 +264,14 @@ def lib() -> ctypes.CDLL:
                                       ctypes.POINTER(ctypes.c_double)]
     L.pbx_test_tiff_band_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, i32,
                                           ctypes.POINTER(u64)]
+    L.pbx_planes_register_tiff_samples.argtypes = [vp, u64, ctypes.POINTER(PbxPlaneDesc),
+                                                   ctypes.POINTER(PbxZarrSlice), u64,
+                                                   ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(i32),
+                                                   ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double)]
+    L.pbx_band_write_tiff_sample.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxTiffSegments), i32, i32,
+                                             ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_tiff_plan_samples.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, i32, i32,
+                                             ctypes.POINTER(u64)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -754,11 +763,11 @@ TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
 _TIFF_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4,
                    16: 8, 17: 8, 18: 8}
 _TIFF_INT_FMT = {1: "B", 3: "H", 4: "I", 13: "I", 16: "Q", 18: "Q", 6: "b", 8: "h", 9: "i", 17: "q"}
-_TIFF_TAGS = {256: "width", 257: "length", 258: "bits", 259: "compression", 266: "fillorder",
-              270: "description", 273: "strip_offsets", 274: "orientation", 277: "spp",
-              278: "rows_per_strip", 279: "strip_counts", 317: "predictor", 322: "tile_w",
+_TIFF_TAGS = {256: "width", 257: "length", 258: "bits", 259: "compression", 262: "photometric",
+              266: "fillorder", 270: "description", 273: "strip_offsets", 274: "orientation", 277: "spp",
+              278: "rows_per_strip", 279: "strip_counts", 284: "planar", 317: "predictor", 322: "tile_w",
               323: "tile_h", 324: "tile_offsets", 325: "tile_counts", 330: "subifd_offsets",
-              339: "sampleformat"}
+              338: "extrasamples", 339: "sampleformat"}
 _TIFF_MAX_IFDS = 1 << 16
 _TIFF_PIXEL_TYPES = {(1, 8): UINT8, (2, 8): INT8, (1, 16): UINT16, (2, 16): INT16, (1, 32): UINT32,
                      (2, 32): INT32, (3, 32): FLOAT, (3, 64): DOUBLE}
@@ -767,7 +776,9 @@ _TIFF_PIXEL_TYPES = {(1, 8): UINT8, (2, 8): INT8, (1, 16): UINT16, (2, 16): INT1
 def tiff_ifds(path: str) -> List[dict]:
     """The IFD chain of a classic TIFF or BigTIFF file (II or MM), SubIFDs (tag 330) included,
     without any pixel data.  One dict per main IFD: width, length, bits (BitsPerSample),
-    sampleformat, spp (SamplesPerPixel), compression, predictor, fillorder, orientation, tiled,
+    sampleformat, spp (SamplesPerPixel), bits_count / sampleformat_count (how many values those
+    two tags hold; 1 if absent), planar (PlanarConfiguration, default 1), photometric (None if
+    absent), extrasamples (a list), compression, predictor, fillorder, orientation, tiled,
     seg_w x seg_h (TileWidth x TileLength, or ImageWidth x RowsPerStrip capped at the length),
     offsets / counts of the segments, description (ImageDescription or None), byteorder ("<" or
     ">"), bigtiff, subifds (such dicts).  Every offset and count is checked against the file
@@ -849,7 +860,12 @@ def tiff_ifds(path: str) -> List[dict]:
                        sampleformat=one("sampleformat", 1), spp=one("spp", 1),
                        compression=one("compression", 1), predictor=one("predictor", 1),
                        fillorder=one("fillorder", 1), orientation=one("orientation", 1),
-                       description=d.get("description"), byteorder=bo, bigtiff=big)
+                       description=d.get("description"), byteorder=bo, bigtiff=big,
+                       planar=one("planar", 1),
+                       photometric=one("photometric") if "photometric" in d else None,
+                       extrasamples=list(d.get("extrasamples", [])),
+                       bits_count=len(d["bits"]) if "bits" in d else 1,
+                       sampleformat_count=len(d["sampleformat"]) if "sampleformat" in d else 1)
             if out["width"] < 1 or out["length"] < 1:
                 raise PbxError(400, "%s: image of %d x %d" % (path, out["width"], out["length"]))
             if "tile_offsets" in d:
@@ -883,11 +899,23 @@ def tiff_ifds(path: str) -> List[dict]:
 
 
 def _tiff_pixel_type(path: str, ifd: dict) -> int:
-    """The pixel type of an IFD this library can load, else PbxError 400 with the reason."""
-    if ifd["spp"] != 1:
-        raise PbxError(400, "%s: SamplesPerPixel %d (only 1 is supported)" % (path, ifd["spp"]))
+    """The pixel type of an IFD this library can load, else PbxError 400 with the reason.
+    SamplesPerPixel 1 to 4: every sample is a channel of that type, ExtraSamples included."""
+    spp = ifd["spp"]
+    if spp < 1 or spp > 4:
+        raise PbxError(400, "%s: SamplesPerPixel %d (1 to 4 are supported)" % (path, spp))
+    if spp > 1 and ifd.get("bits_count", 1) != spp:  # TIFF 6.0: one BitsPerSample value per sample
+        raise PbxError(400, "%s: SamplesPerPixel %d with %d BitsPerSample value(s)"
+                       % (path, spp, ifd.get("bits_count", 1)))
+    if spp > 1 and ifd.get("photometric") not in (None, 1, 2):
+        raise PbxError(400, "%s: PhotometricInterpretation %d with SamplesPerPixel %d (1 BlackIsZero or 2 RGB; "
+                       "palette, CMYK and YCbCr are not supported)" % (path, ifd["photometric"], spp))
+    if ifd.get("planar", 1) not in (1, 2):
+        raise PbxError(400, "%s: PlanarConfiguration %d (1 chunky or 2 planar)" % (path, ifd["planar"]))
     if ifd["bits"] not in (8, 16, 32, 64):
         raise PbxError(400, "%s: BitsPerSample %d (8, 16, 32 or 64)" % (path, ifd["bits"]))
+    if spp > 1 and ifd["bits"] == 64:
+        raise PbxError(400, "%s: SamplesPerPixel %d with 64-bit samples" % (path, spp))
     pt = _TIFF_PIXEL_TYPES.get((ifd["sampleformat"], ifd["bits"]))
     if pt is None:
         raise PbxError(400, "%s: SampleFormat %d with %d bits is none of the pixel types"
@@ -906,25 +934,38 @@ def _tiff_pixel_type(path: str, ifd: dict) -> int:
     return pt
 
 
-def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int, level: int = 0) -> dict:
-    """register_tiff_planes() arguments for the plane one IFD (a tiff_ifds() dict, main or
-    SubIFD) holds: its segments are read from the file as they are, nothing is decoded here.
-    PbxError 400 names what is not supported."""
-    return dict(_tiff_segment_rows(path, ifd, 0, None), image_id=image_id, z=z, c=c, t=t, level=level)
+def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int, level: int = 0,
+                    sample: int = 0) -> dict:
+    """register_tiff_planes() arguments for the plane that is sample `sample` of one IFD (a
+    tiff_ifds() dict, main or SubIFD): its segments are read from the file as they are, nothing
+    is decoded here.  A chunky IFD (PlanarConfiguration 1) of S samples per pixel gives
+    samples_per_pixel = S and all its segments, each holding all S samples; a planar one
+    (PlanarConfiguration 2) an ordinary single-sample spec (samples_per_pixel = 1, sample = 0)
+    of the segments of its group `sample`.  PbxError 400 names what is not supported."""
+    return dict(_tiff_segment_rows(path, ifd, 0, None, sample), image_id=image_id, z=z, c=c, t=t, level=level)
 
 
-def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int]) -> dict:
+def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sample: int = 0) -> dict:
     """What tiff_plane_spec and tiff_band_spec share: the IFD's pixel type, geometry and byte
     order, and segments = (data, offsets) of its segment rows [sr0, sr1) (sr1 None: to the last;
     sr1 == sr0: none, segments is None and the file is not opened), each full width, read from
-    the file as they are."""
+    the file as they are.  A planar IFD holds spp groups of gx * gy segments, one per sample:
+    the rows are those of group `sample`."""
     import numpy as np
     pt = _tiff_pixel_type(path, ifd)
+    spp = ifd["spp"]
+    if not 0 <= sample < spp:
+        raise PbxError(400, "%s: sample %d outside SamplesPerPixel %d" % (path, sample, spp))
+    planar = spp > 1 and ifd.get("planar", 1) == 2
     gx = -(-ifd["width"] // ifd["seg_w"]) if ifd["tiled"] else 1
     gy = -(-ifd["length"] // ifd["seg_h"])
-    if len(ifd["offsets"]) != gx * gy:
+    if planar and len(ifd["offsets"]) != spp * gx * gy:
+        raise PbxError(400, "%s: %d segments for %d planar samples on a grid of %d x %d"
+                       % (path, len(ifd["offsets"]), spp, gx, gy))
+    if not planar and len(ifd["offsets"]) != gx * gy:
         raise PbxError(400, "%s: %d segments for a grid of %d x %d" % (path, len(ifd["offsets"]), gx, gy))
-    k0, k1 = sr0 * gx, (gy if sr1 is None else sr1) * gx
+    base = sample * gx * gy if planar else 0
+    k0, k1 = base + sr0 * gx, base + (gy if sr1 is None else sr1) * gx
     segments = None
     if k1 > k0:
         offsets = np.zeros(k1 - k0 + 1, dtype=np.uint64)
@@ -936,16 +977,17 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int]) -> di
                 if f.readinto(memoryview(data)[int(offsets[k]):int(offsets[k]) + n]) != n:
                     raise PbxError(400, "%s: segment %d is truncated" % (path, k0 + k))
         segments = (data, offsets)
-    return dict(pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
+    return dict(samples_per_pixel=1 if planar else spp, sample=0 if planar else sample, pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
                 big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"], seg_h=ifd["seg_h"],
                 tiled=ifd["tiled"],
                 compression=TIFF_DEFLATE if ifd["compression"] == 32946 else ifd["compression"],
                 predictor=ifd["predictor"], segments=segments)
 
 
-def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int) -> dict:
-    """band_write_tiff() arguments for rows [y0, y0 + rows) of the plane one IFD (a tiff_ifds()
-    dict, main or SubIFD) holds: pixel_type, size_x, size_y, big_endian (the file's byte order),
+def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0) -> dict:
+    """band_write_tiff() arguments for rows [y0, y0 + rows) of the plane that is sample `sample`
+    of one IFD (a tiff_ifds() dict, main or SubIFD; samples_per_pixel and sample as
+    tiff_plane_spec, and of a planar IFD only that sample's segments are read): pixel_type, size_x, size_y, big_endian (the file's byte order),
     seg_w, seg_h, tiled, compression, predictor and segments = (data, offsets) of the segment
     rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 only, each full width; exactly those byte
     ranges of the file are read.  rows == 0 reads nothing (segments is None): the geometry and
@@ -954,12 +996,14 @@ def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int) -> dict:
         raise PbxError(400, "%s: rows %d+%d outside the image (%d rows)" % (path, y0, rows, ifd["length"]))
     sr0 = y0 // ifd["seg_h"]
     sr1 = -(-(y0 + rows) // ifd["seg_h"]) if rows else sr0
-    return dict(_tiff_segment_rows(path, ifd, sr0, sr1), y0=y0, rows=rows)
+    return dict(_tiff_segment_rows(path, ifd, sr0, sr1, sample), y0=y0, rows=rows)
 
 
-def _ome_layout(path: str, xml: str) -> Optional[dict]:
+def _ome_layout(path: str, xml: str, samples: int = 1) -> Optional[dict]:
     """SizeZ/C/T, DimensionOrder and Type of the first Image of an OME-XML ImageDescription (None
-    if the description is not OME-XML).  400 for what register_tiff_image cannot follow."""
+    if the description is not OME-XML).  400 for what register_tiff_image cannot follow.  With
+    `samples` = S samples per pixel in every IFD, the IFDs run over SizeC / S channel groups in
+    DimensionOrder: planes[k] is the (z, c0, t) of IFD k's first sample, c0 a multiple of S."""
     if "<OME" not in xml[:4096]:
         return None
     import xml.etree.ElementTree as ET
@@ -989,14 +1033,25 @@ def _ome_layout(path: str, xml: str) -> Optional[dict]:
         raise PbxError(400, "%s: OME-XML pixel Type %r" % (path, typ))
     if min(sz, sc, st) < 1:
         raise PbxError(400, "%s: OME-XML SizeZ/C/T %d/%d/%d" % (path, sz, sc, st))
-    ext = {"Z": sz, "C": sc, "T": st}
+    for ch in (el for el in px[0] if local(el) == "Channel"):
+        try:
+            cs = int(ch.attrib.get("SamplesPerPixel", 1))
+        except ValueError as e:
+            raise PbxError(400, "%s: OME-XML Channel attribute %s" % (path, e))
+        if cs != samples:
+            raise PbxError(400, "%s: OME-XML Channel with SamplesPerPixel %d, the first IFD has %d"
+                           % (path, cs, samples))
+    if sc % samples:
+        raise PbxError(400, "%s: OME-XML SizeC %d is no multiple of the IFDs' SamplesPerPixel %d"
+                       % (path, sc, samples))
+    ext = {"Z": sz, "C": sc // samples, "T": st}
     planes = []
-    for k in range(sz * sc * st):
+    for k in range(sz * (sc // samples) * st):
         idx, r = {}, k
         for ax in order[2:]:
             idx[ax] = r % ext[ax]
             r //= ext[ax]
-        planes.append((idx["Z"], idx["C"], idx["T"]))
+        planes.append((idx["Z"], idx["C"] * samples, idx["T"]))
     at = {p: k for k, p in enumerate(planes)}
     for td in (el for el in px[0] if local(el) == "TiffData"):
         for u in (el for el in td if local(el) == "UUID"):
@@ -1018,13 +1073,16 @@ def _ome_layout(path: str, xml: str) -> Optional[dict]:
 
 def tiff_image_layout(path: str) -> dict:
     """What register_tiff_image and TiffSource make of a file: ifds (tiff_ifds), planes = the
-    (z, c, t) of main IFD k, size_z / size_c / size_t, pixel_type, levels (1 + SubIFDs per main
-    IFD).  OME-TIFF: the first Image's SizeZ/C/T and DimensionOrder, IFD k = plane k in that
-    order.  Any other multi-page TIFF: page k is t = k (Bio-Formats' BaseTiffReader puts the
-    pages of a plain TIFF on the time axis)."""
+    (z, c, t) of main IFD k's first sample, samples = S (SamplesPerPixel, the same in every IFD),
+    size_z / size_c / size_t, pixel_type, levels (1 + SubIFDs per main IFD).  Every sample is a
+    channel, ExtraSamples included: channel c lies in the IFD of (z, c - c % S, t) as sample
+    c % S.  OME-TIFF: the first Image's SizeZ/C/T and DimensionOrder, IFD k = channel group k in
+    that order.  Any other multi-page TIFF: page k is t = k and size_c = S (Bio-Formats'
+    BaseTiffReader puts the pages of a plain TIFF on the time axis)."""
     ifds = tiff_ifds(path)
     pt = _tiff_pixel_type(path, ifds[0])
-    ome = _ome_layout(path, ifds[0]["description"]) if ifds[0]["description"] else None
+    S = ifds[0]["spp"]
+    ome = _ome_layout(path, ifds[0]["description"], S) if ifds[0]["description"] else None
     if ome is not None:
         n = len(ome["planes"])
         if len(ifds) < n:
@@ -1033,12 +1091,16 @@ def tiff_image_layout(path: str) -> dict:
             raise PbxError(400, "%s: OME-XML Pixels disagree with the first IFD on type or size" % path)
         out = dict(ome, ifds=ifds[:n])
     else:
-        out = dict(size_z=1, size_c=1, size_t=len(ifds), planes=[(0, 0, k) for k in range(len(ifds))],
+        out = dict(size_z=1, size_c=S, size_t=len(ifds), planes=[(0, 0, k) for k in range(len(ifds))],
                    pixel_type=pt, ifds=ifds)
+    out["samples"] = S
     first = out["ifds"][0]
     for k, d in enumerate(out["ifds"]):
         if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d) != pt:
             raise PbxError(400, "%s: IFD %d differs from the first in size or pixel type" % (path, k))
+        for sd in [d] + d["subifds"]:
+            if sd["spp"] != S:
+                raise PbxError(400, "%s: IFD %d has SamplesPerPixel %d, the first has %d" % (path, k, sd["spp"], S))
         if len(d["subifds"]) != len(first["subifds"]):
             raise PbxError(400, "%s: IFD %d has %d SubIFDs, the first has %d" % (path, k, len(d["subifds"]),
                                                                                 len(first["subifds"])))
@@ -1362,8 +1424,13 @@ class PixelsService:
         (pbx_planes_register_tiff): each dict (tiff_plane_spec) holds image_id, z, c, t,
         pixel_type, size_x, size_y, seg_w, seg_h, tiled, compression (1 none, 5 LZW, 8 deflate),
         predictor (1 or 2), segments (a sequence of bytes in C order over the grid, or
-        pack_chunks()' (data, offsets) pair) [, big_endian = the FILE's byte order, level].  All are
+        pack_chunks()' (data, offsets) pair) [, big_endian = the FILE's byte order, level,
+        samples_per_pixel, sample].  Specs with samples_per_pixel > 1 (chunky segments of that many
+        interleaved samples per pixel) that carry the SAME segments object are the samples of one
+        layer, uploaded and decoded once (pbx_planes_register_tiff_samples).  All are
         registered or none.  Returns the plane ids (and the kernels' device ms with timing=True)."""
+        if any(p.get("samples_per_pixel", 1) != 1 for p in planes):
+            return self._register_tiff_samples(planes, timing)
         n = len(planes)
         descs = (PbxPlaneDesc * n)()
         sgs = (PbxTiffSegments * n)()
@@ -1387,18 +1454,73 @@ class PixelsService:
         del keep
         return (list(ids), (ms[0], ms[1])) if timing else list(ids)
 
+    def _register_tiff_samples(self, planes: Sequence[dict], timing: bool):
+        n = len(planes)
+        descs = (PbxPlaneDesc * n)()
+        rf = (PbxZarrSlice * n)()
+        layer_of: Dict[int, int] = {}
+        layers: List[dict] = []
+        for k, p in enumerate(planes):
+            spp, sample = p.get("samples_per_pixel", 1), p.get("sample", 0)
+            l = layer_of.get(id(p["segments"])) if spp > 1 else None
+            if l is None:
+                l = len(layers)
+                layers.append(p)
+                if spp > 1:
+                    layer_of[id(p["segments"])] = l
+            elif any(layers[l].get(f) != p.get(f) for f in ("samples_per_pixel", "seg_w", "seg_h", "tiled",
+                                                             "compression", "predictor")):
+                raise PbxError(400, "plane %d: shares its segments with plane %d but not their layout"
+                               % (k, planes.index(layers[l])))
+            if not (0 <= sample < 2 ** 32):
+                raise PbxError(400, "plane %d: bad sample %r" % (k, sample))
+            d = descs[k]
+            d.image_id, d.z, d.c, d.t = p["image_id"], p["z"], p["c"], p["t"]
+            d.resolution = p.get("level", 0)
+            d.pixel_type, d.size_x, d.size_y = p["pixel_type"], p["size_x"], p["size_y"]
+            d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
+            rf[k].layer, rf[k].slice = l, sample
+        nl = len(layers)
+        sgs = (PbxTiffSegments * nl)()
+        spps = (ctypes.c_int32 * nl)()
+        keep = []
+        for l, p in enumerate(layers):
+            seg = p["segments"]
+            data, offsets = seg if isinstance(seg, tuple) else pack_chunks(seg)
+            keep += [offsets, data]
+            s = sgs[l]
+            s.seg_w, s.seg_h, s.tiled = p["seg_w"], p["seg_h"], 1 if p["tiled"] else 0
+            s.compression, s.predictor, s.flags = p["compression"], p.get("predictor", 1), p.get("flags", 0)
+            s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
+            spps[l] = p.get("samples_per_pixel", 1)
+        ids = (ctypes.c_uint64 * n)()
+        ms = (ctypes.c_double * 2)()
+        _check(lib().pbx_planes_register_tiff_samples(self._h, n, descs, rf, nl, sgs, spps, ids, ms))
+        del keep
+        return (list(ids), (ms[0], ms[1])) if timing else list(ids)
+
     def register_tiff_image(self, path: str, image_id: int) -> Dict[int, Dict[Tuple[int, int, int], int]]:
         """A whole TIFF / OME-TIFF file -- what the ordinary PixelsService opens through
         Bio-Formats for an image without an NGFF fileset (config.yaml:18) -- in ONE set of GPU
         launches: every plane of every level (tiff_image_layout: OME-XML axes, or page k = t;
-        each main IFD's SubIFDs are stored levels 1, 2, ... of its plane).  All are registered,
-        or none.  Returns {level: {(z, c, t): plane id}}, as register_ngff_image."""
+        each main IFD's SubIFDs are stored levels 1, 2, ... of its plane).  An IFD of S samples
+        per pixel gives the S channels c .. c + S - 1: a chunky one is one layer, read and
+        decoded once and split into its S planes on the GPU; a planar one S single-sample
+        planes.  All are registered, or none.  Returns {level: {(z, c, t): plane id}}, as
+        register_ngff_image."""
         lay = tiff_image_layout(path)
         specs, keys = [], []
         for (z, c, t), ifd in zip(lay["planes"], lay["ifds"]):
             for k, d in enumerate([ifd] + ifd["subifds"]):
-                specs.append(tiff_plane_spec(path, d, image_id, z, c, t, k))
-                keys.append((k, (z, c, t)))
+                first = tiff_plane_spec(path, d, image_id, z, c, t, k)
+                for s in range(lay["samples"]):
+                    if s == 0:
+                        specs.append(first)
+                    elif first["samples_per_pixel"] > 1:  # chunky: the same segments object, one layer
+                        specs.append(dict(first, c=c + s, sample=s))
+                    else:  # planar: the sample's own segments
+                        specs.append(tiff_plane_spec(path, d, image_id, z, c + s, t, k, sample=s))
+                    keys.append((k, (z, c + s, t)))
         ids = self.register_tiff_planes(specs)
         out: Dict[int, Dict[Tuple[int, int, int], int]] = {}
         for (k, p), pid in zip(keys, ids):
@@ -1530,12 +1652,15 @@ class PixelsService:
         return (ms[0], ms[1]) if timing else None
 
     def band_write_tiff(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
-                        compression: int, predictor: int, segments, timing: bool = False):
+                        compression: int, predictor: int, segments, timing: bool = False,
+                        samples_per_pixel: int = 1, sample: int = 0):
         """pbx_band_write_tiff: rows [y0, y0 + rows) of one band, decoded on the GPU from the TIFF
         segment rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 that cover them (strips, or
         rows of tiles at full width, C order: a sequence of bytes, or pack_chunks()' (data,
         offsets) pair, as tiff_band_spec returns).  compression and predictor as
         register_tiff_planes; the sparse plane must have been created in the file's byte order.
+        With samples_per_pixel > 1 the segments are chunky and hold that many interleaved samples
+        per pixel, of which only `sample` is written (pbx_band_write_tiff_sample).
         With timing=True returns the decoders' and the placement's device ms."""
         data, offsets = segments if isinstance(segments, tuple) else pack_chunks(segments)
         s = PbxTiffSegments()
@@ -1543,7 +1668,11 @@ class PixelsService:
         s.compression, s.predictor, s.flags = compression, predictor, 0
         s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
         ms = (ctypes.c_double * 2)()
-        _check(lib().pbx_band_write_tiff(self._h, plane_id, y0, rows, ctypes.byref(s), ms))
+        if samples_per_pixel == 1 and sample == 0:
+            _check(lib().pbx_band_write_tiff(self._h, plane_id, y0, rows, ctypes.byref(s), ms))
+        else:
+            _check(lib().pbx_band_write_tiff_sample(self._h, plane_id, y0, rows, ctypes.byref(s),
+                                                    samples_per_pixel, sample, ms))
         return [ms[0], ms[1]] if timing else None
 
     def band_abort(self, plane_id: int, y0: int) -> None:
@@ -1700,7 +1829,9 @@ class PixelsService:
                             if tsp is not None:
                                 self.band_write_tiff(pid, r0, r1 - r0, tsp["seg_w"], tsp["seg_h"],
                                                      tsp["tiled"], tsp["compression"], tsp["predictor"],
-                                                     tsp["segments"])
+                                                     tsp["segments"],
+                                                     samples_per_pixel=tsp.get("samples_per_pixel", 1),
+                                                     sample=tsp.get("sample", 0))
                             elif sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
@@ -2145,22 +2276,28 @@ class TiffSource(PixelSource):
         return Pixels(image_id, lay["pixel_type"], lay["ifds"][0]["width"], lay["ifds"][0]["length"],
                       lay["size_z"], lay["size_c"], lay["size_t"], levels=lay["levels"])
 
-    def _ifd(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> dict:
+    def _ifd(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Tuple[dict, int]:
+        """(the IFD that holds channel c, c's sample in it): channel c of a file with S samples
+        per pixel is sample c % S of the IFD of (z, c - c % S, t)."""
         lay = self._open(pixels.image_id)
-        ifd = lay["ifds"][lay["planes"].index((z, c, t))]
-        return ifd if level == 0 else ifd["subifds"][level - 1]
+        sample = c % lay["samples"]
+        ifd = lay["ifds"][lay["planes"].index((z, c - sample, t))]
+        return (ifd if level == 0 else ifd["subifds"][level - 1]), sample
 
     def level_size(self, pixels: Pixels, level: int) -> Tuple[int, int]:
-        d = self._ifd(pixels, 0, 0, 0, level)
+        d = self._ifd(pixels, 0, 0, 0, level)[0]
         return d["width"], d["length"]
 
     def plane_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Optional[dict]:
-        return tiff_plane_spec(self.images[pixels.image_id], self._ifd(pixels, z, c, t, level),
-                               pixels.image_id, z, c, t, level)
+        ifd, sample = self._ifd(pixels, z, c, t, level)
+        return tiff_plane_spec(self.images[pixels.image_id], ifd, pixels.image_id, z, c, t, level, sample=sample)
 
     def band_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
                       rows: int) -> Optional[dict]:
-        return tiff_band_spec(self.images[pixels.image_id], self._ifd(pixels, z, c, t, level), y0, rows)
+        ifd, sample = self._ifd(pixels, z, c, t, level)
+        path = self.images[pixels.image_id]
+        # (sample 0 -- every single-sample file -- is the call it always was)
+        return tiff_band_spec(path, ifd, y0, rows) if sample == 0 else tiff_band_spec(path, ifd, y0, rows, sample=sample)
 
     def read_rows(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
                   rows: int) -> bytes:
