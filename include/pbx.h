@@ -364,25 +364,38 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  *   LZW      TIFF 6.0 section 13 (MSB-first codes, "early change"), k_tiff_lzw, one wave a segment;
  *   DEFLATE  zlib streams (compression 8, and 32946 which the caller maps to 8), k_zarr_inflate2,
  *            Adler-32 checked;
+ *   ZSTD     one Zstandard frame a segment (compression 50000: libtiff >= 4.0.10, tifffile, GDAL),
+ *            k_zarr_zstd; the frame's header and block headers are checked on the host first (no
+ *            dictionary id, no skippable frame, nothing after the frame, a content size -- if the
+ *            frame carries one -- equal to the segment's decoded bytes), its content checksum and
+ *            decoded length on the device;
  * then Predictor = 2 (horizontal differencing over whole samples in the file's byte order) is
  * undone per segment row (k_tiff_unpred) and k_zarr_place puts the segments into the plane.
+ * Predictor = 3, the floating-point predictor (Adobe TIFF Technical Note 3), is accepted on float
+ * and double planes of one sample per pixel, behind every compression: a segment row is stored
+ * as byte planes (most significant bytes first in II and MM files alike) differenced byte by byte
+ * over the whole row, and k_tiff_fpunpred_place undoes the differences, interleaves the planes
+ * into samples in the file's byte order and places them, at registration and in band writes
+ * alike (no k_tiff_unpred, no k_zarr_place; stored segments are read where they were uploaded).
  * pbx_band_write_tiff loads a sparse plane band by band from the segment rows a band covers.
  * Files with 2 .. 4 samples per pixel (RGB, RGBA) give one plane per sample: chunky segments
  * (PlanarConfiguration 1) through pbx_planes_register_tiff_samples / pbx_band_write_tiff_sample,
  * which split them on the GPU (k_tiff_split_place); planar ones (PlanarConfiguration 2) are
  * single-sample segments already and go through the calls below.
- * Not supported (400 by the caller or here): SamplesPerPixel > 4, Predictor 3, FillOrder 2,
- * pre-6.0 (LSB-first) LZW streams, JPEG / PackBits / other compressions, YCbCr / CMYK / palette
+ * Not supported (400 by the caller or here): SamplesPerPixel > 4, Predictor 3 on integer or
+ * chunky multi-sample (RGB float) data, half-precision samples, FillOrder 2, pre-6.0 (LSB-first)
+ * LZW streams, JPEG / PackBits / LZMA / LERC / WebP and other compressions, YCbCr / CMYK / palette
  * colour, sub-byte or 12-bit samples.
  * The JNI shim does not wrap these calls (as the deep Zarr calls). */
-enum pbx_tiff_compression { PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8 };
+enum pbx_tiff_compression { PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8, PBX_TIFF_ZSTD = 50000 };
 typedef struct pbx_tiff_segments {
     int32_t seg_w, seg_h;       /* tiles: TileWidth x TileLength (edge tiles are full, padded);
                                    strips: ImageWidth x RowsPerStrip (the last strip holds only
                                    the rows left) */
     int32_t tiled;              /* 0 strips, else tiles */
     int32_t compression;        /* enum pbx_tiff_compression */
-    int32_t predictor;          /* 1 none, 2 horizontal differencing (integer samples only) */
+    int32_t predictor;          /* 1 none, 2 horizontal differencing (integer samples only),
+                                   3 floating-point (float / double planes, one sample a pixel) */
     int32_t flags;              /* 0 */
     const uint8_t* data;        /* the segments' bytes, concatenated in C order over the grid */
     const uint64_t* offsets;    /* gx * gy + 1 offsets into data (as pbx_zarr_chunks); a strip
@@ -393,11 +406,13 @@ typedef struct pbx_tiff_segments {
  * order (II little, MM big): the plane keeps it, nothing is swapped at load time.
  * 400 on the host for: null pointers, offsets that decrease, an empty segment (TIFF has no missing
  * chunk), seg_w / seg_h < 1, tiles whose width or length is not a multiple of 16 (TIFF 6.0
- * section 15), a strip width != size_x, a compression outside {1, 5, 8}, a predictor outside
- * {1, 2} or predictor 2 on float / double, flags != 0, an uncompressed segment whose length is not
+ * section 15), a strip width != size_x, a compression outside {1, 5, 8, 50000}, a predictor
+ * outside {1, 2, 3}, predictor 2 on float / double, predictor 3 on anything but a float / double
+ * plane of one sample per pixel ("bad predictor 3 ..."), a zstd segment that is not exactly one
+ * frame decoding to the segment's bytes, flags != 0, an uncompressed segment whose length is not
  * its rows' bytes, an old-style LZW stream (first byte 0 and bit 0 of the second set: libtiff's
  * test).  A stream the device rejects (bad LZW code, fewer bytes than the segment holds, bad
- * deflate data or Adler-32) is 400 and nothing is registered.  A missing LZW EOI is accepted, as
+ * deflate data or Adler-32, corrupt zstd data or content checksum) is 400 and nothing is registered.  A missing LZW EOI is accepted, as
  * libtiff accepts it.  kernel_ms (may be NULL): [0] decoders + un-predictor, [1] placement. */
 int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
                              const pbx_tiff_segments* segs, uint64_t* plane_ids, double* kernel_ms);
@@ -711,7 +726,9 @@ int pbx_test_zarr_plan(const pbx_zarr_chunks* chunks, int32_t size_x, int32_t si
 /* Test hook: the host planner of pbx_planes_register_tiff alone (no context, no device call) for
  * a plane of size_x x size_y samples of bpp bytes.  out: streams planned, the sum of their decoded
  * lengths (every segment's own rows: a short last strip counts its rows, an edge tile is full),
- * scratch bytes, 1 if the un-predictor launch is needed.  400 as the real call. */
+ * scratch bytes, 1 if the un-predictor launch is needed.  With Predictor = 3 (bpp 4 or 8 only)
+ * out[3] is instead the number of segments handed to k_tiff_fpunpred_place, and stored segments
+ * plan no stream and no scratch.  400 as the real call. */
 int pbx_test_tiff_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
                        uint64_t out[4]);
 
@@ -719,7 +736,8 @@ int pbx_test_tiff_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t si
  * [y0, y0 + rows) of a plane of size_x x size_y samples of bpp bytes; segs holds the covering
  * segment rows only.  out: streams handed to a decoder (LZW and deflate; stored segments count
  * 0), the sum of the decoded lengths of every covered segment, scratch bytes, 1 if the fused
- * un-predict-and-place kernel is launched.  400 as the real call, and for rows < 1 or rows
+ * un-predict-and-place kernel is launched (with Predictor = 3: the number of segments handed to
+ * k_tiff_fpunpred_place).  400 as the real call, and for rows < 1 or rows
  * outside the plane. */
 int pbx_test_tiff_band_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
                             int32_t y0, int32_t rows, uint64_t out[4]);
@@ -731,8 +749,8 @@ int pbx_test_tiff_band_plan(const pbx_tiff_segments* segs, int32_t size_x, int32
  * decoder (stored multi-sample segments count 0: they are read where they were uploaded), the sum
  * of the decoded lengths of every segment planned (samples_per_pixel times the single-sample
  * figure), scratch bytes, and the number of segments handed to k_tiff_split_place (for
- * samples_per_pixel == 1: out[3] of pbx_test_tiff_plan / pbx_test_tiff_band_plan).  400 as the real
- * calls. */
+ * samples_per_pixel == 1: out[3] of pbx_test_tiff_plan / pbx_test_tiff_band_plan, Predictor = 3
+ * included).  400 as the real calls. */
 int pbx_test_tiff_plan_samples(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
                                int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[4]);
 

@@ -11,7 +11,12 @@
 //   k_tiff_split_place    chunky segments of 2 .. 4 samples per pixel (RGB, RGBA): the sums with
 //                   a stride of S samples and the S interleaved components scattered into S
 //                   pitched planes, in one pass (registration and band writes alike)
+//   k_tiff_fpunpred_place float and double segments stored with Predictor = 3 (the floating-point
+//                   predictor): byte planes summed across their boundaries, interleaved into
+//                   samples and stored into the pitched plane, in one pass (registration and
+//                   band writes alike)
 //
+// Zstandard segments (Compression = 50000) go through k_zarr_zstd (kernels_zstd.hip).
 // Deflate segments go through k_zarr_inflate2 and stored ones through k_zarr_copy; every kind
 // is placed by k_zarr_place (kernels_zarr.hip).  A band write reads stored segments where they
 // were uploaded, and with Predictor = 2 k_tiff_unpred_place stands in for k_tiff_unpred +
@@ -415,6 +420,150 @@ __global__ __launch_bounds__(64 * UP_WAVES) void k_tiff_split_place(const TPlace
     }
 }
 
+// ------------------------------------ floating-point un-predictor and place (Predictor = 3)
+// Adobe TIFF Technical Note 3: a segment row of wc samples of BPP bytes is stored as BPP byte
+// planes of wc bytes each, most significant bytes first whatever the file's byte order, and the
+// row's BPP * wc bytes are differenced byte by byte straight across the plane boundaries.  Byte b
+// (0 = MSB) of sample i is therefore the running sum, modulo 256, of the row's bytes up to
+// b * wc + i: (the total of the planes before b) + (the prefix inside plane b up to i).
+// k_tiff_unpred_place's geometry and clipping.  A row is walked twice by its wave: the first
+// pass adds up the planes 0 .. BPP - 2 over the segment's whole width (an edge tile's padding is
+// differenced too and need not be zero), one wave reduction per plane; the second walks the
+// visible width only, 64 / BPP samples a lane a step: that many consecutive bytes from each of
+// the BPP planes (guarded loads: strips are unaligned), unpred_group<1> on each plane with the
+// plane's own carry, a 4 x 4 byte transpose with v_perm_b32 into whole samples in the file's
+// byte order, and 64 bytes a lane into the plane: four aligned 16-byte stores, or word by word
+// in the row's last, partial group.  A row of at most 256 visible samples (a 256 x 256 tile, the
+// usual one) would leave three lanes in four idle at 16 samples a lane: it is walked at four
+// samples a lane instead, one step, one or two 16-byte stores a lane.  No LDS, no scratch,
+// nothing rewritten in place.
+__device__ __forceinline__ void fp_transpose4(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t* o) {
+    // o[s] = [a.byte s, b.byte s, c.byte s, d.byte s]; perm(hi, lo, sel): bytes 0-3 of lo, 4-7 of hi
+    const uint32_t ab0 = __builtin_amdgcn_perm(b, a, 0x05010400u), ab1 = __builtin_amdgcn_perm(b, a, 0x07030602u);
+    const uint32_t cd0 = __builtin_amdgcn_perm(d, c, 0x05010400u), cd1 = __builtin_amdgcn_perm(d, c, 0x07030602u);
+    o[0] = __builtin_amdgcn_perm(cd0, ab0, 0x05040100u);
+    o[1] = __builtin_amdgcn_perm(cd0, ab0, 0x07060302u);
+    o[2] = __builtin_amdgcn_perm(cd1, ab1, 0x05040100u);
+    o[3] = __builtin_amdgcn_perm(cd1, ab1, 0x07060302u);
+}
+
+constexpr uint32_t FP_NARROW = 4;  // samples a lane a step where a row is at most 256 samples wide
+
+// the lane's `have` (0 .. G) bytes at p, the rest zero
+template <uint32_t G>
+__device__ __forceinline__ void fp_load(const uint8_t* p, uint32_t have, uint32_t (&wv)[4]) {
+    wv[0] = wv[1] = wv[2] = wv[3] = 0;
+    if (have == G) {
+        __builtin_memcpy(wv, p, G);
+    } else {
+#pragma unroll
+        for (uint32_t b = 0; b < G; b++)
+            if (b < have) wv[b >> 2] |= (uint32_t)p[b] << (8 * (b & 3));
+    }
+}
+
+// G: samples (bytes of every plane) a lane a step, 64 / BPP (64 bytes a lane out) or FP_NARROW
+template <uint32_t BPP, bool BE, uint32_t G>
+__device__ __forceinline__ void fp_place_row(const uint8_t* __restrict__ row, uint8_t* __restrict__ out,
+                                             uint32_t wc, uint32_t nvis, uint32_t lane) {
+    constexpr uint32_t PG = G == FP_NARROW ? 4 : 16;  // bytes a lane a step of the first pass
+    uint32_t carry[BPP];
+    carry[0] = 0;
+#pragma unroll
+    for (uint32_t b = 0; b + 1 < BPP; b++) {  // the total of plane b, padding included
+        uint32_t acc = 0;
+        for (uint32_t k0 = 0; k0 < wc; k0 += 64 * PG) {
+            const uint32_t off = k0 + PG * lane;
+            const uint32_t have = off >= wc ? 0u : wc - off < PG ? wc - off : PG;
+            uint32_t wv[4];
+            fp_load<PG>(row + (uint64_t)b * wc + off, have, wv);
+#pragma unroll
+            for (uint32_t j = 0; j < PG / 4; j++)
+                acc += (wv[j] & 0xffu) + ((wv[j] >> 8) & 0xffu) + ((wv[j] >> 16) & 0xffu) + (wv[j] >> 24);
+        }
+        carry[b + 1] = carry[b] + rdl(wave_incl_add(acc, lane), 63);
+    }
+    for (uint32_t k0 = 0; k0 < nvis; k0 += 64 * G) {
+        const uint32_t i0 = k0 + G * lane;
+        const uint32_t have = i0 >= nvis ? 0u : nvis - i0 < G ? nvis - i0 : G;  // samples
+        uint32_t pv[BPP][4];
+#pragma unroll
+        for (uint32_t b = 0; b < BPP; b++) {
+            uint32_t wv[4];
+            fp_load<G>(row + (uint64_t)b * wc + i0, have, wv);
+            unpred_group<1>(wv, false, lane, carry[b], pv[BE ? b : BPP - 1 - b]);  // in stored byte order
+        }
+        uint32_t ow[G * BPP / 4];
+#pragma unroll
+        for (uint32_t j = 0; j < G / 4; j++) {  // samples 4 j .. 4 j + 3
+            if (BPP == 4) {
+                fp_transpose4(pv[0][j], pv[1][j], pv[2][j], pv[3][j], ow + 4 * j);
+            } else {
+                uint32_t lo[4], hi[4];
+                fp_transpose4(pv[0][j], pv[1][j], pv[2][j], pv[3][j], lo);
+                fp_transpose4(pv[4 % BPP][j], pv[5 % BPP][j], pv[6 % BPP][j], pv[7 % BPP][j], hi);
+#pragma unroll
+                for (uint32_t s = 0; s < 4; s++) {
+                    ow[8 * j + 2 * s] = lo[s];
+                    ow[8 * j + 2 * s + 1] = hi[s];
+                }
+            }
+        }
+        uint8_t* o = out + (uint64_t)i0 * BPP;
+        if (have == G) {
+#pragma unroll
+            for (uint32_t q = 0; q < G * BPP / 16; q++)
+                *(uint4*)(o + 16 * q) = make_uint4(ow[4 * q], ow[4 * q + 1], ow[4 * q + 2], ow[4 * q + 3]);
+        } else {
+#pragma unroll
+            for (uint32_t q = 0; q < G * BPP / 4; q++)
+                if (4 * q < have * BPP) *(uint32_t*)(o + 4 * q) = ow[q];
+        }
+    }
+}
+
+template <uint32_t BPP, bool BE>
+__device__ __forceinline__ void fp_place_rows(const uint8_t* __restrict__ s, uint32_t rb, uint8_t* __restrict__ o,
+                                              int64_t pitch, int32_t r0, int32_t r1, uint32_t nvis, uint32_t lane,
+                                              uint32_t w) {
+    if (nvis <= 64 * FP_NARROW) {  // one step of four samples a lane covers the row
+        for (int32_t r = r0 + (int32_t)w; r < r1; r += (int32_t)UP_WAVES)
+            fp_place_row<BPP, BE, FP_NARROW>(s + (uint64_t)r * rb, o + (int64_t)r * pitch, rb / BPP, nvis, lane);
+    } else {
+        for (int32_t r = r0 + (int32_t)w; r < r1; r += (int32_t)UP_WAVES)
+            fp_place_row<BPP, BE, 64 / BPP>(s + (uint64_t)r * rb, o + (int64_t)r * pitch, rb / BPP, nvis, lane);
+    }
+}
+
+__global__ __launch_bounds__(64 * UP_WAVES) void k_tiff_fpunpred_place(const TPlace* __restrict__ sg,
+                                                                       const TPlaceDst* __restrict__ dt,
+                                                                       const uint8_t* __restrict__ scratch,
+                                                                       const uint8_t* __restrict__ input) {
+    const uint32_t lane = threadIdx.x & 63, w = rfl(threadIdx.x >> 6);
+    const TPlace u = sg[blockIdx.x];
+    const TPlaceDst d = dt[rfl(u.pad)];
+    const int32_t x0 = (int32_t)rfl((uint32_t)u.x0), y0 = (int32_t)rfl((uint32_t)u.y0);
+    const int32_t rows = (int32_t)rfl(u.rows);
+    const uint32_t rb = rfl(u.row_bytes), bpp = rfl(d.bpp);
+    // segment rows of this run that lie in the window and in the plane
+    int32_t r0 = (int32_t)(blockIdx.y * UP_ROWS), r1 = r0 + (int32_t)UP_ROWS;
+    const int32_t top = d.y_lo > 0 ? d.y_lo : 0, bottom = d.y_hi < d.sy ? d.y_hi : d.sy;
+    r1 = r1 < rows ? r1 : rows;
+    r0 = r0 > top - y0 ? r0 : top - y0;
+    r1 = r1 < bottom - y0 ? r1 : bottom - y0;
+    if (r0 >= r1 || x0 >= d.sx || (bpp != 4 && bpp != 8)) return;
+    const uint32_t wvis = (uint32_t)(d.sx - x0), wc = rb / bpp;
+    const uint32_t nvis = wvis < wc ? wvis : wc;  // visible samples of a row
+    const uint8_t* s = (rfl(u.from_input) ? input : scratch) + u.src;
+    uint8_t* o = d.dev + (int64_t)y0 * d.pitch + (int64_t)x0 * bpp;
+    switch (bpp * 2 + (rfl(d.big_endian) ? 1u : 0u)) {  // once per workgroup
+        case 8: fp_place_rows<4, false>(s, rb, o, d.pitch, r0, r1, nvis, lane, w); break;
+        case 9: fp_place_rows<4, true>(s, rb, o, d.pitch, r0, r1, nvis, lane, w); break;
+        case 16: fp_place_rows<8, false>(s, rb, o, d.pitch, r0, r1, nvis, lane, w); break;
+        default: fp_place_rows<8, true>(s, rb, o, d.pitch, r0, r1, nvis, lane, w); break;
+    }
+}
+
 hipError_t launch_tiff_lzw(hipStream_t st, const ZStream* d_streams, uint32_t n, const uint8_t* src,
                            uint8_t* scratch, uint32_t* err) {
     if (!n) return hipSuccess;
@@ -436,6 +585,14 @@ hipError_t launch_tiff_unpred_place(hipStream_t st, const TPlace* d_segs, uint32
     if (!n || !max_rows) return hipSuccess;
     hipLaunchKernelGGL(k_tiff_unpred_place, dim3(n, (max_rows + UP_ROWS - 1) / UP_ROWS), dim3(64 * UP_WAVES), 0, st,
                        d_segs, dst, scratch, input);
+    return hipGetLastError();
+}
+
+hipError_t launch_tiff_fpunpred_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
+                                      const TPlaceDst* d_dst, const uint8_t* scratch, const uint8_t* input) {
+    if (!n || !max_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tiff_fpunpred_place, dim3(n, (max_rows + UP_ROWS - 1) / UP_ROWS), dim3(64 * UP_WAVES), 0,
+                       st, d_segs, d_dst, scratch, input);
     return hipGetLastError();
 }
 

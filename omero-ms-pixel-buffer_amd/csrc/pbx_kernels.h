@@ -195,6 +195,7 @@ struct TPlace {
     int32_t x0, y0;      // its origin in the plane
     uint32_t from_input;
     uint32_t pad;        // k_tiff_split_place: the segment's entry in the launch's TSplitDst table
+                         // (k_tiff_fpunpred_place: in its TPlaceDst table)
 };
 static_assert(sizeof(TPlace) == 32, "TPlace is uploaded as is");
 struct TPlaceDst {       // passed by value
@@ -202,11 +203,20 @@ struct TPlaceDst {       // passed by value
     int64_t pitch;       // a multiple of 256
     int32_t sx, sy;      // plane size in samples
     int32_t y_lo, y_hi;  // plane rows that may be written
-    uint32_t bpp;        // 1, 2 or 4
+    uint32_t bpp;        // 1, 2 or 4 (k_tiff_fpunpred_place: 4 or 8)
     uint32_t big_endian;
 };
+static_assert(sizeof(TPlaceDst) == 40, "TPlaceDst is uploaded as is (k_tiff_fpunpred_place)");
 hipError_t launch_tiff_unpred_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
                                     const TPlaceDst& dst, const uint8_t* scratch, const uint8_t* input);
+// k_tiff_fpunpred_place (Predictor = 3 on float / double samples): TPlace::row_bytes = seg_w * bpp
+// bytes hold bpp byte planes of seg_w bytes, most significant first, differenced byte by byte
+// over the whole row.  The kernel undoes the differences, interleaves the planes into samples in
+// the destination's byte order and stores them, clipped as k_tiff_unpred_place clips.  d_dst is a
+// device table with one entry per layer of a registration (one for a band write), named by
+// TPlace::pad.
+hipError_t launch_tiff_fpunpred_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
+                                      const TPlaceDst* d_dst, const uint8_t* scratch, const uint8_t* input);
 // k_tiff_split_place (SamplesPerPixel 2 .. 4, PlanarConfiguration 1): a segment row holds spp
 // interleaved samples per pixel (TPlace::row_bytes = seg_w * bpp * spp).  The kernel undoes
 // Predictor = 2 with a stride of spp samples and stores component s of every pixel into plane

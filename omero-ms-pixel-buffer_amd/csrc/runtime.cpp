@@ -2340,6 +2340,14 @@ struct ZarrPlan {
     // segment's entry in the launch's TSplitDst table
     std::vector<TPlace> split;
     uint32_t split_rows = 0;      // the tallest of them
+    // TIFF segments stored with Predictor = 3 (float / double planes): every segment, registration
+    // and band writes alike, for k_tiff_fpunpred_place (then no `unpred`, no `uplace` and no
+    // `chunks`); TPlace::pad names the segment's entry in `fdst`, one per tiff_plan call, whose
+    // destination fields zarr_decode_place takes from the launch's ZPlane fdst_plane[entry]
+    std::vector<TPlace> fplace;
+    uint32_t fplace_rows = 0;     // the tallest of them
+    std::vector<TPlaceDst> fdst;
+    std::vector<uint32_t> fdst_plane;
 };
 
 // A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
@@ -2351,37 +2359,37 @@ struct ZarrWant {
 // One RFC 8878 frame in f[0 .. len) that must decode to cb bytes: the header, then the block
 // headers to the frame's end (no block is read).  A frame without a content size passes; the
 // decoder's length check decides.
-int zstd_frame_check(const uint8_t* f, uint64_t len, uint64_t cb, long long i) {
-    if (len < 6) return fail(PBX_E_BADARG, "chunk %lld: short zstd frame", i);
+int zstd_frame_check(const uint8_t* f, uint64_t len, uint64_t cb, long long i, const char* what = "chunk") {
+    if (len < 6) return fail(PBX_E_BADARG, "%s %lld: short zstd frame", what, i);
     const uint32_t magic = rd_le32(f);
-    if ((magic & 0xfffffff0u) == 0x184D2A50u) return fail(PBX_E_BADARG, "chunk %lld: skippable zstd frame", i);
-    if (magic != 0xFD2FB528u) return fail(PBX_E_BADARG, "chunk %lld: not a zstd frame", i);
+    if ((magic & 0xfffffff0u) == 0x184D2A50u) return fail(PBX_E_BADARG, "%s %lld: skippable zstd frame", what, i);
+    if (magic != 0xFD2FB528u) return fail(PBX_E_BADARG, "%s %lld: not a zstd frame", what, i);
     const uint32_t fhd = f[4], fcs_flag = fhd >> 6, single = (fhd >> 5) & 1;
-    if (fhd & 3) return fail(PBX_E_BADARG, "chunk %lld: zstd frame with a dictionary id", i);
-    if (fhd & 8) return fail(PBX_E_BADARG, "chunk %lld: reserved zstd frame header bit", i);
+    if (fhd & 3) return fail(PBX_E_BADARG, "%s %lld: zstd frame with a dictionary id", what, i);
+    if (fhd & 8) return fail(PBX_E_BADARG, "%s %lld: reserved zstd frame header bit", what, i);
     uint64_t q = 5 + (single ? 0 : 1);
     const uint32_t fcs_size = fcs_flag == 0 ? single : 1u << fcs_flag;
-    if (q + fcs_size > len) return fail(PBX_E_BADARG, "chunk %lld: short zstd frame", i);
+    if (q + fcs_size > len) return fail(PBX_E_BADARG, "%s %lld: short zstd frame", what, i);
     if (fcs_size) {
         uint64_t fcs = 0;
         for (uint32_t k = 0; k < fcs_size; k++) fcs |= (uint64_t)f[q + k] << (8 * k);
         if (fcs_size == 2) fcs += 256;
         if (fcs != cb)
-            return fail(PBX_E_BADARG, "chunk %lld: zstd content size %llu != chunk bytes %llu", i,
-                        (unsigned long long)fcs, (unsigned long long)cb);
+            return fail(PBX_E_BADARG, "%s %lld: zstd content size %llu != %s bytes %llu", what, i,
+                        (unsigned long long)fcs, what, (unsigned long long)cb);
     }
     q += fcs_size;
     for (;;) {
-        if (q + 3 > len) return fail(PBX_E_BADARG, "chunk %lld: truncated zstd frame", i);
+        if (q + 3 > len) return fail(PBX_E_BADARG, "%s %lld: truncated zstd frame", what, i);
         const uint32_t bh = (uint32_t)f[q] | (uint32_t)f[q + 1] << 8 | (uint32_t)f[q + 2] << 16;
         const uint32_t type = (bh >> 1) & 3;
-        if (type == 3) return fail(PBX_E_BADARG, "chunk %lld: reserved zstd block type", i);
+        if (type == 3) return fail(PBX_E_BADARG, "%s %lld: reserved zstd block type", what, i);
         q += 3 + (type == 1 ? 1 : bh >> 3);
         if (bh & 1) break;
     }
     if (fhd & 4) q += 4;  // content checksum
-    if (q > len) return fail(PBX_E_BADARG, "chunk %lld: truncated zstd frame", i);
-    if (q < len) return fail(PBX_E_BADARG, "chunk %lld: %llu bytes after the zstd frame", i, (unsigned long long)(len - q));
+    if (q > len) return fail(PBX_E_BADARG, "%s %lld: truncated zstd frame", what, i);
+    if (q < len) return fail(PBX_E_BADARG, "%s %lld: %llu bytes after the zstd frame", what, i, (unsigned long long)(len - q));
     return PBX_OK;
 }
 
@@ -2605,7 +2613,9 @@ struct ZarrInput {
 // segments stored with Predictor = 2) is undone in scratch between the decoders and the placement;
 // P.uplace (the same for a band write) is un-predicted and placed into zp[0] by one kernel after
 // the decoders, and k_zarr_place is launched only if P has chunks.  P.split (multi-sample TIFF
-// segments) is un-predicted and split into the planes of `sd` by k_tiff_split_place.
+// segments) is un-predicted and split into the planes of `sd` by k_tiff_split_place.  P.fplace
+// (TIFF segments stored with Predictor = 3) is un-predicted and placed by k_tiff_fpunpred_place
+// into the planes P.fdst_plane names.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms,
                       const std::vector<TSplitDst>* sd = nullptr) {
@@ -2639,13 +2649,15 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     TPlace* d_tp = nullptr;
     TPlace* d_sp = nullptr;
     TSplitDst* d_sd = nullptr;
+    TPlace* d_fp = nullptr;
+    TPlaceDst* d_fd = nullptr;
     uint32_t* d_err = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto cleanup = [&] {
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2666,6 +2678,16 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (!P.split.empty()) {
         dget(d_sp, sizeof(TPlace) * P.split.size());
         dget(d_sd, sizeof(TSplitDst) * sd->size());
+    }
+    std::vector<TPlaceDst> fd = P.fdst;  // Predictor = 3: the destinations of this launch
+    for (size_t i = 0; i < fd.size(); i++) {
+        const ZPlane& z = zp[P.fdst_plane[i]];
+        fd[i].dev = z.dev; fd[i].pitch = z.pitch; fd[i].sx = z.sx; fd[i].sy = z.sy;
+        fd[i].y_lo = z.y_lo; fd[i].y_hi = z.y_hi;
+    }
+    if (!P.fplace.empty()) {
+        dget(d_fp, sizeof(TPlace) * P.fplace.size());
+        dget(d_fd, sizeof(TPlaceDst) * fd.size());
     }
     dget(d_err, sizeof(uint32_t) * (nerr + 1));
     for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
@@ -2698,6 +2720,10 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = hipMemcpyAsync(d_sp, P.split.data(), sizeof(TPlace) * P.split.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_sd)
         e = hipMemcpyAsync(d_sd, sd->data(), sizeof(TSplitDst) * sd->size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_fp)
+        e = hipMemcpyAsync(d_fp, P.fplace.data(), sizeof(TPlace) * P.fplace.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_fd)
+        e = hipMemcpyAsync(d_fd, fd.data(), sizeof(TPlaceDst) * fd.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
     // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
@@ -2723,6 +2749,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     }
     if (e == hipSuccess && d_sp)
         e = launch_tiff_split_place(st, d_sp, (uint32_t)P.split.size(), P.split_rows, d_sd, d_scr, d_in);
+    if (e == hipSuccess && d_fp)
+        e = launch_tiff_fpunpred_place(st, d_fp, (uint32_t)P.fplace.size(), P.fplace_rows, d_fd, d_scr, d_in);
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     std::vector<uint32_t> err(nerr + 1, 0);
@@ -2795,9 +2823,11 @@ int tiff_segments_check(const pbx_tiff_segments* s) {
     if (s->tiled && ((s->seg_w | s->seg_h) & 15))
         return fail(PBX_E_BADARG, "tile %d x %d: TileWidth and TileLength must be multiples of 16 (TIFF 6.0 section 15)",
                     s->seg_w, s->seg_h);
-    if (s->compression != PBX_TIFF_NONE && s->compression != PBX_TIFF_LZW && s->compression != PBX_TIFF_DEFLATE)
-        return fail(PBX_E_BADARG, "bad compression %d (1 none, 5 LZW, 8 deflate)", s->compression);
-    if (s->predictor != 1 && s->predictor != 2) return fail(PBX_E_BADARG, "bad predictor %d (1 or 2)", s->predictor);
+    if (s->compression != PBX_TIFF_NONE && s->compression != PBX_TIFF_LZW && s->compression != PBX_TIFF_DEFLATE &&
+        s->compression != PBX_TIFF_ZSTD)
+        return fail(PBX_E_BADARG, "bad compression %d (1 none, 5 LZW, 8 deflate, 50000 zstd)", s->compression);
+    if (s->predictor < 1 || s->predictor > 3)
+        return fail(PBX_E_BADARG, "bad predictor %d (1, 2, or 3 on float and double planes)", s->predictor);
     if (s->flags) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
     return PBX_OK;
 }
@@ -2808,6 +2838,13 @@ int tiff_samples_check(int32_t spp, int64_t sample, int bpp) {
     if (sample < 0 || sample >= spp)
         return fail(PBX_E_BADARG, "sample %lld outside segments of %d samples per pixel", (long long)sample, spp);
     if (spp > 1 && bpp == 8) return fail(PBX_E_BADARG, "samples_per_pixel %d on 64-bit samples", spp);
+    return PBX_OK;
+}
+
+// Predictor = 3 (the floating-point predictor) is defined on IEEE samples only.
+int tiff_fp_predictor_check(const pbx_tiff_segments* s, int32_t pixel_type) {
+    if (s->predictor == 3 && pixel_type != PBX_FLOAT && pixel_type != PBX_DOUBLE)
+        return fail(PBX_E_BADARG, "bad predictor 3 (the floating-point predictor) on a plane of integer samples");
     return PBX_OK;
 }
 
@@ -2823,12 +2860,26 @@ int tiff_samples_check(int32_t spp, int64_t sample, int bpp) {
 // band writes are planned alike: a stored segment is read where it was uploaded, and every
 // segment, whatever the predictor, goes into P.split for k_tiff_split_place with `dst` as its
 // entry in the launch's TSplitDst table.
+// Compression 50000 is one zstd frame per segment (zstd_frame_check, then ZS_ZSTD), under any
+// predictor.  Predictor = 3 (bpp 4 or 8, spp 1) is planned as spp > 1 is, registration and band
+// writes alike: a stored segment is read where it was uploaded, no TUnpred and no ZChunk, every
+// segment a TPlace in P.fplace for k_tiff_fpunpred_place, its destination ZPlane `plane`.
 int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pbx_tiff_segments* s,
               uint64_t in_base, uint32_t plane, ZarrPlan& P, uint64_t* dlen_sum, bool band = false,
               int64_t sr0 = 0, int64_t sr1 = -1, int spp = 1, uint32_t split_dst = 0) {
     if (!s->tiled && s->seg_w != size_x)
         return fail(PBX_E_BADARG, "strip width %d != plane width %d", s->seg_w, size_x);
     if (s->predictor == 2 && bpp == 8) return fail(PBX_E_BADARG, "predictor 2 on floating-point samples");
+    const bool fp = s->predictor == 3;
+    if (fp && bpp != 4 && bpp != 8)
+        return fail(PBX_E_BADARG, "bad predictor 3 (the floating-point predictor) on %d-byte samples", bpp);
+    if (fp && spp != 1)
+        return fail(PBX_E_BADARG, "bad predictor 3 (the floating-point predictor) on chunky segments of %d samples "
+                                  "per pixel", spp);
+    if (fp) {  // the call's destination: the rest of it comes from ZPlane `plane` at the launch
+        P.fdst.push_back(TPlaceDst{nullptr, 0, 0, 0, 0, 0, (uint32_t)bpp, big_endian ? 1u : 0u});
+        P.fdst_plane.push_back(plane);
+    }
     const int64_t gx = s->tiled ? ((int64_t)size_x + s->seg_w - 1) / s->seg_w : 1;
     const int64_t gy = ((int64_t)size_y + s->seg_h - 1) / s->seg_h;
     if (sr1 < 0) sr1 = gy;
@@ -2845,7 +2896,7 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
         if (dlen > 0x7fffffffull || len > 0x7fffffffull || rows > (65535 << 4))
             return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
         const uint64_t ob = o + in_base;
-        const bool in_place = (band || spp > 1) && s->compression == PBX_TIFF_NONE;  // read from the upload buffer
+        const bool in_place = (band || spp > 1 || fp) && s->compression == PBX_TIFF_NONE;  // read from the upload buffer
         const uint64_t dst = in_place ? ob : P.scratch;
         uint32_t kind = ZS_COPY;
         if (s->compression == PBX_TIFF_NONE) {
@@ -2857,6 +2908,10 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
             if (len >= 2 && s->data[o] == 0 && (s->data[o + 1] & 1))
                 return fail(PBX_E_BADARG, "segment %lld: old-style (pre-6.0, LSB-first) LZW", (long long)i);
             kind = ZS_LZW;
+        } else if (s->compression == PBX_TIFF_ZSTD) {
+            // one frame that decodes to the segment (a content size, if the frame has one, is dlen)
+            if (int rc = zstd_frame_check(s->data + o, len, dlen, (long long)i, "segment")) return rc;
+            kind = ZS_ZSTD;
         } else {
             kind = ZS_ZLIB;
         }
@@ -2867,6 +2922,12 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
             P.split.push_back(TPlace{dst, (uint32_t)s->seg_w * (uint32_t)bpp * (uint32_t)spp, (uint32_t)rows, x0, y0,
                                      in_place ? 1u : 0u, split_dst});
             P.split_rows = std::max(P.split_rows, (uint32_t)rows);
+            continue;
+        }
+        if (fp) {
+            P.fplace.push_back(TPlace{dst, (uint32_t)s->seg_w * (uint32_t)bpp, (uint32_t)rows, x0, y0,
+                                      in_place ? 1u : 0u, (uint32_t)P.fdst.size() - 1});
+            P.fplace_rows = std::max(P.fplace_rows, (uint32_t)rows);
             continue;
         }
         if (band && s->predictor == 2) {
@@ -2907,6 +2968,7 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     if (int rc = tiff_samples_check(spp, sample, bpp_of(q->pixel_type))) return rc;
     if (s->predictor == 2 && (q->pixel_type == PBX_FLOAT || q->pixel_type == PBX_DOUBLE))
         return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)q->id);
+    if (int rc = tiff_fp_predictor_check(s, q->pixel_type)) return rc;
     const int bpp = bpp_of(q->pixel_type);
     const int64_t gx = s->tiled ? ((int64_t)q->size_x + s->seg_w - 1) / s->seg_w : 1;
     const int64_t sr0 = y0 / s->seg_h, sr1 = ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h;
@@ -2950,6 +3012,7 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
             if (int rc = tiff_segments_check(&ts[refs[k].layer])) return rc;
             if (ts[refs[k].layer].predictor == 2 && (d->pixel_type == PBX_FLOAT || d->pixel_type == PBX_DOUBLE))
                 return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)k);
+            if (int rc = tiff_fp_predictor_check(&ts[refs[k].layer], d->pixel_type)) return rc;
             if (int rc = tiff_samples_check(depths[refs[k].layer], refs[k].slice, bpp_of(d->pixel_type))) return rc;
             for (const ZarrWant& w : want[refs[k].layer])
                 if (w.slice == refs[k].slice)
@@ -3169,7 +3232,7 @@ int pbx_test_tiff_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t size_
     for (const auto& k : P.kind) out[0] += k.size();
     out[1] = sum;
     out[2] = P.scratch;
-    out[3] = P.unpred.empty() ? 0 : 1;
+    out[3] = s->predictor == 3 ? P.fplace.size() : P.unpred.empty() ? 0 : 1;
     return PBX_OK;
 }
 
@@ -3233,7 +3296,9 @@ int pbx_test_tiff_plan_samples(const pbx_tiff_segments* s, int32_t size_x, int32
     for (const auto& k : P.kind) out[0] += k.size();
     out[1] = sum;
     out[2] = P.scratch;
-    out[3] = samples_per_pixel > 1 ? P.split.size() : (band ? P.uplace.empty() : P.unpred.empty()) ? 0 : 1;
+    out[3] = samples_per_pixel > 1 ? P.split.size()
+             : s->predictor == 3   ? P.fplace.size()
+                                   : (band ? P.uplace.empty() : P.unpred.empty()) ? 0 : 1;
     return PBX_OK;
 }
 
@@ -3254,7 +3319,7 @@ int pbx_test_tiff_band_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t 
     for (const auto& k : P.kind) out[0] += k.size();
     out[1] = sum;
     out[2] = P.scratch;
-    out[3] = P.uplace.empty() ? 0 : 1;
+    out[3] = s->predictor == 3 ? P.fplace.size() : P.uplace.empty() ? 0 : 1;
     return PBX_OK;
 }
 

@@ -760,6 +760,7 @@ def pack_chunks(chunks: Sequence[Optional[bytes]]):
 # pixel data is decoded on the GPU (pbx_planes_register_tiff).
 
 TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
+TIFF_ZSTD = 50000
 _TIFF_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4,
                    16: 8, 17: 8, 18: 8}
 _TIFF_INT_FMT = {1: "B", 3: "H", 4: "I", 13: "I", 16: "Q", 18: "Q", 6: "b", 8: "h", 9: "i", 17: "q"}
@@ -920,11 +921,16 @@ def _tiff_pixel_type(path: str, ifd: dict) -> int:
     if pt is None:
         raise PbxError(400, "%s: SampleFormat %d with %d bits is none of the pixel types"
                        % (path, ifd["sampleformat"], ifd["bits"]))
-    if ifd["compression"] not in (1, 5, 8, 32946):
-        raise PbxError(400, "%s: Compression %d (1 none, 5 LZW, 8 / 32946 deflate)" % (path, ifd["compression"]))
-    if ifd["predictor"] not in (1, 2):
-        raise PbxError(400, "%s: Predictor %d (1 or 2; the floating-point predictor 3 is not supported)"
-                       % (path, ifd["predictor"]))
+    if ifd["compression"] not in (1, 5, 8, 32946, TIFF_ZSTD):
+        raise PbxError(400, "%s: Compression %d (1 none, 5 LZW, 8 / 32946 deflate, 50000 zstd)"
+                       % (path, ifd["compression"]))
+    if ifd["predictor"] not in (1, 2, 3):
+        raise PbxError(400, "%s: Predictor %d (1, 2, or 3 on floating-point samples)" % (path, ifd["predictor"]))
+    if ifd["predictor"] == 3 and pt not in (FLOAT, DOUBLE):
+        raise PbxError(400, "%s: Predictor 3 (the floating-point predictor) on integer samples" % path)
+    if ifd["predictor"] == 3 and spp > 1 and ifd.get("planar", 1) != 2:
+        raise PbxError(400, "%s: Predictor 3 (the floating-point predictor) on chunky segments of %d samples per "
+                       "pixel is not supported" % (path, spp))
     if ifd["predictor"] == 2 and pt in (FLOAT, DOUBLE):
         raise PbxError(400, "%s: Predictor 2 on floating-point samples" % path)
     if ifd["fillorder"] != 1:
@@ -1422,8 +1428,8 @@ class PixelsService:
     def register_tiff_planes(self, planes: Sequence[dict], timing: bool = False):
         """Planes from TIFF strips or tiles, decoded by one set of GPU launches
         (pbx_planes_register_tiff): each dict (tiff_plane_spec) holds image_id, z, c, t,
-        pixel_type, size_x, size_y, seg_w, seg_h, tiled, compression (1 none, 5 LZW, 8 deflate),
-        predictor (1 or 2), segments (a sequence of bytes in C order over the grid, or
+        pixel_type, size_x, size_y, seg_w, seg_h, tiled, compression (1 none, 5 LZW, 8 deflate, 50000 zstd),
+        predictor (1, 2, or 3 on FLOAT / DOUBLE planes), segments (a sequence of bytes in C order over the grid, or
         pack_chunks()' (data, offsets) pair) [, big_endian = the FILE's byte order, level,
         samples_per_pixel, sample].  Specs with samples_per_pixel > 1 (chunky segments of that many
         interleaved samples per pixel) that carry the SAME segments object are the samples of one
