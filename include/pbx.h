@@ -384,10 +384,15 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * single-sample segments already and go through the calls below.
  * Not supported (400 by the caller or here): SamplesPerPixel > 4, Predictor 3 on integer or
  * chunky multi-sample (RGB float) data, half-precision samples, FillOrder 2, pre-6.0 (LSB-first)
- * LZW streams, JPEG / PackBits / LZMA / LERC / WebP and other compressions, YCbCr / CMYK / palette
- * colour, sub-byte or 12-bit samples.
+ * LZW streams, PackBits / LZMA / LERC / WebP / JPEG 2000 / JPEG XR and other compressions, CMYK /
+ * palette colour, sub-byte or 12-bit samples.  JPEG (Compression 7, baseline, 8-bit, gray / RGB /
+ * YCbCr) goes through the pbx_*_tiff_jpeg calls further down and through no other: old-style JPEG
+ * (Compression 6), progressive, lossless, arithmetic-coded and 12-bit streams, YCbCr under any
+ * other compression, and the Aperio habit of YCbCr data under PhotometricInterpretation 2 (stored
+ * as it is, libtiff's rule) are not supported.
  * The JNI shim does not wrap these calls (as the deep Zarr calls). */
-enum pbx_tiff_compression { PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8, PBX_TIFF_ZSTD = 50000 };
+enum pbx_tiff_compression { PBX_TIFF_JPEG = 7 /* through the pbx_*_tiff_jpeg calls only */,
+                            PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8, PBX_TIFF_ZSTD = 50000 };
 typedef struct pbx_tiff_segments {
     int32_t seg_w, seg_h;       /* tiles: TileWidth x TileLength (edge tiles are full, padded);
                                    strips: ImageWidth x RowsPerStrip (the last strip holds only
@@ -466,6 +471,48 @@ int pbx_planes_register_tiff_samples(pbx_ctx* ctx, uint64_t n, const pbx_plane_d
 int pbx_band_write_tiff_sample(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                                const pbx_tiff_segments* segs, int32_t samples_per_pixel, int32_t sample,
                                double* kernel_ms);
+/* JPEG-compressed segments (Compression = 7, TIFF Technical Note 2; DESIGN.md §10b "JPEG
+ * segments"): every strip or tile is a baseline sequential Huffman JPEG stream (SOF0, 8-bit, one
+ * scan of all components) of exactly the segment's size -- TileWidth x TileLength, or ImageWidth
+ * x the strip's own row count -- with its tables in the IFD's JPEGTables (tag 347: SOI, DQT / DHT,
+ * EOI) and / or in the stream itself, whose own override.  The host reads marker segments only;
+ * entropy decoding (restart intervals, FF 00 stuffing, fill bytes), dequantisation and the
+ * accurate integer IDCT run in k_tiff_jpeg_decode, one wave per segment, and k_tiff_jpeg_place
+ * upsamples ("fancy" triangle filter), converts and places.  The arithmetic is libjpeg's, so the
+ * planes equal libjpeg-turbo's (libtiff, PIL; by assumption javax.imageio and so Bio-Formats) byte
+ * for byte as long as no IDCT output leaves [-512, 511] before the clamp.
+ * Components: 1 (samples_per_pixel 1), or 3 (samples_per_pixel 3, chunky) which are converted
+ * YCbCr -> RGB if and only if ycbcr is set (PhotometricInterpretation 6; libtiff's rule) and are
+ * otherwise stored as they are; sampling 1x1, and under ycbcr also 2x1 or 2x2 luma over 1x1 chroma
+ * (taken from the SOF, not from tag 530).  Planar files hand over each sample's segments as
+ * one-sample segments. */
+typedef struct pbx_tiff_jpeg {
+    const uint8_t* tables;   /* tag 347's bytes, or NULL */
+    uint64_t tables_len;
+    int32_t ycbcr;           /* 1: PhotometricInterpretation 6, convert to RGB */
+    int32_t reserved;        /* 0 */
+} pbx_tiff_jpeg;             /* 24 bytes */
+/* pbx_planes_register_tiff_samples for JPEG layers, jpeg[l] going with layers[l].  In these calls
+ * compression must be 7, predictor 1 and every plane PBX_UINT8 (the other TIFF calls keep
+ * answering "bad compression 7").  Keys, all-or-none, staging, statuses and kernel_ms ([0] decode,
+ * [1] placement) are shared with that call.  400 on the host, before anything is uploaded, names:
+ * a segment or tables stream that does not start with SOI or whose header is cut short, SOF1 /
+ * SOF2 / SOF3 and arithmetic coding, precision != 8, 4 components, sampling factors outside the
+ * three above, subsampling without ycbcr, ycbcr with samples_per_pixel != 3, more than one scan,
+ * SOF size != segment size, a missing quantiser or Huffman table, an over-subscribed Huffman
+ * table, a 16-bit quantiser.  400 from the device (nothing registered): entropy data that ends
+ * before the last MCU, a code in no table, a run past coefficient 63, a DC size > 11 or an AC
+ * size > 10, a restart marker missing, out of sequence or misplaced. */
+int pbx_planes_register_tiff_jpeg(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
+                                  const pbx_zarr_slice* refs, uint64_t n_layers,
+                                  const pbx_tiff_segments* layers, const int32_t* samples_per_pixel,
+                                  const pbx_tiff_jpeg* jpeg, uint64_t* plane_ids, double* kernel_ms);
+/* pbx_band_write_tiff_sample for JPEG segments: the covering segment rows are decoded for this
+ * call and sample `sample` alone is stored.  A device refusal fails the band's load as a bad LZW
+ * stream does. */
+int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                             const pbx_tiff_segments* segs, int32_t samples_per_pixel, int32_t sample,
+                             const pbx_tiff_jpeg* jpeg, double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -753,6 +800,16 @@ int pbx_test_tiff_band_plan(const pbx_tiff_segments* segs, int32_t size_x, int32
  * included).  400 as the real calls. */
 int pbx_test_tiff_plan_samples(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t bpp,
                                int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[4]);
+
+/* Test hook: the header parser and planner of pbx_planes_register_tiff_jpeg (rows == 0: the whole
+ * plane) or pbx_band_write_tiff_jpeg (rows >= 1, segs holding the covering segment rows only)
+ * alone, no context and no device call.  Returns the status (the message through
+ * pbx_last_error).  out: streams, decoded samples (every component of every segment at full
+ * resolution), scratch bytes, distinct table sets, the first segment's placement mode (0 stored
+ * as it is, 1 YCbCr 1x1, 2 h2v1, 3 h2v2), and the bytes of entropy-coded data (each stream from
+ * the end of its SOS header to the end of its segment). */
+int pbx_test_tiff_jpeg_plan(const pbx_tiff_segments* segs, const pbx_tiff_jpeg* jpeg, int32_t size_x, int32_t size_y,
+                            int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[6]);
 
 #ifdef __cplusplus
 }

@@ -236,4 +236,61 @@ static_assert(sizeof(TSplitDst) == 72, "TSplitDst is uploaded as is");
 hipError_t launch_tiff_split_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
                                    const TSplitDst* d_dst, const uint8_t* scratch, const uint8_t* input);
 
+// JPEG-compressed TIFF segments (kernels_tiff_jpeg.hip; Compression = 7, baseline streams of
+// 8-bit samples).  The host parses the marker segments; the tables reach the device resolved per
+// component of the scan, one JTabSet per distinct set of a launch.
+// JHuff, a canonical Huffman code as the decoder reads it: lut[the next 9 bits] = length << 8 |
+// symbol for codes of at most 9 bits (0: a longer code, or none), and for longer ones libjpeg's
+// walk: the code of l bits is in the table if it is <= maxcode[l] (-1: no code of that length),
+// and its symbol is val[code + valoff[l]].
+struct JHuff {
+    uint16_t lut[512];
+    int32_t maxcode[18];  // [1 .. 16]
+    int32_t valoff[18];   // [1 .. 16]: index of the first symbol of that length - its code
+    uint8_t val[256];
+};
+static_assert(sizeof(JHuff) == 1424, "JHuff is uploaded as is");
+struct JTabSet {
+    uint16_t q[3][64];    // component c's quantiser, de-zigzagged (row-major)
+    JHuff h[6];           // component c's DC table at 2 c, its AC table at 2 c + 1
+};
+static_assert(sizeof(JTabSet) == 8928, "JTabSet is uploaded as is");
+// One stream (a strip or tile).  Its decoded planes lie in scratch from dst_off: component 0 with
+// mcuy * vs * 8 rows of pitch0 bytes, then (ncomp == 3) components 1 and 2 at offc1 / offc2 with
+// mcuy * 8 rows of pitchc bytes.  Pitches are multiples of 16, the offsets of 256.
+struct JStream {
+    uint64_t src_off;     // the entropy-coded data (after the SOS header) in the upload buffer
+    uint64_t dst_off;
+    uint32_t csize;       // bytes from src_off to the segment's end
+    uint32_t tabset;      // index into the launch's JTabSet table
+    uint32_t ncomp;       // 1 or 3
+    uint32_t hs, vs;      // component 0's sampling factors: 1x1, 2x1 or 2x2 (the others: 1x1)
+    uint32_t mcux, mcuy;  // the MCU grid
+    uint32_t restart;     // restart interval in MCUs, 0 = none
+    uint32_t pitch0, pitchc, offc1, offc2;
+};
+static_assert(sizeof(JStream) == 64, "JStream is uploaded as is");
+// err[]: 0, or 1 entropy data ends before the last MCU, 2 a code that is in no table, 3 a run that
+// passes coefficient 63, 4 a DC size > 11 or an AC size > 10, 5 a restart marker that is missing,
+// out of sequence or misplaced.
+hipError_t launch_tiff_jpeg_decode(hipStream_t st, const JStream* d_streams, uint32_t n, const JTabSet* d_tabs,
+                                   const uint8_t* src, uint8_t* scratch, uint32_t* err);
+// k_tiff_jpeg_place: a decoded segment (JStream's planes) upsampled, converted, split and placed
+// into the planes of entry `dst` of the launch's TSplitDst table (bpp 1; spp 1 or 3; a null dev[s]
+// is a component nobody wants), clipped as k_tiff_split_place clips.
+enum : uint32_t { JM_COPY = 0, JM_YCC = 1, JM_YCC_H2V1 = 2, JM_YCC_H2V2 = 3 };
+struct TJpegSeg {
+    uint64_t src;         // JStream::dst_off
+    uint32_t offc1, offc2, pitch0, pitchc;
+    uint32_t w, rows;     // the segment's own size in pixels (the SOF's)
+    int32_t x0, y0;       // its origin in the plane
+    uint32_t mode;        // JM_*: components as they are (gray, or RGB stored as such), or YCbCr
+                          // -> RGB with component 0 at 1x1, 2x1 (h2v1) or 2x2 (h2v2)
+    uint32_t ncomp;       // 1 or 3
+    uint32_t dst, pad;
+};
+static_assert(sizeof(TJpegSeg) == 56, "TJpegSeg is uploaded as is");
+hipError_t launch_tiff_jpeg_place(hipStream_t st, const TJpegSeg* d_segs, uint32_t n, uint32_t max_rows,
+                                  const TSplitDst* d_dst, const uint8_t* scratch);
+
 }  // namespace pbx

@@ -2348,6 +2348,13 @@ struct ZarrPlan {
     uint32_t fplace_rows = 0;     // the tallest of them
     std::vector<TPlaceDst> fdst;
     std::vector<uint32_t> fdst_plane;
+    // JPEG-compressed TIFF segments (tiff_jpeg_plan): one JStream and one TJpegSeg per segment
+    // (then no `kind`, no `chunks`), the distinct table sets of the launch, and the tallest
+    // segment; TJpegSeg::dst names the segment's entry in the launch's TSplitDst table
+    std::vector<JStream> jstreams;
+    std::vector<TJpegSeg> jsegs;
+    std::vector<JTabSet> jtabs;
+    uint32_t jseg_rows = 0;
 };
 
 // A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
@@ -2615,11 +2622,13 @@ struct ZarrInput {
 // the decoders, and k_zarr_place is launched only if P has chunks.  P.split (multi-sample TIFF
 // segments) is un-predicted and split into the planes of `sd` by k_tiff_split_place.  P.fplace
 // (TIFF segments stored with Predictor = 3) is un-predicted and placed by k_tiff_fpunpred_place
-// into the planes P.fdst_plane names.
+// into the planes P.fdst_plane names.  P.jstreams (JPEG-compressed TIFF segments) are decoded by
+// k_tiff_jpeg_decode after the other decoders, their err[] entries after the checks', and
+// P.jsegs upsampled, converted and placed into the planes of `sd` by k_tiff_jpeg_place.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms,
                       const std::vector<TSplitDst>* sd = nullptr) {
-    if (!P.split.empty() && (!sd || sd->empty()))
+    if ((!P.split.empty() || !P.jsegs.empty()) && (!sd || sd->empty()))
         return fail(PBX_E_INTERNAL, "zarr decode: split segments without destinations");
     uint32_t counts[ZS_NKINDS], nstreams = 0;
     std::vector<ZStream> all;
@@ -2639,7 +2648,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         for (const ZCheck& c : P.checks[k]) if (c.len >= split) checks.push_back(c);
         ck_n[k] = (uint32_t)checks.size() - ck_first[k];
     }
-    const uint32_t nchecks = (uint32_t)checks.size(), nerr = nstreams + nchecks;
+    const uint32_t nchecks = (uint32_t)checks.size(), njpeg = (uint32_t)P.jstreams.size();
+    const uint32_t nerr = nstreams + nchecks + njpeg;  // err[]: streams, checks, JPEG streams
     uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
     ZStream* d_st = nullptr;
     ZCheck* d_ck = nullptr;
@@ -2651,13 +2661,16 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     TSplitDst* d_sd = nullptr;
     TPlace* d_fp = nullptr;
     TPlaceDst* d_fd = nullptr;
+    JStream* d_js = nullptr;
+    JTabSet* d_jt = nullptr;
+    TJpegSeg* d_jp = nullptr;
     uint32_t* d_err = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto cleanup = [&] {
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_js, (void*)d_jt, (void*)d_jp, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2675,9 +2688,12 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     dget(d_pl, sizeof(ZPlane) * zp.size());
     if (!P.unpred.empty()) dget(d_up, sizeof(TUnpred) * P.unpred.size());
     if (!P.uplace.empty()) dget(d_tp, sizeof(TPlace) * P.uplace.size());
-    if (!P.split.empty()) {
-        dget(d_sp, sizeof(TPlace) * P.split.size());
-        dget(d_sd, sizeof(TSplitDst) * sd->size());
+    if (!P.split.empty()) dget(d_sp, sizeof(TPlace) * P.split.size());
+    if (!P.split.empty() || njpeg) dget(d_sd, sizeof(TSplitDst) * sd->size());
+    if (njpeg) {
+        dget(d_js, sizeof(JStream) * njpeg);
+        dget(d_jt, sizeof(JTabSet) * P.jtabs.size());
+        dget(d_jp, sizeof(TJpegSeg) * P.jsegs.size());
     }
     std::vector<TPlaceDst> fd = P.fdst;  // Predictor = 3: the destinations of this launch
     for (size_t i = 0; i < fd.size(); i++) {
@@ -2724,6 +2740,12 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = hipMemcpyAsync(d_fp, P.fplace.data(), sizeof(TPlace) * P.fplace.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_fd)
         e = hipMemcpyAsync(d_fd, fd.data(), sizeof(TPlaceDst) * fd.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_js)
+        e = hipMemcpyAsync(d_js, P.jstreams.data(), sizeof(JStream) * njpeg, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_jt)
+        e = hipMemcpyAsync(d_jt, P.jtabs.data(), sizeof(JTabSet) * P.jtabs.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_jp)
+        e = hipMemcpyAsync(d_jp, P.jsegs.data(), sizeof(TJpegSeg) * P.jsegs.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
     // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
@@ -2737,6 +2759,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess) e = launch_zarr_decode(st, d_st, counts, d_in, d_scr, d_lit, d_err);
     if (e == hipSuccess) e = crc(ZK_CRC32);
     if (e == hipSuccess && d_up) e = launch_tiff_unpred(st, d_up, (uint32_t)P.unpred.size(), P.unpred_rows, d_scr);
+    if (e == hipSuccess && d_js)
+        e = launch_tiff_jpeg_decode(st, d_js, njpeg, d_jt, d_in, d_scr, d_err + nstreams + nchecks);
     if (e == hipSuccess) e = hipEventRecord(ev[1], st);
     if (e == hipSuccess && !P.chunks.empty())
         e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
@@ -2751,6 +2775,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = launch_tiff_split_place(st, d_sp, (uint32_t)P.split.size(), P.split_rows, d_sd, d_scr, d_in);
     if (e == hipSuccess && d_fp)
         e = launch_tiff_fpunpred_place(st, d_fp, (uint32_t)P.fplace.size(), P.fplace_rows, d_fd, d_scr, d_in);
+    if (e == hipSuccess && d_jp)
+        e = launch_tiff_jpeg_place(st, d_jp, (uint32_t)P.jsegs.size(), P.jseg_rows, d_sd, d_scr);
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     std::vector<uint32_t> err(nerr + 1, 0);
@@ -2774,6 +2800,15 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
             cleanup();
             return fail(PBX_E_BADARG, "chunk checksum mismatch: the %s of %u bytes is not 0x%08x",
                         c.poly == ZK_CRC32C ? "crc32c" : "gzip CRC-32", c.len, c.expect);
+        }
+    for (uint32_t s = 0; s < njpeg; s++)
+        if (const uint32_t code = err[nstreams + nchecks + s]) {
+            static const char* why[6] = {"", "entropy data ends before the last MCU", "a code that is in no table",
+                                         "a run that passes coefficient 63", "a DC size > 11 or an AC size > 10",
+                                         "a restart marker missing, out of sequence or misplaced"};
+            cleanup();
+            return fail(PBX_E_BADARG, "corrupt segment stream %u (jpeg, decoder code %u: %s)", s, code,
+                        code < 6 ? why[code] : "?");
         }
     if (kernel_ms) {
         float a = 0, b = 0;
@@ -2955,16 +2990,340 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
     return PBX_OK;
 }
 
+// ------------------------------------------------------- JPEG-compressed TIFF segments
+// Compression = 7 (TIFF Technical Note 2): every strip or tile is a JPEG stream of its own, the
+// tables usually once per IFD in tag 347 (JPEGTables: SOI, DQT / DHT segments, EOI) and the
+// segments abbreviated.  The host reads marker segments only -- never a byte of entropy-coded
+// data, restart markers included -- and every length is checked against the bytes it lies in.
+static_assert(sizeof(pbx_tiff_jpeg) == 24, "pbx_tiff_jpeg is part of the C-ABI (ctypes mirror PbxTiffJpeg)");
+
+// The quantisers and Huffman codes in force: tag 347's, then overridden by the segment's own.
+struct JpegTables {
+    bool qset[4] = {false, false, false, false};
+    uint16_t q[4][64];  // in zigzag order, as stored
+    bool hset[2][4] = {{false, false, false, false}, {false, false, false, false}};  // [DC / AC][Th]
+    uint8_t bits[2][4][17];
+    uint8_t vals[2][4][256];
+};
+
+// A segment's header up to the scan's entropy-coded data.
+struct JpegHeader {
+    uint32_t width = 0, height = 0, ncomp = 0;
+    uint32_t h[3] = {0, 0, 0}, v[3] = {0, 0, 0}, tq[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+    uint32_t restart = 0;
+    uint64_t data = 0;  // offset of the entropy-coded data in the segment
+};
+
+// DQT payload p[0 .. len)
+int jpeg_dqt(const uint8_t* p, uint64_t len, JpegTables& T, const char* what) {
+    uint64_t q = 0;
+    while (q < len) {
+        const uint32_t pq = p[q] >> 4, tq = p[q] & 15;
+        if (pq > 1 || tq > 3) return fail(PBX_E_BADARG, "%s: bad DQT (Pq %u, Tq %u)", what, pq, tq);
+        if (pq == 1) return fail(PBX_E_BADARG, "%s: 16-bit quantiser (DQT with Pq = 1) is not supported", what);
+        if (q + 65 > len) return fail(PBX_E_BADARG, "%s: truncated DQT", what);
+        for (int k = 0; k < 64; k++) T.q[tq][k] = p[q + 1 + k];
+        T.qset[tq] = true;
+        q += 65;
+    }
+    return PBX_OK;
+}
+
+// DHT payload p[0 .. len): counts per length, then the symbols; the Kraft sum of every table
+int jpeg_dht(const uint8_t* p, uint64_t len, JpegTables& T, const char* what) {
+    uint64_t q = 0;
+    while (q < len) {
+        const uint32_t tc = p[q] >> 4, th = p[q] & 15;
+        if (tc > 1 || th > 3) return fail(PBX_E_BADARG, "%s: bad DHT (Tc %u, Th %u)", what, tc, th);
+        if (q + 17 > len) return fail(PBX_E_BADARG, "%s: truncated DHT", what);
+        uint32_t n = 0, kraft = 0;
+        T.bits[tc][th][0] = 0;
+        for (int l = 1; l <= 16; l++) {
+            T.bits[tc][th][l] = p[q + l];
+            n += p[q + l];
+            kraft += (uint32_t)p[q + l] << (16 - l);
+        }
+        if (n > 256 || kraft > 65536)
+            return fail(PBX_E_BADARG, "%s: over-subscribed Huffman table (%s %u: %u codes, Kraft sum %u / 65536)", what,
+                        tc ? "AC" : "DC", th, n, kraft);
+        if (q + 17 + n > len) return fail(PBX_E_BADARG, "%s: truncated DHT", what);
+        memset(T.vals[tc][th], 0, 256);
+        memcpy(T.vals[tc][th], p + q + 17, n);
+        T.hset[tc][th] = true;
+        q += 17 + n;
+    }
+    return PBX_OK;
+}
+
+// The marker at f[q ..] (fill bytes before it skipped): its code, and for one with a length its
+// payload [*pay, *pay + *plen); q moves past it.  400 if it or its payload leaves f[0 .. len).
+int jpeg_next_marker(const uint8_t* f, uint64_t len, uint64_t& q, uint32_t* code, uint64_t* pay, uint64_t* plen,
+                     const char* what) {
+    if (q >= len || f[q] != 0xFF) return fail(PBX_E_BADARG, "%s: truncated header (no marker at byte %llu)", what, (unsigned long long)q);
+    while (q < len && f[q] == 0xFF) q++;
+    if (q >= len) return fail(PBX_E_BADARG, "%s: truncated header", what);
+    *code = f[q++];
+    *pay = q;
+    *plen = 0;
+    if (*code == 0xD8 || *code == 0xD9 || *code == 0x01 || (*code >= 0xD0 && *code <= 0xD7)) return PBX_OK;
+    if (*code == 0) return fail(PBX_E_BADARG, "%s: FF 00 where a marker should stand", what);
+    if (q + 2 > len) return fail(PBX_E_BADARG, "%s: truncated header", what);
+    const uint32_t L = (uint32_t)f[q] << 8 | f[q + 1];
+    if (L < 2 || q + L > len) return fail(PBX_E_BADARG, "%s: truncated header (marker FF %02X of %u bytes)", what, *code, L);
+    *pay = q + 2;
+    *plen = L - 2;
+    q += L;
+    return PBX_OK;
+}
+
+// Tag 347: SOI, table segments, EOI.
+int jpeg_parse_tables(const uint8_t* f, uint64_t len, JpegTables& T) {
+    const char* what = "JPEGTables";
+    if (len < 2 || f[0] != 0xFF || f[1] != 0xD8) return fail(PBX_E_BADARG, "%s does not start with SOI", what);
+    uint64_t q = 2;
+    for (;;) {
+        uint32_t code;
+        uint64_t pay, plen;
+        if (int rc = jpeg_next_marker(f, len, q, &code, &pay, &plen, what)) return rc;
+        if (code == 0xD9) return PBX_OK;
+        if (code == 0xDB) { if (int rc = jpeg_dqt(f + pay, plen, T, what)) return rc; }
+        else if (code == 0xC4) { if (int rc = jpeg_dht(f + pay, plen, T, what)) return rc; }
+        else if (code == 0xDA || (code >= 0xC0 && code <= 0xCF && code != 0xC8))
+            return fail(PBX_E_BADARG, "%s: marker FF %02X in a tables-only stream", what, code);
+    }
+}
+
+// A segment's marker segments up to and including the SOS header.  T (may be null) takes its
+// DQT / DHT; *own says whether it has any (with T null they are stepped over, length-checked
+// like every marker segment, and left for a second walk that has somewhere to put them).
+int jpeg_parse_header(const uint8_t* f, uint64_t len, JpegTables* T, bool* own, JpegHeader& H, const char* what) {
+    if (len < 2 || f[0] != 0xFF || f[1] != 0xD8) return fail(PBX_E_BADARG, "%s does not start with SOI (Compression 7)", what);
+    uint64_t q = 2;
+    bool sof = false;
+    uint32_t cid[3] = {0, 0, 0};
+    for (;;) {
+        uint32_t code;
+        uint64_t pay, plen;
+        if (int rc = jpeg_next_marker(f, len, q, &code, &pay, &plen, what)) return rc;
+        const uint8_t* p = f + pay;
+        if (code == 0xDB || code == 0xC4) {
+            *own = true;
+            if (T)
+                if (int rc = code == 0xDB ? jpeg_dqt(p, plen, *T, what) : jpeg_dht(p, plen, *T, what)) return rc;
+            continue;
+        }
+        if (code == 0xDD) {
+            if (plen != 2) return fail(PBX_E_BADARG, "%s: bad DRI", what);
+            H.restart = (uint32_t)p[0] << 8 | p[1];
+            continue;
+        }
+        if (code == 0xCC) return fail(PBX_E_BADARG, "%s: arithmetic coding (DAC) is not supported", what);
+        if (code >= 0xC1 && code <= 0xCF && code != 0xC8) {
+            static const char* names[16] = {"", "SOF1 (extended sequential)", "SOF2 (progressive)", "SOF3 (lossless)", "",
+                                            "SOF5 (differential)", "SOF6 (differential progressive)", "SOF7 (differential lossless)",
+                                            "", "SOF9 (arithmetic coding)", "SOF10 (progressive, arithmetic coding)",
+                                            "SOF11 (lossless, arithmetic coding)", "", "SOF13 (arithmetic coding)",
+                                            "SOF14 (arithmetic coding)", "SOF15 (arithmetic coding)"};
+            return fail(PBX_E_BADARG, "%s: %s is not supported (baseline SOF0 only)", what, names[code & 15]);
+        }
+        if (code == 0xC0) {
+            if (sof) return fail(PBX_E_BADARG, "%s: two SOF markers", what);
+            if (plen < 6) return fail(PBX_E_BADARG, "%s: truncated SOF", what);
+            if (p[0] != 8) return fail(PBX_E_BADARG, "%s: sample precision %u (8 only)", what, p[0]);
+            H.height = (uint32_t)p[1] << 8 | p[2];
+            H.width = (uint32_t)p[3] << 8 | p[4];
+            H.ncomp = p[5];
+            if (H.ncomp == 4) return fail(PBX_E_BADARG, "%s: 4 components (CMYK / YCCK) are not supported", what);
+            if (H.ncomp != 1 && H.ncomp != 3) return fail(PBX_E_BADARG, "%s: %u components (1 or 3)", what, H.ncomp);
+            if (plen != 6 + 3ull * H.ncomp) return fail(PBX_E_BADARG, "%s: truncated SOF", what);
+            for (uint32_t c = 0; c < H.ncomp; c++) {
+                cid[c] = p[6 + 3 * c];
+                H.h[c] = p[7 + 3 * c] >> 4;
+                H.v[c] = p[7 + 3 * c] & 15;
+                H.tq[c] = p[8 + 3 * c];
+                if (H.tq[c] > 3) return fail(PBX_E_BADARG, "%s: component %u names quantiser %u", what, c, H.tq[c]);
+            }
+            sof = true;
+            continue;
+        }
+        if (code == 0xDA) {
+            if (!sof) return fail(PBX_E_BADARG, "%s: SOS before SOF", what);
+            if (plen < 1) return fail(PBX_E_BADARG, "%s: truncated SOS", what);
+            const uint32_t ns = p[0];
+            if (ns != H.ncomp)
+                return fail(PBX_E_BADARG, "%s: more than one scan (the first holds %u of %u components)", what, ns, H.ncomp);
+            if (plen != 4 + 2ull * ns) return fail(PBX_E_BADARG, "%s: truncated SOS", what);
+            for (uint32_t c = 0; c < ns; c++) {
+                if (p[1 + 2 * c] != cid[c]) return fail(PBX_E_BADARG, "%s: the scan's components are not the frame's, in order", what);
+                H.td[c] = p[2 + 2 * c] >> 4;
+                H.ta[c] = p[2 + 2 * c] & 15;
+                if (H.td[c] > 3 || H.ta[c] > 3) return fail(PBX_E_BADARG, "%s: component %u names Huffman tables %u / %u", what, c, H.td[c], H.ta[c]);
+            }
+            if (p[1 + 2 * ns] != 0 || p[2 + 2 * ns] != 63 || p[3 + 2 * ns] != 0)
+                return fail(PBX_E_BADARG, "%s: a scan of coefficients %u .. %u, Ah/Al 0x%02x (sequential: 0 .. 63, 0)", what,
+                            p[1 + 2 * ns], p[2 + 2 * ns], p[3 + 2 * ns]);
+            H.data = q;
+            return PBX_OK;
+        }
+        if (code == 0xD9) return fail(PBX_E_BADARG, "%s: EOI before any scan", what);
+        if (code == 0xD8 || code == 0x01 || (code >= 0xD0 && code <= 0xD7))
+            return fail(PBX_E_BADARG, "%s: marker FF %02X in the header", what, code);
+        // APPn, COM and anything else with a length: skipped
+    }
+}
+
+// The decoder's form of one canonical code (JHuff, pbx_kernels.h).
+void jpeg_build_huff(const uint8_t* bits, const uint8_t* vals, JHuff& h) {
+    memset(&h, 0, sizeof h);
+    uint32_t code = 0, p = 0;
+    for (int l = 1; l <= 16; l++) {
+        h.maxcode[l] = -1;
+        h.valoff[l] = (int32_t)p - (int32_t)code;
+        for (uint32_t i = 0; i < bits[l]; i++, p++, code++)
+            if (l <= 9)
+                for (uint32_t k = 0; k < (1u << (9 - l)); k++) h.lut[(code << (9 - l)) + k] = (uint16_t)(l << 8 | vals[p]);
+        if (bits[l]) h.maxcode[l] = (int32_t)code - 1;
+        code <<= 1;
+    }
+    memcpy(h.val, vals, 256);
+}
+
+// pbx_tiff_segments / pbx_tiff_jpeg fields of a JPEG layer that can be checked without the plane.
+int tiff_jpeg_check(const pbx_tiff_segments* s, const pbx_tiff_jpeg* j, int32_t pixel_type, int32_t spp) {
+    if (!s->data || !s->offsets || !j) return fail(PBX_E_BADARG, "null argument");
+    if (s->seg_w < 1 || s->seg_h < 1) return fail(PBX_E_BADARG, "bad segment shape %d x %d", s->seg_w, s->seg_h);
+    if (s->tiled && ((s->seg_w | s->seg_h) & 15))
+        return fail(PBX_E_BADARG, "tile %d x %d: TileWidth and TileLength must be multiples of 16 (TIFF 6.0 section 15)",
+                    s->seg_w, s->seg_h);
+    if (s->compression != PBX_TIFF_JPEG) return fail(PBX_E_BADARG, "bad compression %d (the JPEG calls take 7)", s->compression);
+    if (s->predictor != 1) return fail(PBX_E_BADARG, "bad predictor %d on JPEG segments (1 only)", s->predictor);
+    if (s->flags) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
+    if (j->reserved || (j->ycbcr != 0 && j->ycbcr != 1)) return fail(PBX_E_BADARG, "bad pbx_tiff_jpeg (ycbcr %d, reserved %d)", j->ycbcr, j->reserved);
+    if (!j->tables && j->tables_len) return fail(PBX_E_BADARG, "null argument");
+    if (pixel_type != PBX_UINT8) return fail(PBX_E_BADARG, "JPEG segments on a plane that is not uint8");
+    if (spp != 1 && spp != 3) return fail(PBX_E_BADARG, "JPEG segments of %d samples per pixel (1 or 3)", spp);
+    if (j->ycbcr && spp != 3) return fail(PBX_E_BADARG, "YCbCr (PhotometricInterpretation 6) with %d samples per pixel", spp);
+    return PBX_OK;
+}
+
+// Host plan of the JPEG segment rows [sr0, sr1) (sr1 < 0: all) of a uint8 plane: tiff_plan's
+// geometry, one JStream and one TJpegSeg per segment, table sets shared between the segments (and
+// layers) whose resolved tables are the same bytes.  Every refusal is made here, before anything
+// is uploaded.  Scratch holds one byte per decoded sample of every component, rows and columns
+// padded to whole MCUs (pitches to 16, planes to 256 bytes).
+int tiff_jpeg_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, const pbx_tiff_jpeg* j, uint64_t in_base,
+                   ZarrPlan& P, int64_t sr0, int64_t sr1, int spp, uint32_t dst, uint64_t* dlen_sum = nullptr) {
+    if (!s->tiled && s->seg_w != size_x)
+        return fail(PBX_E_BADARG, "strip width %d != plane width %d", s->seg_w, size_x);
+    JpegTables base;
+    if (j->tables && j->tables_len)
+        if (int rc = jpeg_parse_tables(j->tables, j->tables_len, base)) return rc;
+    std::vector<std::pair<uint64_t, uint32_t>> known;  // (tables named, set) of this layer's abbreviated segments
+    const int64_t gx = s->tiled ? ((int64_t)size_x + s->seg_w - 1) / s->seg_w : 1;
+    const int64_t gy = ((int64_t)size_y + s->seg_h - 1) / s->seg_h;
+    if (sr1 < 0) sr1 = gy;
+    const int64_t n = gx * (sr1 - sr0);
+    const uint64_t total = s->offsets[n];
+    for (int64_t i = 0; i < n; i++) {
+        const uint64_t o = s->offsets[i], len = s->offsets[i + 1] - o;
+        if (s->offsets[i + 1] < o || s->offsets[i + 1] > total)
+            return fail(PBX_E_BADARG, "segment %lld: bad offsets", (long long)i);
+        if (len == 0) return fail(PBX_E_BADARG, "segment %lld is empty", (long long)i);
+        if (len > 0x7fffffffull) return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
+        const int32_t x0 = (int32_t)((i % gx) * s->seg_w), y0 = (int32_t)((sr0 + i / gx) * s->seg_h);
+        const int32_t rows = s->tiled ? s->seg_h : std::min(s->seg_h, size_y - y0);
+        char what[48];
+        snprintf(what, sizeof what, "segment %lld", (long long)i);
+        // An abbreviated segment (no DQT / DHT of its own: the normal case under tag 347) that
+        // names the tables an earlier one of this layer named has that one's set: nothing is
+        // copied, built or compared for it.
+        JpegHeader H;
+        bool own = false;
+        if (int rc = jpeg_parse_header(s->data + o, len, nullptr, &own, H, what)) return rc;
+        JpegTables mine;
+        if (own) {
+            mine = base;
+            H = JpegHeader();
+            if (int rc = jpeg_parse_header(s->data + o, len, &mine, &own, H, what)) return rc;
+        }
+        const JpegTables& T = own ? mine : base;
+        if ((int64_t)H.width != s->seg_w || (int64_t)H.height != rows)
+            return fail(PBX_E_BADARG, "%s: SOF size %u x %u != segment size %d x %d", what, H.width, H.height, s->seg_w, rows);
+        if ((int)H.ncomp != spp)
+            return fail(PBX_E_BADARG, "%s: a stream of %u components in segments of %d samples per pixel", what, H.ncomp, spp);
+        uint32_t mode = JM_COPY;
+        if (H.ncomp == 1) {
+            if (H.h[0] != 1 || H.v[0] != 1)
+                return fail(PBX_E_BADARG, "%s: sampling factors %ux%u on a one-component stream (1x1)", what, H.h[0], H.v[0]);
+        } else {
+            const bool sub = H.h[0] != 1 || H.v[0] != 1;
+            if (H.h[1] != 1 || H.v[1] != 1 || H.h[2] != 1 || H.v[2] != 1 ||
+                !((H.h[0] == 1 && H.v[0] == 1) || (H.h[0] == 2 && H.v[0] == 1) || (H.h[0] == 2 && H.v[0] == 2)))
+                return fail(PBX_E_BADARG, "%s: sampling factors %ux%u, %ux%u, %ux%u (luma 1x1, 2x1 or 2x2 with chroma 1x1)", what,
+                            H.h[0], H.v[0], H.h[1], H.v[1], H.h[2], H.v[2]);
+            if (sub && !j->ycbcr)
+                return fail(PBX_E_BADARG, "%s: subsampling %ux%u without PhotometricInterpretation 6 (YCbCr)", what, H.h[0], H.v[0]);
+            mode = !j->ycbcr ? JM_COPY : H.h[0] == 1 ? JM_YCC : H.v[0] == 1 ? JM_YCC_H2V1 : JM_YCC_H2V2;
+        }
+        uint64_t names = H.ncomp;  // which tables the frame and the scan name
+        for (uint32_t c = 0; c < H.ncomp; c++) names = names << 6 | H.tq[c] << 4 | H.td[c] << 2 | H.ta[c];
+        uint32_t tabset = ~0u;
+        if (!own)
+            for (const auto& kn : known)
+                if (kn.first == names) tabset = kn.second;
+        JTabSet ts;
+        if (tabset == ~0u) memset(&ts, 0, sizeof ts);
+        for (uint32_t c = 0; c < H.ncomp && tabset == ~0u; c++) {
+            if (!T.qset[H.tq[c]]) return fail(PBX_E_BADARG, "%s: missing quantiser %u (component %u)", what, H.tq[c], c);
+            if (!T.hset[0][H.td[c]]) return fail(PBX_E_BADARG, "%s: missing Huffman table DC %u (component %u)", what, H.td[c], c);
+            if (!T.hset[1][H.ta[c]]) return fail(PBX_E_BADARG, "%s: missing Huffman table AC %u (component %u)", what, H.ta[c], c);
+            static const uint8_t nat[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+            for (int k = 0; k < 64; k++) ts.q[c][nat[k]] = T.q[H.tq[c]][k];
+            jpeg_build_huff(T.bits[0][H.td[c]], T.vals[0][H.td[c]], ts.h[2 * c]);
+            jpeg_build_huff(T.bits[1][H.ta[c]], T.vals[1][H.ta[c]], ts.h[2 * c + 1]);
+        }
+        if (tabset == ~0u) {
+            tabset = 0;
+            while (tabset < P.jtabs.size() && memcmp(&P.jtabs[tabset], &ts, sizeof ts)) tabset++;
+            if (tabset == P.jtabs.size()) P.jtabs.push_back(ts);
+            if (!own) known.emplace_back(names, tabset);
+        }
+        const uint32_t hs = H.ncomp == 3 ? H.h[0] : 1, vs = H.ncomp == 3 ? H.v[0] : 1;
+        const uint32_t mcux = (H.width + 8 * hs - 1) / (8 * hs), mcuy = (H.height + 8 * vs - 1) / (8 * vs);
+        const uint32_t pitch0 = (mcux * hs * 8 + 15) & ~15u, pitchc = (mcux * 8 + 15) & ~15u;
+        const uint64_t size0 = ((uint64_t)pitch0 * mcuy * vs * 8 + 255) & ~255ull;
+        const uint64_t sizec = H.ncomp == 3 ? ((uint64_t)pitchc * mcuy * 8 + 255) & ~255ull : 0;
+        if (size0 + 2 * sizec > 0x7fffffffull) return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
+        const uint64_t dstoff = P.scratch;
+        P.scratch += size0 + 2 * sizec;
+        P.jstreams.push_back(JStream{o + in_base + H.data, dstoff, (uint32_t)(len - H.data), tabset, H.ncomp, hs, vs, mcux,
+                                     mcuy, H.restart, pitch0, pitchc, (uint32_t)size0, (uint32_t)(size0 + sizec)});
+        P.jsegs.push_back(TJpegSeg{dstoff, (uint32_t)size0, (uint32_t)(size0 + sizec), pitch0, pitchc, H.width, H.height, x0,
+                                   y0, mode, H.ncomp, dst, 0});
+        P.jseg_rows = std::max(P.jseg_rows, H.height);
+        if (dlen_sum) *dlen_sum += (uint64_t)H.width * H.height * H.ncomp;
+    }
+    return PBX_OK;
+}
+
 // pbx_band_write_tiff: pbx_band_write_zarr for segment rows.  The piece's covering segment rows
 // are planned on the host first (a malformed piece never joins the band's load), then uploaded,
 // decoded and placed under the band state machine of band_load_rows.
 // With spp > 1 the segments are chunky and only component `sample` is written (the others'
 // destinations are null).
+// With `j` (pbx_band_write_tiff_jpeg) the segments are JPEG streams: tiff_jpeg_plan, and the one
+// TSplitDst entry for one-sample segments too.
 int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
-                    int32_t spp, int32_t sample, double* kernel_ms) {
+                    int32_t spp, int32_t sample, double* kernel_ms, const pbx_tiff_jpeg* j = nullptr) {
     int32_t k = 0;
     if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
-    if (int rc = tiff_segments_check(s)) return rc;
+    if (j) {
+        if (int rc = tiff_jpeg_check(s, j, q->pixel_type, spp)) return rc;
+    } else if (int rc = tiff_segments_check(s)) {
+        return rc;
+    }
     if (int rc = tiff_samples_check(spp, sample, bpp_of(q->pixel_type))) return rc;
     if (s->predictor == 2 && (q->pixel_type == PBX_FLOAT || q->pixel_type == PBX_DOUBLE))
         return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)q->id);
@@ -2973,7 +3332,9 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     const int64_t gx = s->tiled ? ((int64_t)q->size_x + s->seg_w - 1) / s->seg_w : 1;
     const int64_t sr0 = y0 / s->seg_h, sr1 = ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h;
     ZarrPlan P;
-    if (int rc = tiff_plan(q->size_x, q->size_y, bpp, !q->little_endian, s, 0, 0, P, nullptr, true, sr0, sr1, spp, 0))
+    if (j) {
+        if (int rc = tiff_jpeg_plan(q->size_x, q->size_y, s, j, 0, P, sr0, sr1, spp, 0)) return rc;
+    } else if (int rc = tiff_plan(q->size_x, q->size_y, bpp, !q->little_endian, s, 0, 0, P, nullptr, true, sr0, sr1, spp, 0))
         return rc;
     const uint64_t used = s->offsets[gx * (sr1 - sr0)], len = (used + 15) & ~15ull;
     const std::vector<ZarrInput> in{ZarrInput{s->data, used, 0, len}};
@@ -2982,7 +3343,7 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
         const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
                                             q->size_y, s->seg_w, s->seg_h, (uint32_t)bpp, 0, 0, y0, y0 + rows}};
         std::vector<TSplitDst> sd;
-        if (spp > 1) {
+        if (spp > 1 || j) {
             sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, q->pitch, q->size_x, q->size_y, y0, y0 + rows,
                                    (uint32_t)bpp, q->little_endian ? 0u : 1u, (uint32_t)spp, (uint32_t)s->predictor});
             sd[0].dev[sample] = zp[0].dev;
@@ -3002,14 +3363,20 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
 // each at most once, all split out of the one decode by k_tiff_split_place.
 int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
                          uint64_t n_layers, const pbx_zarr_chunks* zs, const int32_t* depths,
-                         uint64_t* plane_ids, double* kernel_ms, const pbx_tiff_segments* ts = nullptr) {
+                         uint64_t* plane_ids, double* kernel_ms, const pbx_tiff_segments* ts = nullptr,
+                         const pbx_tiff_jpeg* tj = nullptr) {  // tj: the TIFF layers are JPEG streams
     std::vector<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t>> keys;
     std::vector<std::vector<ZarrWant>> want(n_layers);
     for (uint64_t k = 0; k < n; k++) {
         const pbx_plane_desc* d = &ds[k];
         if (refs[k].layer >= n_layers) return fail(PBX_E_BADARG, "plane %llu: no layer %u", (unsigned long long)k, refs[k].layer);
         if (ts) {
-            if (int rc = tiff_segments_check(&ts[refs[k].layer])) return rc;
+            if (tj) {
+                if (int rc = tiff_jpeg_check(&ts[refs[k].layer], &tj[refs[k].layer], d->pixel_type, depths[refs[k].layer]))
+                    return rc;
+            } else if (int rc = tiff_segments_check(&ts[refs[k].layer])) {
+                return rc;
+            }
             if (ts[refs[k].layer].predictor == 2 && (d->pixel_type == PBX_FLOAT || d->pixel_type == PBX_DOUBLE))
                 return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)k);
             if (int rc = tiff_fp_predictor_check(&ts[refs[k].layer], d->pixel_type)) return rc;
@@ -3073,10 +3440,13 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
             const pbx_tiff_segments* s = &ts[l];
             const int bpp = bpp_of(d->pixel_type);
             const bool big = d->byte_order != PBX_LITTLE_ENDIAN;
-            if (int rc = tiff_plan(d->size_x, d->size_y, bpp, big, s, in_base[l], want[l][0].plane, P, nullptr, false,
-                                   0, -1, depths[l], (uint32_t)sd.size()))
+            if (tj) {
+                if (int rc = tiff_jpeg_plan(d->size_x, d->size_y, s, &tj[l], in_base[l], P, 0, -1, depths[l], (uint32_t)sd.size()))
+                    return rc;
+            } else if (int rc = tiff_plan(d->size_x, d->size_y, bpp, big, s, in_base[l], want[l][0].plane, P, nullptr, false,
+                                          0, -1, depths[l], (uint32_t)sd.size()))
                 return rc;
-            if (depths[l] > 1) {
+            if (depths[l] > 1 || tj) {
                 sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255,
                                        d->size_x, d->size_y, 0, d->size_y, (uint32_t)bpp, big && bpp > 1 ? 1u : 0u,
                                        (uint32_t)depths[l], (uint32_t)s->predictor});
@@ -3218,6 +3588,51 @@ int pbx_planes_register_tiff_samples(pbx_ctx* ctx, uint64_t n, const pbx_plane_d
         return fail(PBX_E_BADARG, "null argument");
     if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
     return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms, layers);
+}
+
+int pbx_planes_register_tiff_jpeg(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
+                                  uint64_t n_layers, const pbx_tiff_segments* layers, const int32_t* samples_per_pixel,
+                                  const pbx_tiff_jpeg* jpeg, uint64_t* plane_ids, double* kernel_ms) {
+    if (!ctx || !ds || !refs || !layers || !samples_per_pixel || !jpeg || !plane_ids || n == 0 || n_layers == 0)
+        return fail(PBX_E_BADARG, "null argument");
+    if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms, layers, jpeg);
+}
+
+int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
+                             int32_t samples_per_pixel, int32_t sample, const pbx_tiff_jpeg* jpeg, double* kernel_ms) {
+    if (!ctx || !s || !jpeg) return fail(PBX_E_BADARG, "null argument");
+    int rc;
+    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
+    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
+    rc = band_write_tiff(ctx, q, y0, rows, s, samples_per_pixel, sample, kernel_ms, jpeg);
+    const std::string msg = g_err;
+    unpin_one(ctx, q);
+    g_err = msg;
+    return rc;
+}
+
+int pbx_test_tiff_jpeg_plan(const pbx_tiff_segments* s, const pbx_tiff_jpeg* jpeg, int32_t size_x, int32_t size_y,
+                            int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[6]) {
+    if (!s || !jpeg || !out) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = tiff_jpeg_check(s, jpeg, PBX_UINT8, samples_per_pixel)) return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    if (rows < 0 || y0 < 0 || (int64_t)y0 + rows > size_y)
+        return fail(PBX_E_BADARG, "rows %d+%d outside the plane (%d rows)", y0, rows, size_y);
+    ZarrPlan P;
+    uint64_t sum = 0;
+    const bool band = rows > 0;
+    if (int rc = tiff_jpeg_plan(size_x, size_y, s, jpeg, 0, P, band ? y0 / s->seg_h : 0,
+                                band ? ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h : -1, samples_per_pixel, 0, &sum))
+        return rc;
+    out[0] = P.jstreams.size();
+    out[1] = sum;
+    out[2] = P.scratch;
+    out[3] = P.jtabs.size();
+    out[4] = P.jsegs.empty() ? 0 : P.jsegs[0].mode;
+    out[5] = 0;
+    for (const JStream& t : P.jstreams) out[5] += t.csize;
+    return PBX_OK;
 }
 
 int pbx_test_tiff_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t bpp, uint64_t out[4]) {

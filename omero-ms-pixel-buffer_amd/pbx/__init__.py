@@ -99,6 +99,22 @@ class PbxTiffSegments(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("data", ctypes.c_void_p), ("offsets", ctypes.c_void_p)]
 
 
+class PbxTiffJpeg(ctypes.Structure):
+    _fields_ = [("tables", ctypes.c_void_p), ("tables_len", ctypes.c_uint64), ("ycbcr", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+def _fill_tiff_jpeg(j: "PbxTiffJpeg", jpeg: Mapping) -> object:
+    """pbx_tiff_jpeg from a spec's `jpeg` dict (tables = tag 347's bytes or None, ycbcr); returns
+    the buffer the struct points into, to be kept alive over the call."""
+    tables = jpeg.get("tables")
+    buf = ctypes.create_string_buffer(bytes(tables), len(tables)) if tables else None
+    j.tables = ctypes.addressof(buf) if buf is not None else None
+    j.tables_len = len(tables) if tables else 0
+    j.ycbcr, j.reserved = 1 if jpeg.get("ycbcr") else 0, 0
+    return buf
+
+
 class PbxZarrSlice(ctypes.Structure):
     _fields_ = [("layer", ctypes.c_uint32), ("slice", ctypes.c_uint32)]
 
@@ -164,7 +180,8 @@ EXPORTS = [
     "pbx_band_write_zarr", "pbx_planes_register_zarr_deep", "pbx_band_write_zarr_deep",
     "pbx_test_zarr_plan", "pbx_planes_register_tiff", "pbx_test_tiff_plan",
     "pbx_band_write_tiff", "pbx_test_tiff_band_plan", "pbx_planes_register_tiff_samples",
-    "pbx_band_write_tiff_sample", "pbx_test_tiff_plan_samples",
+    "pbx_band_write_tiff_sample", "pbx_test_tiff_plan_samples", "pbx_planes_register_tiff_jpeg",
+    "pbx_band_write_tiff_jpeg", "pbx_test_tiff_jpeg_plan",
 ]
 
 _lib = None
@@ -272,6 +289,15 @@ def lib() -> ctypes.CDLL:
                                              ctypes.POINTER(ctypes.c_double)]
     L.pbx_test_tiff_plan_samples.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, i32, i32,
                                              ctypes.POINTER(u64)]
+    L.pbx_planes_register_tiff_jpeg.argtypes = [vp, u64, ctypes.POINTER(PbxPlaneDesc),
+                                                ctypes.POINTER(PbxZarrSlice), u64,
+                                                ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(i32),
+                                                ctypes.POINTER(PbxTiffJpeg), ctypes.POINTER(u64),
+                                                ctypes.POINTER(ctypes.c_double)]
+    L.pbx_band_write_tiff_jpeg.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxTiffSegments), i32, i32,
+                                           ctypes.POINTER(PbxTiffJpeg), ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_tiff_jpeg_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(PbxTiffJpeg), i32, i32,
+                                          i32, i32, i32, ctypes.POINTER(u64)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -761,6 +787,7 @@ def pack_chunks(chunks: Sequence[Optional[bytes]]):
 
 TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
 TIFF_ZSTD = 50000
+TIFF_JPEG = 7  # through the pbx_*_tiff_jpeg calls only
 _TIFF_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4,
                    16: 8, 17: 8, 18: 8}
 _TIFF_INT_FMT = {1: "B", 3: "H", 4: "I", 13: "I", 16: "Q", 18: "Q", 6: "b", 8: "h", 9: "i", 17: "q"}
@@ -768,7 +795,7 @@ _TIFF_TAGS = {256: "width", 257: "length", 258: "bits", 259: "compression", 262:
               266: "fillorder", 270: "description", 273: "strip_offsets", 274: "orientation", 277: "spp",
               278: "rows_per_strip", 279: "strip_counts", 284: "planar", 317: "predictor", 322: "tile_w",
               323: "tile_h", 324: "tile_offsets", 325: "tile_counts", 330: "subifd_offsets",
-              338: "extrasamples", 339: "sampleformat"}
+              338: "extrasamples", 339: "sampleformat", 347: "jpeg_tables", 530: "ycbcr_subsampling"}
 _TIFF_MAX_IFDS = 1 << 16
 _TIFF_PIXEL_TYPES = {(1, 8): UINT8, (2, 8): INT8, (1, 16): UINT16, (2, 16): INT16, (1, 32): UINT32,
                      (2, 32): INT32, (3, 32): FLOAT, (3, 64): DOUBLE}
@@ -779,7 +806,8 @@ def tiff_ifds(path: str) -> List[dict]:
     without any pixel data.  One dict per main IFD: width, length, bits (BitsPerSample),
     sampleformat, spp (SamplesPerPixel), bits_count / sampleformat_count (how many values those
     two tags hold; 1 if absent), planar (PlanarConfiguration, default 1), photometric (None if
-    absent), extrasamples (a list), compression, predictor, fillorder, orientation, tiled,
+    absent), extrasamples (a list), jpeg_tables (tag 347's bytes or None), ycbcr_subsampling (tag
+    530's two values or None), compression, predictor, fillorder, orientation, tiled,
     seg_w x seg_h (TileWidth x TileLength, or ImageWidth x RowsPerStrip capped at the length),
     offsets / counts of the segments, description (ImageDescription or None), byteorder ("<" or
     ">"), bigtiff, subifds (such dicts).  Every offset and count is checked against the file
@@ -831,6 +859,10 @@ def tiff_ifds(path: str) -> List[dict]:
                 if name is None:
                     continue
                 tsz = _TIFF_TYPE_SIZE.get(typ)
+                if tag == 347 and typ in (1, 7):  # JPEGTables: UNDEFINED (or BYTE) bytes, kept as they are
+                    d[name] = e[4 + inline:4 + inline + count] if count <= inline else \
+                        read(struct.unpack(bo + off_fmt, e[4 + inline:])[0], count, "the value of tag 347")
+                    continue
                 if tsz is None or (typ != 2 and typ not in _TIFF_INT_FMT):
                     raise PbxError(400, "%s: tag %d has field type %d" % (path, tag, typ))
                 nbytes = tsz * count
@@ -865,6 +897,8 @@ def tiff_ifds(path: str) -> List[dict]:
                        planar=one("planar", 1),
                        photometric=one("photometric") if "photometric" in d else None,
                        extrasamples=list(d.get("extrasamples", [])),
+                       jpeg_tables=d.get("jpeg_tables"),
+                       ycbcr_subsampling=list(d["ycbcr_subsampling"]) if "ycbcr_subsampling" in d else None,
                        bits_count=len(d["bits"]) if "bits" in d else 1,
                        sampleformat_count=len(d["sampleformat"]) if "sampleformat" in d else 1)
             if out["width"] < 1 or out["length"] < 1:
@@ -899,18 +933,138 @@ def tiff_ifds(path: str) -> List[dict]:
         return ifds
 
 
+_JPEG_SOF_NAMES = {0xC1: "SOF1 (extended sequential)", 0xC2: "SOF2 (progressive)", 0xC3: "SOF3 (lossless)",
+                   0xC5: "SOF5 (differential)", 0xC6: "SOF6 (differential progressive)",
+                   0xC7: "SOF7 (differential lossless)", 0xC9: "SOF9 (arithmetic coding)",
+                   0xCA: "SOF10 (progressive, arithmetic coding)", 0xCB: "SOF11 (lossless, arithmetic coding)",
+                   0xCD: "SOF13 (arithmetic coding)", 0xCE: "SOF14 (arithmetic coding)",
+                   0xCF: "SOF15 (arithmetic coding)"}
+
+
+def jpeg_header(data: bytes, what: str) -> dict:
+    """The marker segments of a JPEG stream up to its first SOS header (no entropy-coded byte is
+    read): precision, height, width, components = [(id, h, v, tq)], scan_components, dqt = [(pq,
+    tq)], dht = [(tc, th)], restart (DRI, 0 if none), sof (the SOFn code), data = the offset
+    after the SOS header.  A tables-only stream (tag 347) ends at EOI: sof and data are None.
+    PbxError 400 with `what` for a stream that does not start with SOI or is cut short."""
+    n = len(data)
+    if n < 2 or data[0] != 0xFF or data[1] != 0xD8:
+        raise PbxError(400, "%s does not start with SOI" % what)
+    out = dict(precision=None, height=None, width=None, components=[], scan_components=None, dqt=[], dht=[],
+               restart=0, sof=None, data=None)
+    q = 2
+    while True:
+        if q >= n or data[q] != 0xFF:
+            raise PbxError(400, "%s: truncated header (no marker at byte %d)" % (what, q))
+        while q < n and data[q] == 0xFF:
+            q += 1
+        if q >= n:
+            raise PbxError(400, "%s: truncated header" % what)
+        code = data[q]
+        q += 1
+        if code == 0xD9:
+            return out
+        if code in (0xD8, 0x01, 0x00) or 0xD0 <= code <= 0xD7:
+            raise PbxError(400, "%s: marker FF %02X in the header" % (what, code))
+        if q + 2 > n:
+            raise PbxError(400, "%s: truncated header" % what)
+        L = data[q] << 8 | data[q + 1]
+        if L < 2 or q + L > n:
+            raise PbxError(400, "%s: truncated header (marker FF %02X of %d bytes)" % (what, code, L))
+        p = data[q + 2:q + L]
+        q += L
+        if code == 0xDB:
+            k = 0
+            while k < len(p):
+                out["dqt"].append((p[k] >> 4, p[k] & 15))
+                k += 65 + 64 * (p[k] >> 4)
+        elif code == 0xC4:
+            k = 0
+            while k + 17 <= len(p):
+                out["dht"].append((p[k] >> 4, p[k] & 15))
+                k += 17 + sum(p[k + 1:k + 17])
+        elif code == 0xDD and len(p) == 2:
+            out["restart"] = p[0] << 8 | p[1]
+        elif 0xC0 <= code <= 0xCF and code not in (0xC4, 0xC8, 0xCC):
+            if len(p) >= 6 and p[5] == 4:
+                raise PbxError(400, "%s: 4 components (CMYK / YCCK) are not supported" % what)
+            if len(p) < 6 or len(p) != 6 + 3 * p[5]:
+                raise PbxError(400, "%s: truncated SOF" % what)
+            out.update(sof=code, precision=p[0], height=p[1] << 8 | p[2], width=p[3] << 8 | p[4],
+                       components=[(p[6 + 3 * c], p[7 + 3 * c] >> 4, p[7 + 3 * c] & 15, p[8 + 3 * c])
+                                   for c in range(p[5])])
+        elif code == 0xCC:
+            out["sof"] = out["sof"] or 0xCC
+        elif code == 0xDA:
+            if not p or len(p) != 4 + 2 * p[0]:
+                raise PbxError(400, "%s: truncated SOS" % what)
+            out["scan_components"] = p[0]
+            out["data"] = q
+            return out
+
+
+def _tiff_jpeg_first_segment(path: str, ifd: dict, spp: int) -> None:
+    """What the IFD and the first segment's header show of a Compression-7 file this library cannot
+    load: PbxError 400 with the reason (the C-ABI checks every segment again)."""
+    what = "%s: Compression 7: " % path
+    if ifd.get("jpeg_tables") is not None:
+        jpeg_header(bytes(ifd["jpeg_tables"]), what + "JPEGTables")
+    if not ifd["offsets"]:
+        return
+    with open(path, "rb") as f:
+        f.seek(ifd["offsets"][0])
+        data = f.read(ifd["counts"][0])  # the whole segment: APPn data may push the SOS anywhere in it
+    h = jpeg_header(data, what + "segment 0")
+    if h["sof"] is None:
+        raise PbxError(400, what + "segment 0: no SOF before the scan")
+    if h["sof"] != 0xC0:
+        raise PbxError(400, what + "segment 0: %s is not supported (baseline SOF0 only)"
+                       % ("arithmetic coding (DAC)" if h["sof"] == 0xCC else _JPEG_SOF_NAMES[h["sof"]]))
+    if h["precision"] != 8:
+        raise PbxError(400, what + "segment 0: sample precision %d (8 only)" % h["precision"])
+    comps = h["components"]
+    if len(comps) == 4:
+        raise PbxError(400, what + "segment 0: 4 components (CMYK / YCCK) are not supported")
+    if len(comps) != spp:
+        raise PbxError(400, what + "segment 0: a stream of %d components in segments of %d samples per pixel"
+                       % (len(comps), spp))
+    if any(pq for pq, _ in h["dqt"]):
+        raise PbxError(400, what + "segment 0: 16-bit quantiser (DQT with Pq = 1) is not supported")
+    rows = ifd["seg_h"] if ifd["tiled"] else min(ifd["seg_h"], ifd["length"])
+    if (h["width"], h["height"]) != (ifd["seg_w"], rows):
+        raise PbxError(400, what + "segment 0: SOF size %d x %d != segment size %d x %d"
+                       % (h["width"], h["height"], ifd["seg_w"], rows))
+    samp = [(c[1], c[2]) for c in comps]
+    if len(comps) == 1 and samp[0] != (1, 1):
+        raise PbxError(400, what + "segment 0: sampling factors %dx%d on a one-component stream (1x1)" % samp[0])
+    if len(comps) == 3:
+        if samp[1:] != [(1, 1), (1, 1)] or samp[0] not in ((1, 1), (2, 1), (2, 2)):
+            raise PbxError(400, what + "segment 0: sampling factors %s (luma 1x1, 2x1 or 2x2 with chroma 1x1)"
+                           % ", ".join("%dx%d" % s for s in samp))
+        if samp[0] != (1, 1) and ifd.get("photometric") != 6:
+            raise PbxError(400, what + "segment 0: subsampling %dx%d without PhotometricInterpretation 6 (YCbCr)"
+                           % samp[0])
+    if h["scan_components"] is not None and h["scan_components"] != len(comps):
+        raise PbxError(400, what + "segment 0: more than one scan (the first holds %d of %d components)"
+                       % (h["scan_components"], len(comps)))
+
+
 def _tiff_pixel_type(path: str, ifd: dict) -> int:
     """The pixel type of an IFD this library can load, else PbxError 400 with the reason.
-    SamplesPerPixel 1 to 4: every sample is a channel of that type, ExtraSamples included."""
+    SamplesPerPixel 1 to 4: every sample is a channel of that type, ExtraSamples included.
+    For a Compression-7 IFD the first segment is read and its header checked too, by every
+    caller (a band spec of no rows included: its refusals are tiff_plane_spec's)."""
     spp = ifd["spp"]
     if spp < 1 or spp > 4:
         raise PbxError(400, "%s: SamplesPerPixel %d (1 to 4 are supported)" % (path, spp))
     if spp > 1 and ifd.get("bits_count", 1) != spp:  # TIFF 6.0: one BitsPerSample value per sample
         raise PbxError(400, "%s: SamplesPerPixel %d with %d BitsPerSample value(s)"
                        % (path, spp, ifd.get("bits_count", 1)))
-    if spp > 1 and ifd.get("photometric") not in (None, 1, 2):
-        raise PbxError(400, "%s: PhotometricInterpretation %d with SamplesPerPixel %d (1 BlackIsZero or 2 RGB; "
-                       "palette, CMYK and YCbCr are not supported)" % (path, ifd["photometric"], spp))
+    jpeg = ifd["compression"] == TIFF_JPEG
+    if spp > 1 and ifd.get("photometric") not in (None, 1, 2) and not (jpeg and ifd["photometric"] == 6 and spp == 3):
+        raise PbxError(400, "%s: PhotometricInterpretation %d with SamplesPerPixel %d (1 BlackIsZero or 2 RGB, 6 YCbCr "
+                       "with 3 samples under Compression 7; palette and CMYK are not supported)"
+                       % (path, ifd["photometric"], spp))
     if ifd.get("planar", 1) not in (1, 2):
         raise PbxError(400, "%s: PlanarConfiguration %d (1 chunky or 2 planar)" % (path, ifd["planar"]))
     if ifd["bits"] not in (8, 16, 32, 64):
@@ -921,9 +1075,25 @@ def _tiff_pixel_type(path: str, ifd: dict) -> int:
     if pt is None:
         raise PbxError(400, "%s: SampleFormat %d with %d bits is none of the pixel types"
                        % (path, ifd["sampleformat"], ifd["bits"]))
-    if ifd["compression"] not in (1, 5, 8, 32946, TIFF_ZSTD):
+    if jpeg and pt != UINT8:
+        raise PbxError(400, "%s: Compression %d (1 none, 5 LZW, 7 JPEG on 8-bit samples, 8 / 32946 deflate, 50000 zstd)"
+                       % (path, ifd["compression"]))
+    if ifd["compression"] not in (1, 5, 8, 32946, TIFF_ZSTD) and not jpeg:  # (the text older callers match)
         raise PbxError(400, "%s: Compression %d (1 none, 5 LZW, 8 / 32946 deflate, 50000 zstd)"
                        % (path, ifd["compression"]))
+    if jpeg:
+        planar = spp > 1 and ifd.get("planar", 1) == 2
+        if ifd["predictor"] != 1:
+            raise PbxError(400, "%s: Predictor %d with Compression 7 (JPEG segments take 1 only)" % (path, ifd["predictor"]))
+        if spp not in (1, 3) and not planar:
+            raise PbxError(400, "%s: Compression 7 with SamplesPerPixel %d (1, or 3 chunky; 4 components, CMYK / YCCK, "
+                           "are not supported)" % (path, spp))
+        if ifd.get("photometric") == 6 and planar:
+            raise PbxError(400, "%s: PhotometricInterpretation 6 (YCbCr) with PlanarConfiguration 2 under Compression 7"
+                           % path)
+        if ifd.get("photometric") == 6 and spp != 3:
+            raise PbxError(400, "%s: PhotometricInterpretation 6 (YCbCr) with SamplesPerPixel %d" % (path, spp))
+        _tiff_jpeg_first_segment(path, ifd, 1 if planar else spp)
     if ifd["predictor"] not in (1, 2, 3):
         raise PbxError(400, "%s: Predictor %d (1, 2, or 3 on floating-point samples)" % (path, ifd["predictor"]))
     if ifd["predictor"] == 3 and pt not in (FLOAT, DOUBLE):
@@ -983,7 +1153,12 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
                 if f.readinto(memoryview(data)[int(offsets[k]):int(offsets[k]) + n]) != n:
                     raise PbxError(400, "%s: segment %d is truncated" % (path, k0 + k))
         segments = (data, offsets)
-    return dict(samples_per_pixel=1 if planar else spp, sample=0 if planar else sample, pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
+    extra = {}
+    if ifd["compression"] == TIFF_JPEG:  # -> the pbx_*_tiff_jpeg calls
+        tables = ifd.get("jpeg_tables")
+        extra["jpeg"] = dict(tables=bytes(tables) if tables is not None else None,
+                             ycbcr=ifd.get("photometric") == 6 and not planar)
+    return dict(extra, samples_per_pixel=1 if planar else spp, sample=0 if planar else sample, pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
                 big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"], seg_h=ifd["seg_h"],
                 tiled=ifd["tiled"],
                 compression=TIFF_DEFLATE if ifd["compression"] == 32946 else ifd["compression"],
@@ -997,7 +1172,8 @@ def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0) ->
     seg_w, seg_h, tiled, compression, predictor and segments = (data, offsets) of the segment
     rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 only, each full width; exactly those byte
     ranges of the file are read.  rows == 0 reads nothing (segments is None): the geometry and
-    byte order alone.  PbxError 400 as tiff_plane_spec, and for rows outside the plane."""
+    byte order alone (of a Compression-7 IFD also segment 0, whose header decides whether the file
+    can be loaded at all).  PbxError 400 as tiff_plane_spec, and for rows outside the plane."""
     if rows < 0 or y0 < 0 or y0 + rows > ifd["length"]:
         raise PbxError(400, "%s: rows %d+%d outside the image (%d rows)" % (path, y0, rows, ifd["length"]))
     sr0 = y0 // ifd["seg_h"]
@@ -1433,9 +1609,28 @@ class PixelsService:
         pack_chunks()' (data, offsets) pair) [, big_endian = the FILE's byte order, level,
         samples_per_pixel, sample].  Specs with samples_per_pixel > 1 (chunky segments of that many
         interleaved samples per pixel) that carry the SAME segments object are the samples of one
-        layer, uploaded and decoded once (pbx_planes_register_tiff_samples).  All are
+        layer, uploaded and decoded once (pbx_planes_register_tiff_samples).  Specs that carry
+        jpeg = dict(tables = tag 347's bytes or None, ycbcr) are JPEG segments (compression 7, UINT8
+        planes, samples_per_pixel 1 or 3) and go through pbx_planes_register_tiff_jpeg; a call
+        that mixes them with others (a file whose pages or levels differ in compression) is two
+        registrations, the others first, undone if the JPEG one fails.  All are
         registered or none.  Returns the plane ids (and the kernels' device ms with timing=True)."""
-        if any(p.get("samples_per_pixel", 1) != 1 for p in planes):
+        jp = [p.get("jpeg") is not None for p in planes]
+        if any(jp) and not all(jp):
+            rest = [k for k, j in enumerate(jp) if not j]
+            mine = [k for k, j in enumerate(jp) if j]
+            a, ta = self.register_tiff_planes([planes[k] for k in rest], timing=True)
+            try:
+                b, tb = self.register_tiff_planes([planes[k] for k in mine], timing=True)
+            except BaseException:
+                for pid in a:
+                    self.release_plane(pid)
+                raise
+            ids = [0] * len(planes)
+            for k, pid in list(zip(rest, a)) + list(zip(mine, b)):
+                ids[k] = pid
+            return (ids, (ta[0] + tb[0], ta[1] + tb[1])) if timing else ids
+        if any(jp) or any(p.get("samples_per_pixel", 1) != 1 for p in planes):
             return self._register_tiff_samples(planes, timing)
         n = len(planes)
         descs = (PbxPlaneDesc * n)()
@@ -1475,7 +1670,7 @@ class PixelsService:
                 if spp > 1:
                     layer_of[id(p["segments"])] = l
             elif any(layers[l].get(f) != p.get(f) for f in ("samples_per_pixel", "seg_w", "seg_h", "tiled",
-                                                             "compression", "predictor")):
+                                                             "compression", "predictor", "jpeg")):
                 raise PbxError(400, "plane %d: shares its segments with plane %d but not their layout"
                                % (k, planes.index(layers[l])))
             if not (0 <= sample < 2 ** 32):
@@ -1501,7 +1696,13 @@ class PixelsService:
             spps[l] = p.get("samples_per_pixel", 1)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
-        _check(lib().pbx_planes_register_tiff_samples(self._h, n, descs, rf, nl, sgs, spps, ids, ms))
+        if layers[0].get("jpeg") is not None:  # (all of them: register_tiff_planes)
+            jps = (PbxTiffJpeg * nl)()
+            for l, p in enumerate(layers):
+                keep.append(_fill_tiff_jpeg(jps[l], p["jpeg"]))
+            _check(lib().pbx_planes_register_tiff_jpeg(self._h, n, descs, rf, nl, sgs, spps, jps, ids, ms))
+        else:
+            _check(lib().pbx_planes_register_tiff_samples(self._h, n, descs, rf, nl, sgs, spps, ids, ms))
         del keep
         return (list(ids), (ms[0], ms[1])) if timing else list(ids)
 
@@ -1659,7 +1860,7 @@ class PixelsService:
 
     def band_write_tiff(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
                         compression: int, predictor: int, segments, timing: bool = False,
-                        samples_per_pixel: int = 1, sample: int = 0):
+                        samples_per_pixel: int = 1, sample: int = 0, jpeg: Optional[Mapping] = None):
         """pbx_band_write_tiff: rows [y0, y0 + rows) of one band, decoded on the GPU from the TIFF
         segment rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 that cover them (strips, or
         rows of tiles at full width, C order: a sequence of bytes, or pack_chunks()' (data,
@@ -1674,7 +1875,13 @@ class PixelsService:
         s.compression, s.predictor, s.flags = compression, predictor, 0
         s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
         ms = (ctypes.c_double * 2)()
-        if samples_per_pixel == 1 and sample == 0:
+        if jpeg is not None:  # JPEG segments (compression 7): a spec's `jpeg` dict, tables and ycbcr
+            j = PbxTiffJpeg()
+            keep = _fill_tiff_jpeg(j, jpeg)
+            _check(lib().pbx_band_write_tiff_jpeg(self._h, plane_id, y0, rows, ctypes.byref(s), samples_per_pixel,
+                                                  sample, ctypes.byref(j), ms))
+            del keep
+        elif samples_per_pixel == 1 and sample == 0:
             _check(lib().pbx_band_write_tiff(self._h, plane_id, y0, rows, ctypes.byref(s), ms))
         else:
             _check(lib().pbx_band_write_tiff_sample(self._h, plane_id, y0, rows, ctypes.byref(s),
@@ -1837,7 +2044,8 @@ class PixelsService:
                                                      tsp["tiled"], tsp["compression"], tsp["predictor"],
                                                      tsp["segments"],
                                                      samples_per_pixel=tsp.get("samples_per_pixel", 1),
-                                                     sample=tsp.get("sample", 0))
+                                                     sample=tsp.get("sample", 0),
+                                                     **({"jpeg": tsp["jpeg"]} if tsp.get("jpeg") is not None else {}))
                             elif sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
