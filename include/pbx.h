@@ -384,14 +384,17 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * single-sample segments already and go through the calls below.
  * Not supported (400 by the caller or here): SamplesPerPixel > 4, Predictor 3 on integer or
  * chunky multi-sample (RGB float) data, half-precision samples, FillOrder 2, pre-6.0 (LSB-first)
- * LZW streams, PackBits / LZMA / LERC / WebP / JPEG 2000 / JPEG XR and other compressions, CMYK /
- * palette colour, sub-byte or 12-bit samples.  JPEG (Compression 7, baseline, 8-bit, gray / RGB /
+ * LZW streams, PackBits / LZMA / LERC / WebP / JPEG XR and other compressions, CMYK /
+ * palette colour, sub-byte or 12-bit samples.  Lossless JPEG 2000 (the reversible 5/3 path) goes
+ * through the pbx_*_tiff_j2k calls further down and through no other; the irreversible 9/7 path
+ * ("JPEG-2000 Lossy", Aperio SVS) is not supported.  JPEG (Compression 7, baseline, 8-bit, gray / RGB /
  * YCbCr) goes through the pbx_*_tiff_jpeg calls further down and through no other: old-style JPEG
  * (Compression 6), progressive, lossless, arithmetic-coded and 12-bit streams, YCbCr under any
  * other compression, and the Aperio habit of YCbCr data under PhotometricInterpretation 2 (stored
  * as it is, libtiff's rule) are not supported.
  * The JNI shim does not wrap these calls (as the deep Zarr calls). */
 enum pbx_tiff_compression { PBX_TIFF_JPEG = 7 /* through the pbx_*_tiff_jpeg calls only */,
+                            PBX_TIFF_J2K = 34712 /* through the pbx_*_tiff_j2k calls only */,
                             PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8, PBX_TIFF_ZSTD = 50000 };
 typedef struct pbx_tiff_segments {
     int32_t seg_w, seg_h;       /* tiles: TileWidth x TileLength (edge tiles are full, padded);
@@ -513,6 +516,41 @@ int pbx_planes_register_tiff_jpeg(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc
 int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                              const pbx_tiff_segments* segs, int32_t samples_per_pixel, int32_t sample,
                              const pbx_tiff_jpeg* jpeg, double* kernel_ms);
+/* JPEG 2000 segments (TIFF Compression 33003, 33004, 33005 and 34712, which all hand over as
+ * compression = PBX_TIFF_J2K; DESIGN.md section 10b "JPEG 2000 segments"): every strip or tile is
+ * one raw codestream (FF4F FF51 ...) of one tile of exactly the segment's size -- TileWidth x
+ * TileLength, or ImageWidth x the strip's own row count.  Only the reversible path is decoded: the
+ * 5/3 wavelet, no quantisation, optionally the reversible colour transform, so the planes equal
+ * the encoder's input bit for bit.  The host reads SIZ, COD and QCD only; packet headers
+ * (k_tiff_j2k_packets), the MQ and bit-plane decoder (k_tiff_j2k_blocks, one wave per code block),
+ * the inverse wavelet (k_tiff_j2k_idwt) and the colour transform, level shift and placement
+ * (k_tiff_j2k_place) run on the device.
+ * Components: 1 (samples_per_pixel 1) of precision 8 on a PBX_UINT8 plane or 16 on a PBX_UINT16
+ * plane, or 3 (samples_per_pixel 3, chunky) of precision 8, stored as they are or through the
+ * inverse RCT as the COD says.  0 .. 32 levels, any code-block size, all five progression orders,
+ * one layer, one precinct per resolution, code-block style 0; COM, TLM, PLM and PLT are skipped.
+ * pbx_planes_register_tiff_samples for such layers: compression must be PBX_TIFF_J2K and
+ * predictor 1 (the other TIFF calls keep answering "bad compression 34712").  Keys, all-or-none,
+ * staging, statuses and kernel_ms ([0] decode through the inverse wavelet, [1] placement) are
+ * shared with that call.  400 on the host, before anything is uploaded, names: a jp2 box instead
+ * of a codestream, a header cut short, the irreversible wavelet and quantisation styles 1 and 2,
+ * more than one layer, tile or tile-part, non-zero offsets, subsampled or signed components, a
+ * precision other than 8 or 16, three components at precision 16, 2 or more than 3 components, a
+ * SIZ size that is not the segment's, any code-block style bit, SOP or EPH markers, COC / QCC /
+ * POC / RGN / PPM / PPT / CRG markers, more than one precinct in a resolution.  400 from the
+ * device (nothing registered): "corrupt segment stream N (j2k, decoder code C)", C = 1 a packet
+ * header or packet data past the stream's end, 2 a malformed packet header, 3 zero bit-planes
+ * above the band's magnitude bit-planes or more passes than the bit-planes allow. */
+int pbx_planes_register_tiff_j2k(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
+                                 const pbx_zarr_slice* refs, uint64_t n_layers,
+                                 const pbx_tiff_segments* layers, const int32_t* samples_per_pixel,
+                                 uint64_t* plane_ids, double* kernel_ms);
+/* pbx_band_write_tiff_sample for JPEG 2000 segments: the covering segment rows are decoded for
+ * this call and sample `sample` alone is stored.  A device refusal fails the band's load as a bad
+ * LZW stream does. */
+int pbx_band_write_tiff_j2k(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                            const pbx_tiff_segments* segs, int32_t samples_per_pixel, int32_t sample,
+                            double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -810,6 +848,20 @@ int pbx_test_tiff_plan_samples(const pbx_tiff_segments* segs, int32_t size_x, in
  * the end of its SOS header to the end of its segment). */
 int pbx_test_tiff_jpeg_plan(const pbx_tiff_segments* segs, const pbx_tiff_jpeg* jpeg, int32_t size_x, int32_t size_y,
                             int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[6]);
+
+/* Test hook: the header parser and planner of pbx_planes_register_tiff_j2k (rows == 0: the whole
+ * plane) or pbx_band_write_tiff_j2k (rows >= 1, segs holding the covering segment rows only)
+ * alone, no context and no device call.  Returns the status (the message through
+ * pbx_last_error).  out: streams, code blocks, packets, scratch bytes. */
+int pbx_test_tiff_j2k_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t pixel_type,
+                           int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[4]);
+
+/* Test hook: the whole plane decoded on the CPU by the planner's tables and the device's own
+ * serial code (packet headers, MQ and bit-plane decoder), no context and no device call.  out:
+ * samples_per_pixel planes of size_x * size_y samples (uint8, or uint16 in host order), no
+ * pitch; out_bytes must be exactly that. */
+int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t pixel_type,
+                             int32_t samples_per_pixel, void* out, uint64_t out_bytes);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,225 @@
+// kernels_tiff_j2k.hip — JPEG 2000 TIFF segments (Compression 33003 / 33004 / 33005 / 34712: one
+// reversible codestream of one tile per strip or tile; DESIGN.md §10b "JPEG 2000 segments").
+// The host has read SIZ, COD and QCD and laid out every sub-band, code block and coefficient
+// from them (tiff_j2k_plan, runtime.cpp); packet headers and code-block bytes are read here only.
+//
+//   k_tiff_j2k_packets  tier 2, one wave per stream: the packet headers (tag trees, passes,
+//                       Lblock, lengths) into one J2Code per code block, every offset and
+//                       length checked against the stream's length before it is stored
+//   k_tiff_j2k_blocks   tier 1, one wave per code block: the MQ decoder and the three coding
+//                       passes over state in LDS, then the block's coefficients, two's
+//                       complement int32, row by row into its sub-band's rectangle
+//   k_tiff_j2k_idwt     the inverse 5/3 lifting, one workgroup per component, level by level
+//   k_tiff_j2k_place    inverse RCT, level shift, clamp, split and placement, clipped as
+//                       k_tiff_jpeg_place clips
+//
+// The serial halves (tiff_j2k_dev.h) are run by lane 0 of their wave; the lanes together clear
+// the state before it and store the coefficients after it.  An arithmetic decoder has one chain of
+// dependent decisions per code block, so the parallelism of tier 1 is across code blocks.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dev_util.h"
+#include "pbx_common.h"
+#include "pbx_kernels.h"
+#include "tiff_j2k_dev.h"
+#include "zarr_dev.h"
+
+namespace pbx {
+
+__constant__ uint32_t c_j2_mq[J2_MQ_STATES] = {PBX_MQ_TABLE};
+
+__global__ __launch_bounds__(64) void k_tiff_j2k_packets(const J2Stream* __restrict__ st, uint32_t n,
+                                                         const J2Band* __restrict__ bands,
+                                                         const uint8_t* __restrict__ src, uint32_t* tt, J2Code* code,
+                                                         uint32_t* __restrict__ err) {
+    const uint32_t si = blockIdx.x;
+    if (si >= n || threadIdx.x != 0) return;
+    const J2Stream S = st[si];
+    err[si] = j2k_packets(S, bands, src, tt, code);
+}
+
+// LDS: max_coef magnitudes, max_flag flag bytes (rounded up to 16), the contexts, the MQ table.
+__global__ __launch_bounds__(64) void k_tiff_j2k_blocks(const J2Block* __restrict__ blocks, uint32_t n,
+                                                        const J2Code* __restrict__ code,
+                                                        const J2Stream* __restrict__ st,
+                                                        const uint8_t* __restrict__ src, uint8_t* __restrict__ scratch,
+                                                        uint32_t max_coef, uint32_t max_flag) {
+    const uint32_t lane = threadIdx.x, bi = blockIdx.x;
+    if (bi >= n) return;
+    const J2Block B = blocks[bi];
+    const J2Code C = code[bi];
+    const J2Stream S = st[B.stream];
+    const uint32_t w = B.w, h = B.h, nco = w * h, nfl = (w + 2) * (h + 2);
+    if (nco > max_coef || nfl > max_flag) return;  // (the planner sized both from these blocks)
+    const uint32_t flg_off = 4 * max_coef, ctx_off = flg_off + ((max_flag + 15) & ~15u), tab_off = ctx_off + J2_CTX_BYTES;
+    int32_t* mag = (int32_t*)zlds;
+    uint8_t* flg = zlds + flg_off;
+    uint8_t* ctx = zlds + ctx_off;
+    uint32_t* tab = (uint32_t*)(zlds + tab_off);
+    for (uint32_t i = lane; i < nco; i += 64) mag[i] = 0;
+    for (uint32_t i = lane; i < (nfl + 3) / 4; i += 64) lds32(flg_off + 4 * i) = 0;  // (max_flag rounded up to 16)
+    if (lane < 19) ctx[lane] = lane == 0 ? 4 << 1 : lane == 17 ? 3 << 1 : lane == 18 ? 46 << 1 : 0;
+    if (lane < J2_MQ_STATES) tab[lane] = c_j2_mq[lane];
+    __syncthreads();
+    const uint32_t planes = (uint32_t)B.mb - C.zbp;
+    const bool ok = C.passes != 0 && C.zbp < B.mb && planes <= 31 && C.passes <= 3 * planes - 2 &&
+                    C.off <= S.len && C.len <= S.len - C.off;
+    if (ok && lane == 0)
+        j2k_block(mag, flg, ctx, tab, src + S.src_off + C.off, C.len, w, h, B.orient, planes, C.passes);
+    __syncthreads();
+    int32_t* out = (int32_t*)(scratch + B.dst);
+    for (uint32_t y = 0; y < h; y++)
+        for (uint32_t x = lane; x < w; x += 64) {
+            const int32_t v = mag[y * w + x];
+            out[(uint64_t)y * B.pitch + x] = (flg[(y + 1) * (w + 2) + x + 1] & J2F_NEG) ? -v : v;
+        }
+}
+
+// ------------------------------------------------------------------------------ inverse 5/3
+// One dimension of T.800 F.3 for a signal that starts on an even sample: `nl` low-pass samples
+// L(n) at the even places, `nh` = nl or nl - 1 high-pass samples H(n) at the odd ones, extended
+// by whole-sample symmetry.  The even output 2n is E(n) = L(n) - ((H(n - 1) + H(n) + 2) >> 2),
+// the odd one 2n + 1 is H(n) + ((E(n) + E(n + 1)) >> 1); a thread computes both of a pair and
+// recomputes its neighbour's E, so no thread waits for another inside a pass.
+template <class FL, class FH>
+__device__ __forceinline__ int32_t j2_even(uint32_t n, uint32_t nh, FL L, FH H) {
+    if (nh == 0) return L(n);
+    const int32_t hm = H(n ? n - 1 : 0u), hp = H(n < nh ? n : nh - 1);
+    return (int32_t)((uint32_t)L(n) - (uint32_t)((int32_t)((uint32_t)hm + (uint32_t)hp + 2u) >> 2));
+}
+
+constexpr uint32_t J2W_THREADS = 256;
+
+__global__ __launch_bounds__(J2W_THREADS) void k_tiff_j2k_idwt(const J2Comp* __restrict__ comps, uint32_t n,
+                                                               uint8_t* __restrict__ scratch) {
+    if (blockIdx.x >= n) return;
+    const J2Comp c = comps[blockIdx.x];
+    int32_t* A = (int32_t*)(scratch + c.a);
+    int32_t* Bp = (int32_t*)(scratch + c.b);
+    const uint64_t W = c.w;
+    const uint32_t NL = c.levels < 32 ? c.levels : 32;
+    for (uint32_t r = 1; r <= NL; r++) {
+        const uint32_t sh = NL - r;  // 0 .. 31
+        const uint32_t cw = (uint32_t)((c.w + (1ull << sh) - 1) >> sh), ch = (uint32_t)((c.h + (1ull << sh) - 1) >> sh);
+        const uint32_t lw = (cw + 1) / 2, lh = (ch + 1) / 2;  // resolution r - 1
+        if (cw == lw && ch == lh) continue;                   // 1 x 1: nothing to undo
+        const uint32_t hw = cw - lw, hh = ch - lh;
+        // rows: A's [L | H] halves -> B interleaved
+        for (uint64_t i = threadIdx.x; i < (uint64_t)ch * lw; i += J2W_THREADS) {
+            const uint32_t y = (uint32_t)(i / lw), k = (uint32_t)(i % lw);
+            const int32_t* row = A + y * W;
+            auto L = [&](uint32_t q) { return row[q]; };
+            auto H = [&](uint32_t q) { return row[lw + q]; };
+            const int32_t e0 = j2_even(k, hw, L, H);
+            Bp[y * W + 2 * k] = e0;
+            if (k < hw) {
+                const int32_t e1 = k + 1 < lw ? j2_even(k + 1, hw, L, H) : e0;
+                Bp[y * W + 2 * k + 1] = (int32_t)((uint32_t)H(k) + (uint32_t)((int32_t)((uint32_t)e0 + (uint32_t)e1) >> 1));
+            }
+        }
+        __syncthreads();
+        // columns: B's [L ; H] halves -> A interleaved
+        for (uint64_t i = threadIdx.x; i < (uint64_t)lh * cw; i += J2W_THREADS) {
+            const uint32_t k = (uint32_t)(i / cw), x = (uint32_t)(i % cw);
+            const int32_t* col = Bp + x;
+            auto L = [&](uint32_t q) { return col[q * W]; };
+            auto H = [&](uint32_t q) { return col[(lh + q) * W]; };
+            const int32_t e0 = j2_even(k, hh, L, H);
+            A[(2ull * k) * W + x] = e0;
+            if (k < hh) {
+                const int32_t e1 = k + 1 < lh ? j2_even(k + 1, hh, L, H) : e0;
+                A[(2ull * k + 1) * W + x] = (int32_t)((uint32_t)H(k) + (uint32_t)((int32_t)((uint32_t)e0 + (uint32_t)e1) >> 1));
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ------------------------------------------------------------------------------ placement
+// k_tiff_jpeg_place's geometry: a workgroup of four waves per (segment, run of J2P_ROWS segment
+// rows), rows clipped to run, window and plane, only the visible width walked, a lane per pixel.
+constexpr uint32_t J2P_WAVES = 4, J2P_ROWS = 16;
+
+__device__ __forceinline__ uint32_t j2_sample(int32_t v, uint32_t prec) {
+    const int32_t hi = (int32_t)((1u << prec) - 1u);
+    const int64_t s = (int64_t)v + (int64_t)(1u << (prec - 1));
+    return (uint32_t)(s < 0 ? 0 : s > hi ? hi : s);
+}
+
+__global__ __launch_bounds__(64 * J2P_WAVES) void k_tiff_j2k_place(const TJ2Seg* __restrict__ sg,
+                                                                   const TSplitDst* __restrict__ dt,
+                                                                   const uint8_t* __restrict__ scratch) {
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const TJ2Seg u = sg[blockIdx.x];
+    const TSplitDst d = dt[u.dst];
+    const uint32_t prec = u.prec == 16 ? 16u : 8u, bpp = prec == 16 ? 2u : 1u;
+    if (d.bpp != bpp) return;  // (the host checked the plane's pixel type against the precision)
+    const int32_t x0 = u.x0, y0 = u.y0, rows = (int32_t)u.rows;
+    int32_t r0 = (int32_t)(blockIdx.y * J2P_ROWS), r1 = r0 + (int32_t)J2P_ROWS;
+    const int32_t top = d.y_lo > 0 ? d.y_lo : 0, bottom = d.y_hi < d.sy ? d.y_hi : d.sy;
+    r1 = r1 < rows ? r1 : rows;
+    r0 = r0 > top - y0 ? r0 : top - y0;
+    r1 = r1 < bottom - y0 ? r1 : bottom - y0;
+    if (r0 >= r1 || x0 >= d.sx || x0 < 0 || y0 < 0) return;
+    const uint32_t wvis = (uint32_t)(d.sx - x0);
+    const uint32_t vis = wvis < u.w ? wvis : u.w;
+    const uint32_t nc = u.ncomp == 3 ? 3u : 1u;
+    const int32_t* p0 = (const int32_t*)(scratch + u.src[0]);
+    const int32_t* p1 = (const int32_t*)(scratch + u.src[nc == 3 ? 1 : 0]);
+    const int32_t* p2 = (const int32_t*)(scratch + u.src[nc == 3 ? 2 : 0]);
+    for (int32_t r = r0 + (int32_t)wv; r < r1; r += (int32_t)J2P_WAVES) {
+        const uint64_t at = (uint64_t)r * u.w;
+        for (uint32_t x = lane; x < vis; x += 64) {
+            int32_t v[3];
+            v[0] = p0[at + x];
+            if (nc == 3) {
+                v[1] = p1[at + x];
+                v[2] = p2[at + x];
+                if (u.rct) {  // G = Y - ((U + V) >> 2), R = V + G, B = U + G
+                    const int32_t g = (int32_t)((uint32_t)v[0] - (uint32_t)((int32_t)((uint32_t)v[1] + (uint32_t)v[2]) >> 2));
+                    const int32_t rr = (int32_t)((uint32_t)v[2] + (uint32_t)g), bb = (int32_t)((uint32_t)v[1] + (uint32_t)g);
+                    v[0] = rr;
+                    v[1] = g;
+                    v[2] = bb;
+                }
+            }
+#pragma unroll
+            for (uint32_t c = 0; c < 3; c++) {
+                if (c >= nc || !d.dev[c]) continue;
+                uint8_t* o = d.dev[c] + (int64_t)(y0 + r) * d.pitch + ((int64_t)x0 + x) * bpp;
+                const uint32_t s = j2_sample(v[c], prec);
+                if (bpp == 1) *o = (uint8_t)s;
+                else *(uint16_t*)o = d.big_endian ? (uint16_t)(s >> 8 | s << 8) : (uint16_t)s;
+            }
+        }
+    }
+}
+
+hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams, const J2Band* d_bands,
+                                  const J2Block* d_blocks, uint32_t n_blocks, const J2Comp* d_comps, uint32_t n_comps,
+                                  uint32_t max_coef, uint32_t max_flag, uint8_t* meta, const uint8_t* src,
+                                  uint8_t* scratch, uint32_t* err) {
+    if (!n_streams) return hipSuccess;
+    J2Code* code = (J2Code*)meta;
+    uint32_t* tt = (uint32_t*)(meta + sizeof(J2Code) * (uint64_t)n_blocks);
+    hipLaunchKernelGGL(k_tiff_j2k_packets, dim3(n_streams), dim3(64), 0, st, d_streams, n_streams, d_bands, src, tt,
+                       code, err);
+    if (n_blocks) {
+        const uint32_t lds = 4 * max_coef + ((max_flag + 15) & ~15u) + J2_CTX_BYTES + J2_TAB_BYTES;
+        hipLaunchKernelGGL(k_tiff_j2k_blocks, dim3(n_blocks), dim3(64), lds, st, d_blocks, n_blocks, code, d_streams, src,
+                           scratch, max_coef, max_flag);
+    }
+    if (n_comps) hipLaunchKernelGGL(k_tiff_j2k_idwt, dim3(n_comps), dim3(J2W_THREADS), 0, st, d_comps, n_comps, scratch);
+    return hipGetLastError();
+}
+
+hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t max_rows,
+                                 const TSplitDst* d_dst, const uint8_t* scratch) {
+    if (!n || !max_rows) return hipSuccess;
+    hipLaunchKernelGGL(k_tiff_j2k_place, dim3(n, (max_rows + J2P_ROWS - 1) / J2P_ROWS), dim3(64 * J2P_WAVES), 0, st,
+                       d_segs, d_dst, scratch);
+    return hipGetLastError();
+}
+
+}  // namespace pbx

@@ -293,4 +293,76 @@ static_assert(sizeof(TJpegSeg) == 56, "TJpegSeg is uploaded as is");
 hipError_t launch_tiff_jpeg_place(hipStream_t st, const TJpegSeg* d_segs, uint32_t n, uint32_t max_rows,
                                   const TSplitDst* d_dst, const uint8_t* scratch);
 
+// JPEG 2000 TIFF segments (kernels_tiff_j2k.hip; Compression 33003 / 33004 / 33005 / 34712: one
+// reversible 5/3 codestream of one tile per segment).  The host reads SIZ, COD and QCD and lays
+// out everything below from them (tiff_j2k_plan); packet headers and code-block bytes are read
+// on the device only.
+// A component's int32 coefficients live in a plane A of w x h dwords (pitch w) with every
+// resolution's low-pass band top left: resolution r covers [0, rh_r) x [0, rw_r), rw_r =
+// ceil(w / 2^(levels - r)), its HL band right of resolution r - 1, LH below, HH diagonal.  A
+// second plane B of the same size takes the inverse wavelet's horizontal pass.
+struct J2Band {            // one sub-band of one component of one stream
+    uint32_t blk0;         // its first code block in the launch's J2Block / J2Code tables
+    uint32_t nbx, nby;     // the code-block grid, raster order (0 x 0: an empty band)
+    uint32_t mb;           // magnitude bit-planes: guard bits + exponent - 1 (0 .. 31)
+    uint32_t tt;           // its inclusion tag tree in the launch's node table (dwords); the
+                           // zero-bit-plane tree follows it
+    uint32_t nodes;        // nodes of one tree
+    uint32_t tlevels;      // levels of one tree
+    uint32_t pad;
+};
+static_assert(sizeof(J2Band) == 32, "J2Band is uploaded as is");
+struct J2Stream {
+    uint64_t src_off;      // the packets (after SOD) in the upload buffer
+    uint32_t len;          // their bytes
+    uint32_t band0;        // component c's band b (QCD order) is J2Band band0 + c * (3 levels + 1) + b
+    uint32_t ncomp, levels;
+    uint32_t cmajor;       // packets by component then resolution (PCRL, CPRL), else by
+                           // resolution then component (LRCP, RLCP, RPCL)
+    uint32_t pad;
+};
+static_assert(sizeof(J2Stream) == 32, "J2Stream is uploaded as is");
+struct J2Block {
+    uint64_t dst;          // scratch offset of its first coefficient in the component's plane A
+    uint32_t pitch;        // of that plane, in dwords
+    uint16_t w, h;         // clipped to the band
+    uint32_t stream;
+    uint8_t orient, mb;    // 0 LL, 1 HL, 2 LH, 3 HH
+    uint16_t pad;
+};
+static_assert(sizeof(J2Block) == 24, "J2Block is uploaded as is");
+struct J2Code {            // written by k_tiff_j2k_packets (zero: the block is never included)
+    uint32_t off, len;     // its bytes, from J2Stream::src_off; checked against J2Stream::len
+    uint32_t passes, zbp;  // zbp <= mb and passes <= 3 (mb - zbp) - 2
+};
+struct J2Comp {            // one component of one stream, for the inverse wavelet
+    uint64_t a, b;         // its planes in scratch
+    uint32_t w, h, levels, pad;
+};
+static_assert(sizeof(J2Comp) == 32, "J2Comp is uploaded as is");
+struct TJ2Seg {            // one stream, for the placement
+    uint64_t src[3];       // its components' planes A
+    uint32_t w, rows;      // the segment's own size in pixels (the SIZ's)
+    int32_t x0, y0;        // its origin in the plane
+    uint32_t ncomp;        // 1 or 3
+    uint32_t rct;          // 1: inverse reversible colour transform
+    uint32_t prec;         // 8 or 16
+    uint32_t dst;          // its entry in the launch's TSplitDst table
+};
+static_assert(sizeof(TJ2Seg) == 56, "TJ2Seg is uploaded as is");
+// err[]: 0, or 1 a packet header or packet data runs past the stream's end, 2 a malformed packet
+// header (a length of more than 32 bits), 3 zero bit-planes above Mb or more passes than the
+// bit-planes allow.
+enum : uint32_t { J2E_END = 1, J2E_HEADER = 2, J2E_PLANES = 3 };
+// k_tiff_j2k_packets (one workgroup per stream), k_tiff_j2k_blocks (one wave per code block;
+// max_coef / max_flag: the most magnitudes / flag bytes a block of the launch needs in LDS),
+// k_tiff_j2k_idwt (one workgroup per component).  `meta` holds the J2Code table (n_blocks entries)
+// and after it the tag-tree nodes, all zero.
+hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams, const J2Band* d_bands,
+                                  const J2Block* d_blocks, uint32_t n_blocks, const J2Comp* d_comps, uint32_t n_comps,
+                                  uint32_t max_coef, uint32_t max_flag, uint8_t* meta, const uint8_t* src,
+                                  uint8_t* scratch, uint32_t* err);
+hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t max_rows,
+                                 const TSplitDst* d_dst, const uint8_t* scratch);
+
 }  // namespace pbx

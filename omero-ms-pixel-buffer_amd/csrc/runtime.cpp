@@ -29,6 +29,7 @@
 #include "pbx_common.h"
 #include "pbx_config.h"
 #include "pbx_kernels.h"
+#include "tiff_j2k_dev.h"
 
 using namespace pbx;
 
@@ -2355,6 +2356,16 @@ struct ZarrPlan {
     std::vector<TJpegSeg> jsegs;
     std::vector<JTabSet> jtabs;
     uint32_t jseg_rows = 0;
+    // JPEG 2000 TIFF segments (tiff_j2k_plan): one J2Stream and one TJ2Seg per segment, a J2Comp
+    // per component of it, a J2Band per sub-band of those and a J2Block per code block; the
+    // tag-tree nodes of the launch, the largest block's LDS needs, and the tallest segment
+    std::vector<J2Stream> j2streams;
+    std::vector<J2Band> j2bands;
+    std::vector<J2Block> j2blocks;
+    std::vector<J2Comp> j2comps;
+    std::vector<TJ2Seg> j2segs;
+    uint64_t j2nodes = 0;
+    uint32_t j2coef = 0, j2flag = 0, j2seg_rows = 0;
 };
 
 // A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
@@ -2625,10 +2636,12 @@ struct ZarrInput {
 // into the planes P.fdst_plane names.  P.jstreams (JPEG-compressed TIFF segments) are decoded by
 // k_tiff_jpeg_decode after the other decoders, their err[] entries after the checks', and
 // P.jsegs upsampled, converted and placed into the planes of `sd` by k_tiff_jpeg_place.
+// P.j2streams (JPEG 2000 TIFF segments) go through k_tiff_j2k_packets, _blocks and _idwt after
+// those, their err[] entries last, and P.j2segs are placed by k_tiff_j2k_place.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms,
                       const std::vector<TSplitDst>* sd = nullptr) {
-    if ((!P.split.empty() || !P.jsegs.empty()) && (!sd || sd->empty()))
+    if ((!P.split.empty() || !P.jsegs.empty() || !P.j2segs.empty()) && (!sd || sd->empty()))
         return fail(PBX_E_INTERNAL, "zarr decode: split segments without destinations");
     uint32_t counts[ZS_NKINDS], nstreams = 0;
     std::vector<ZStream> all;
@@ -2649,7 +2662,9 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         ck_n[k] = (uint32_t)checks.size() - ck_first[k];
     }
     const uint32_t nchecks = (uint32_t)checks.size(), njpeg = (uint32_t)P.jstreams.size();
-    const uint32_t nerr = nstreams + nchecks + njpeg;  // err[]: streams, checks, JPEG streams
+    const uint32_t nj2 = (uint32_t)P.j2streams.size();
+    const uint32_t nerr = nstreams + nchecks + njpeg + nj2;  // err[]: streams, checks, JPEG, JPEG 2000 streams
+    const uint64_t j2meta = sizeof(J2Code) * P.j2blocks.size() + 4 * P.j2nodes;
     uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
     ZStream* d_st = nullptr;
     ZCheck* d_ck = nullptr;
@@ -2664,13 +2679,19 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     JStream* d_js = nullptr;
     JTabSet* d_jt = nullptr;
     TJpegSeg* d_jp = nullptr;
+    J2Stream* d_2s = nullptr;
+    J2Band* d_2b = nullptr;
+    J2Block* d_2k = nullptr;
+    J2Comp* d_2c = nullptr;
+    TJ2Seg* d_2p = nullptr;
+    uint8_t* d_2m = nullptr;
     uint32_t* d_err = nullptr;
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     auto cleanup = [&] {
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_js, (void*)d_jt, (void*)d_jp, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_js, (void*)d_jt, (void*)d_jp, (void*)d_2s, (void*)d_2b, (void*)d_2k, (void*)d_2c, (void*)d_2p, (void*)d_2m, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2689,7 +2710,15 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (!P.unpred.empty()) dget(d_up, sizeof(TUnpred) * P.unpred.size());
     if (!P.uplace.empty()) dget(d_tp, sizeof(TPlace) * P.uplace.size());
     if (!P.split.empty()) dget(d_sp, sizeof(TPlace) * P.split.size());
-    if (!P.split.empty() || njpeg) dget(d_sd, sizeof(TSplitDst) * sd->size());
+    if (!P.split.empty() || njpeg || nj2) dget(d_sd, sizeof(TSplitDst) * sd->size());
+    if (nj2) {
+        dget(d_2s, sizeof(J2Stream) * nj2);
+        dget(d_2b, sizeof(J2Band) * P.j2bands.size());
+        dget(d_2k, sizeof(J2Block) * P.j2blocks.size());
+        dget(d_2c, sizeof(J2Comp) * P.j2comps.size());
+        dget(d_2p, sizeof(TJ2Seg) * P.j2segs.size());
+        dget(d_2m, j2meta);
+    }
     if (njpeg) {
         dget(d_js, sizeof(JStream) * njpeg);
         dget(d_jt, sizeof(JTabSet) * P.jtabs.size());
@@ -2746,6 +2775,17 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = hipMemcpyAsync(d_jt, P.jtabs.data(), sizeof(JTabSet) * P.jtabs.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_jp)
         e = hipMemcpyAsync(d_jp, P.jsegs.data(), sizeof(TJpegSeg) * P.jsegs.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_2s)
+        e = hipMemcpyAsync(d_2s, P.j2streams.data(), sizeof(J2Stream) * nj2, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_2b)
+        e = hipMemcpyAsync(d_2b, P.j2bands.data(), sizeof(J2Band) * P.j2bands.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_2k && !P.j2blocks.empty())
+        e = hipMemcpyAsync(d_2k, P.j2blocks.data(), sizeof(J2Block) * P.j2blocks.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_2c)
+        e = hipMemcpyAsync(d_2c, P.j2comps.data(), sizeof(J2Comp) * P.j2comps.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_2p)
+        e = hipMemcpyAsync(d_2p, P.j2segs.data(), sizeof(TJ2Seg) * P.j2segs.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_2m) e = hipMemsetAsync(d_2m, 0, std::max<uint64_t>(j2meta, 256), st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
     // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
@@ -2761,6 +2801,10 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess && d_up) e = launch_tiff_unpred(st, d_up, (uint32_t)P.unpred.size(), P.unpred_rows, d_scr);
     if (e == hipSuccess && d_js)
         e = launch_tiff_jpeg_decode(st, d_js, njpeg, d_jt, d_in, d_scr, d_err + nstreams + nchecks);
+    if (e == hipSuccess && d_2s)
+        e = launch_tiff_j2k_decode(st, d_2s, nj2, d_2b, d_2k, (uint32_t)P.j2blocks.size(), d_2c,
+                                   (uint32_t)P.j2comps.size(), P.j2coef, P.j2flag, d_2m, d_in, d_scr,
+                                   d_err + nstreams + nchecks + njpeg);
     if (e == hipSuccess) e = hipEventRecord(ev[1], st);
     if (e == hipSuccess && !P.chunks.empty())
         e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
@@ -2777,6 +2821,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = launch_tiff_fpunpred_place(st, d_fp, (uint32_t)P.fplace.size(), P.fplace_rows, d_fd, d_scr, d_in);
     if (e == hipSuccess && d_jp)
         e = launch_tiff_jpeg_place(st, d_jp, (uint32_t)P.jsegs.size(), P.jseg_rows, d_sd, d_scr);
+    if (e == hipSuccess && d_2p)
+        e = launch_tiff_j2k_place(st, d_2p, (uint32_t)P.j2segs.size(), P.j2seg_rows, d_sd, d_scr);
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     std::vector<uint32_t> err(nerr + 1, 0);
@@ -2809,6 +2855,11 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
             cleanup();
             return fail(PBX_E_BADARG, "corrupt segment stream %u (jpeg, decoder code %u: %s)", s, code,
                         code < 6 ? why[code] : "?");
+        }
+    for (uint32_t s = 0; s < nj2; s++)
+        if (const uint32_t code = err[nstreams + nchecks + njpeg + s]) {
+            cleanup();
+            return fail(PBX_E_BADARG, "corrupt segment stream %u (j2k, decoder code %u)", s, code);
         }
     if (kernel_ms) {
         float a = 0, b = 0;
@@ -3308,6 +3359,259 @@ int tiff_jpeg_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, c
     return PBX_OK;
 }
 
+// ------------------------------------------------------- JPEG 2000 TIFF segments
+// Compression 33003 / 33004 / 33005 / 34712: every strip or tile is one raw JPEG 2000 codestream
+// (SOC SIZ COD QCD ... SOT SOD packets EOC) of one tile.  The host reads marker segments only --
+// never a packet header, never a code-block byte -- and every length is checked against the bytes
+// it lies in.  Accepted: the reversible path (5/3 wavelet, no quantisation), one layer, one
+// precinct per resolution, code-block style 0; everything else is refused by name.
+struct J2kHeader {
+    uint32_t w = 0, h = 0, ncomp = 0, prec = 0;
+    uint32_t prog = 0, mct = 0, levels = 0, xcb = 0, ycb = 0, guard = 0;
+    bool precincts = false;
+    uint8_t pp[33];     // PPx | PPy << 4 per resolution
+    uint8_t exps[97];   // per sub-band, QCD order
+    uint64_t data = 0, end = 0;  // the packets
+};
+
+int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* what) {
+    static const uint8_t jp2[12] = {0, 0, 0, 12, 'j', 'P', ' ', ' ', 13, 10, 0x87, 10};
+    if (len >= 12 && !memcmp(f, jp2, 12)) return fail(PBX_E_BADARG, "%s: jp2 box, not a codestream", what);
+    if (len < 2 || f[0] != 0xFF || f[1] != 0x4F) return fail(PBX_E_BADARG, "%s does not start with SOC (JPEG 2000 codestream)", what);
+    uint64_t q = 2, sot = 0;
+    bool siz = false, cod = false, qcd = false, tile = false;
+    uint32_t nexp = 0, qstyle = 0, psot = 0;
+    for (;;) {
+        if (q + 2 > len) return fail(PBX_E_BADARG, "%s: truncated header", what);
+        if (f[q] != 0xFF) return fail(PBX_E_BADARG, "%s: truncated header (no marker at byte %llu)", what, (unsigned long long)q);
+        const uint32_t code = f[q + 1];
+        if (code == 0x93) {  // SOD
+            if (!tile) return fail(PBX_E_BADARG, "%s: SOD before SOT", what);
+            H.data = q + 2;
+            break;
+        }
+        if (code == 0xD9 || code == 0x4F || code == 0x91 || code == 0x92 || (code >= 0x30 && code <= 0x3F))
+            return fail(PBX_E_BADARG, "%s: marker FF %02X in the header", what, code);
+        if (q + 4 > len) return fail(PBX_E_BADARG, "%s: truncated header", what);
+        const uint32_t L = (uint32_t)f[q + 2] << 8 | f[q + 3];
+        if (L < 2 || q + 2 + L > len) return fail(PBX_E_BADARG, "%s: truncated header (marker FF %02X of %u bytes)", what, code, L);
+        const uint8_t* p = f + q + 4;
+        const uint32_t plen = L - 2;
+        auto be32 = [&](uint32_t at) { return (uint32_t)p[at] << 24 | (uint32_t)p[at + 1] << 16 | (uint32_t)p[at + 2] << 8 | p[at + 3]; };
+        if (!siz && code != 0x51) return fail(PBX_E_BADARG, "%s: marker FF %02X before SIZ", what, code);
+        if (code == 0x51) {
+            if (siz) return fail(PBX_E_BADARG, "%s: two SIZ markers", what);
+            if (plen < 36) return fail(PBX_E_BADARG, "%s: truncated SIZ", what);
+            const uint32_t xs = be32(2), ys = be32(6), xo = be32(10), yo = be32(14), xt = be32(18), yt = be32(22),
+                           xto = be32(26), yto = be32(30), nc = (uint32_t)p[34] << 8 | p[35];
+            if (plen != 36 + 3ull * nc) return fail(PBX_E_BADARG, "%s: truncated SIZ", what);
+            if (xo || yo || xto || yto)
+                return fail(PBX_E_BADARG, "%s: non-zero image or tile offsets (%u, %u; %u, %u)", what, xo, yo, xto, yto);
+            if (!xs || !ys || !xt || !yt) return fail(PBX_E_BADARG, "%s: bad SIZ (%u x %u, tiles %u x %u)", what, xs, ys, xt, yt);
+            if (xt < xs || yt < ys) return fail(PBX_E_BADARG, "%s: more than one tile (%u x %u in tiles of %u x %u)", what, xs, ys, xt, yt);
+            if (nc != 1 && nc != 3) return fail(PBX_E_BADARG, "%s: %u components (1 or 3)", what, nc);
+            for (uint32_t c = 0; c < nc; c++) {
+                const uint32_t ssiz = p[36 + 3 * c], xr = p[37 + 3 * c], yr = p[38 + 3 * c];
+                if (xr != 1 || yr != 1) return fail(PBX_E_BADARG, "%s: subsampled components (component %u: %u x %u)", what, c, xr, yr);
+                if (ssiz & 0x80) return fail(PBX_E_BADARG, "%s: signed components", what);
+                if (c && ssiz + 1 != H.prec) return fail(PBX_E_BADARG, "%s: components of different precisions", what);
+                H.prec = ssiz + 1;
+            }
+            if (H.prec != 8 && H.prec != 16) return fail(PBX_E_BADARG, "%s: precision %u (8 or 16)", what, H.prec);
+            if (nc == 3 && H.prec != 8) return fail(PBX_E_BADARG, "%s: three components at precision 16", what);
+            H.w = xs; H.h = ys; H.ncomp = nc;
+            siz = true;
+        } else if (code == 0x52) {
+            if (tile) return fail(PBX_E_BADARG, "%s: COD in a tile-part header", what);
+            if (cod) return fail(PBX_E_BADARG, "%s: two COD markers", what);
+            if (plen < 10) return fail(PBX_E_BADARG, "%s: truncated COD", what);
+            const uint32_t scod = p[0], layers = (uint32_t)p[2] << 8 | p[3];
+            if (scod & 6) return fail(PBX_E_BADARG, "%s: SOP or EPH markers (Scod 0x%02x)", what, scod);
+            if (scod & ~7u) return fail(PBX_E_BADARG, "%s: bad Scod 0x%02x", what, scod);
+            H.prog = p[1];
+            if (H.prog > 4) return fail(PBX_E_BADARG, "%s: bad progression order %u", what, H.prog);
+            if (layers != 1) return fail(PBX_E_BADARG, "%s: %u quality layers (1)", what, layers);
+            H.mct = p[4];
+            if (H.mct > 1) return fail(PBX_E_BADARG, "%s: bad multiple-component transform %u", what, H.mct);
+            H.levels = p[5];
+            if (H.levels > 32) return fail(PBX_E_BADARG, "%s: %u decomposition levels (0 .. 32)", what, H.levels);
+            H.xcb = p[6] + 2u; H.ycb = p[7] + 2u;
+            if (p[6] > 8 || p[7] > 8 || H.xcb + H.ycb > 12)
+                return fail(PBX_E_BADARG, "%s: bad code-block size 2^%u x 2^%u", what, H.xcb, H.ycb);
+            if (p[8])
+                return fail(PBX_E_BADARG, "%s: code-block style 0x%02x (bypass, reset, termall, vertically causal, predictable "
+                            "termination and segmentation symbols are not supported)", what, p[8]);
+            if (p[9] == 0) return fail(PBX_E_BADARG, "%s: irreversible wavelet (9/7) is not supported", what);
+            if (p[9] != 1) return fail(PBX_E_BADARG, "%s: bad wavelet transformation %u", what, p[9]);
+            H.precincts = scod & 1;
+            if (plen != 10 + (H.precincts ? H.levels + 1 : 0)) return fail(PBX_E_BADARG, "%s: truncated COD", what);
+            for (uint32_t r = 0; r <= H.levels; r++) H.pp[r] = H.precincts ? p[10 + r] : 0xFF;
+            cod = true;
+        } else if (code == 0x5C) {
+            if (tile) return fail(PBX_E_BADARG, "%s: QCD in a tile-part header", what);
+            if (qcd) return fail(PBX_E_BADARG, "%s: two QCD markers", what);
+            if (plen < 1) return fail(PBX_E_BADARG, "%s: truncated QCD", what);
+            qstyle = p[0] & 31;
+            H.guard = p[0] >> 5;
+            if (qstyle == 1 || qstyle == 2)
+                return fail(PBX_E_BADARG, "%s: quantisation style %u (irreversible wavelet) is not supported", what, qstyle);
+            if (qstyle) return fail(PBX_E_BADARG, "%s: bad quantisation style %u", what, qstyle);
+            nexp = plen - 1;
+            if (nexp > 97) return fail(PBX_E_BADARG, "%s: QCD of %u sub-bands", what, nexp);
+            for (uint32_t k = 0; k < nexp; k++) H.exps[k] = p[1 + k] >> 3;
+            qcd = true;
+        } else if (code == 0x90) {
+            if (tile) return fail(PBX_E_BADARG, "%s: more than one tile-part", what);
+            if (plen != 8) return fail(PBX_E_BADARG, "%s: truncated SOT", what);
+            if (p[0] || p[1]) return fail(PBX_E_BADARG, "%s: more than one tile (tile index %u)", what, (uint32_t)p[0] << 8 | p[1]);
+            psot = be32(2);
+            if (p[6] != 0 || p[7] > 1) return fail(PBX_E_BADARG, "%s: more than one tile-part (%u of %u)", what, p[6], p[7]);
+            sot = q;
+            tile = true;
+        } else if (code == 0x53 || code == 0x5D || code == 0x5E || code == 0x5F || code == 0x60 || code == 0x61 || code == 0x63) {
+            static const char* nm[17] = {"", "", "", "COC", "", "", "", "", "", "", "", "", "", "QCC", "RGN", "POC", ""};
+            const char* name = code == 0x60 ? "PPM" : code == 0x61 ? "PPT" : code == 0x63 ? "CRG" : nm[code & 15];
+            return fail(PBX_E_BADARG, "%s: %s markers are not supported", what, name);
+        } else if (code == 0x64 || code == 0x55 || code == 0x57 || code == 0x58) {
+            // COM, TLM, PLM, PLT: skipped
+        } else {
+            return fail(PBX_E_BADARG, "%s: marker FF %02X in the header", what, code);
+        }
+        q += 2 + L;
+    }
+    if (!cod) return fail(PBX_E_BADARG, "%s: no COD marker", what);
+    if (!qcd) return fail(PBX_E_BADARG, "%s: no QCD marker", what);
+    if (nexp != 3 * H.levels + 1)
+        return fail(PBX_E_BADARG, "%s: QCD of %u sub-bands for %u decomposition levels", what, nexp, H.levels);
+    if (H.mct && H.ncomp != 3) return fail(PBX_E_BADARG, "%s: multiple-component transform on %u component(s)", what, H.ncomp);
+    for (uint32_t k = 0; k < nexp; k++)
+        if (H.guard + H.exps[k] > 32)
+            return fail(PBX_E_BADARG, "%s: %u magnitude bit-planes (at most 31)", what, H.guard + H.exps[k] - 1);
+    for (uint32_t r = 0; r <= H.levels; r++) {
+        const uint32_t ppx = H.pp[r] & 15, ppy = H.pp[r] >> 4, sh = H.levels - r;
+        if (r && (!ppx || !ppy)) return fail(PBX_E_BADARG, "%s: precinct exponent 0 at resolution %u", what, r);
+        const uint64_t rw = ((uint64_t)H.w + (1ull << sh) - 1) >> sh, rh = ((uint64_t)H.h + (1ull << sh) - 1) >> sh;
+        if (rw > (1ull << ppx) || rh > (1ull << ppy))
+            return fail(PBX_E_BADARG, "%s: more than one precinct in resolution %u", what, r);
+    }
+    H.end = len;
+    if (psot) {
+        // (a tile-part that says it is longer than its segment ends with the segment: what the
+        // packets then miss is the device's to find)
+        if (sot + psot < H.data) return fail(PBX_E_BADARG, "%s: tile-part length %u ends inside its header", what, psot);
+        H.end = std::min<uint64_t>(sot + psot, len);
+        if (H.end + 2 <= len && f[H.end] == 0xFF && f[H.end + 1] == 0x90)
+            return fail(PBX_E_BADARG, "%s: more than one tile-part", what);
+    } else if (len >= H.data + 2 && f[len - 2] == 0xFF && f[len - 1] == 0xD9) {
+        H.end = len - 2;
+    }
+    return PBX_OK;
+}
+
+// pbx_tiff_segments fields of a JPEG 2000 layer that can be checked without the plane.
+int tiff_j2k_check(const pbx_tiff_segments* s, int32_t pixel_type, int32_t spp) {
+    if (!s->data || !s->offsets) return fail(PBX_E_BADARG, "null argument");
+    if (s->seg_w < 1 || s->seg_h < 1) return fail(PBX_E_BADARG, "bad segment shape %d x %d", s->seg_w, s->seg_h);
+    if (s->tiled && ((s->seg_w | s->seg_h) & 15))
+        return fail(PBX_E_BADARG, "tile %d x %d: TileWidth and TileLength must be multiples of 16 (TIFF 6.0 section 15)",
+                    s->seg_w, s->seg_h);
+    if (s->compression != PBX_TIFF_J2K) return fail(PBX_E_BADARG, "bad compression %d (the JPEG 2000 calls take 34712)", s->compression);
+    if (s->predictor != 1) return fail(PBX_E_BADARG, "bad predictor %d on JPEG 2000 segments (1 only)", s->predictor);
+    if (s->flags) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
+    if (pixel_type != PBX_UINT8 && pixel_type != PBX_UINT16)
+        return fail(PBX_E_BADARG, "JPEG 2000 segments on a plane that is neither uint8 nor uint16");
+    if (spp != 1 && spp != 3) return fail(PBX_E_BADARG, "JPEG 2000 segments of %d samples per pixel (1 or 3)", spp);
+    return PBX_OK;
+}
+
+// Host plan of the JPEG 2000 segment rows [sr0, sr1) (sr1 < 0: all) of a uint8 / uint16 plane:
+// tiff_plan's geometry; per segment a J2Stream and a TJ2Seg, per component two int32 planes in
+// scratch (8 bytes a sample, each plane rounded up to 256 bytes) and a J2Comp, per sub-band
+// (T.800 B.5) a J2Band with its two tag trees, per code block (the band's grid anchored at 0,
+// the last column and row clipped) a J2Block that says where its coefficients go.  Everything
+// follows from SIZ, COD and QCD.
+int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segments* s, uint64_t in_base, ZarrPlan& P,
+                  int64_t sr0, int64_t sr1, int spp, uint32_t dst, uint64_t* packets = nullptr) {
+    if (!s->tiled && s->seg_w != size_x)
+        return fail(PBX_E_BADARG, "strip width %d != plane width %d", s->seg_w, size_x);
+    const int64_t gx = s->tiled ? ((int64_t)size_x + s->seg_w - 1) / s->seg_w : 1;
+    const int64_t gy = ((int64_t)size_y + s->seg_h - 1) / s->seg_h;
+    if (sr1 < 0) sr1 = gy;
+    const int64_t n = gx * (sr1 - sr0);
+    const uint64_t total = s->offsets[n];
+    for (int64_t i = 0; i < n; i++) {
+        const uint64_t o = s->offsets[i], len = s->offsets[i + 1] - o;
+        if (s->offsets[i + 1] < o || s->offsets[i + 1] > total)
+            return fail(PBX_E_BADARG, "segment %lld: bad offsets", (long long)i);
+        if (len == 0) return fail(PBX_E_BADARG, "segment %lld is empty", (long long)i);
+        if (len > 0x7fffffffull) return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
+        const int32_t x0 = (int32_t)((i % gx) * s->seg_w), y0 = (int32_t)((sr0 + i / gx) * s->seg_h);
+        const int32_t rows = s->tiled ? s->seg_h : std::min(s->seg_h, size_y - y0);
+        char what[48];
+        snprintf(what, sizeof what, "segment %lld", (long long)i);
+        J2kHeader H;
+        if (int rc = j2k_parse_header(s->data + o, len, H, what)) return rc;
+        if ((int64_t)H.w != s->seg_w || (int64_t)H.h != rows)
+            return fail(PBX_E_BADARG, "%s: SIZ size %u x %u != segment size %d x %d", what, H.w, H.h, s->seg_w, rows);
+        if ((int)H.ncomp != spp)
+            return fail(PBX_E_BADARG, "%s: a stream of %u components in segments of %d samples per pixel", what, H.ncomp, spp);
+        if ((int)H.prec != 8 * bpp)
+            return fail(PBX_E_BADARG, "%s: precision %u on a plane of %d-bit samples", what, H.prec, 8 * bpp);
+        const uint64_t plane = ((uint64_t)H.w * H.h * 4 + 255) & ~255ull;
+        if (plane > 0x7fffffffull) return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
+        const uint32_t NL = H.levels, stream = (uint32_t)P.j2streams.size();
+        auto res = [&](uint32_t v, uint32_t r) { return (uint32_t)(((uint64_t)v + (1ull << (NL - r)) - 1) >> (NL - r)); };
+        TJ2Seg seg{{0, 0, 0}, H.w, H.h, x0, y0, H.ncomp, H.mct, H.prec, dst};
+        const uint32_t band0 = (uint32_t)P.j2bands.size();
+        for (uint32_t c = 0; c < H.ncomp; c++) {
+            const uint64_t a = P.scratch;
+            P.scratch += 2 * plane;
+            seg.src[c] = a;
+            P.j2comps.push_back(J2Comp{a, a + plane, H.w, H.h, NL, 0});
+            for (uint32_t b = 0; b < 3 * NL + 1; b++) {
+                const uint32_t r = b ? (b + 2) / 3 : 0, orient = b ? (b - 1) % 3 + 1 : 0;
+                const uint32_t cw = res(H.w, r), ch = res(H.h, r);
+                const uint32_t lw = r ? res(H.w, r - 1) : 0, lh = r ? res(H.h, r - 1) : 0;
+                const uint32_t bx0 = orient & 1 ? lw : 0, by0 = orient & 2 ? lh : 0;
+                const uint32_t bw = !r ? cw : orient & 1 ? cw - lw : lw, bh = !r ? ch : orient & 2 ? ch - lh : lh;
+                const uint32_t ppx = H.pp[r] & 15, ppy = H.pp[r] >> 4;
+                const uint32_t xcb = std::min(H.xcb, ppx - (r ? 1 : 0)), ycb = std::min(H.ycb, ppy - (r ? 1 : 0));
+                const uint32_t nbx = bw && bh ? (bw + (1u << xcb) - 1) >> xcb : 0, nby = bw && bh ? (bh + (1u << ycb) - 1) >> ycb : 0;
+                const uint32_t gexp = H.guard + H.exps[b];
+                J2Band B{(uint32_t)P.j2blocks.size(), nbx, nby, gexp ? gexp - 1 : 0, (uint32_t)P.j2nodes, 0, 0, 0};
+                if (nbx) {
+                    uint32_t wl = nbx, hl = nby;
+                    for (;;) {
+                        B.nodes += wl * hl;
+                        B.tlevels++;
+                        if (wl == 1 && hl == 1) break;
+                        wl = (wl + 1) / 2;
+                        hl = (hl + 1) / 2;
+                    }
+                }
+                P.j2nodes += 2ull * B.nodes;
+                if (P.j2blocks.size() + (uint64_t)nbx * nby > 0x3ffffffull || P.j2nodes > 0x3fffffffull)
+                    return fail(PBX_E_BADARG, "segment %lld: too many code blocks", (long long)i);
+                P.j2bands.push_back(B);
+                for (uint32_t by = 0; by < nby; by++)
+                    for (uint32_t bx = 0; bx < nbx; bx++) {
+                        const uint32_t ox = bx << xcb, oy = by << ycb;
+                        const uint32_t w = std::min(1u << xcb, bw - ox), h = std::min(1u << ycb, bh - oy);
+                        P.j2blocks.push_back(J2Block{a + 4 * ((uint64_t)(by0 + oy) * H.w + bx0 + ox), H.w, (uint16_t)w, (uint16_t)h,
+                                                     stream, (uint8_t)orient, (uint8_t)B.mb, 0});
+                        P.j2coef = std::max(P.j2coef, w * h);
+                        P.j2flag = std::max(P.j2flag, (w + 2) * (h + 2));
+                    }
+            }
+        }
+        P.j2streams.push_back(J2Stream{o + in_base + H.data, (uint32_t)(H.end - H.data), band0, H.ncomp, NL, H.prog >= 3 ? 1u : 0u, 0});
+        P.j2segs.push_back(seg);
+        P.j2seg_rows = std::max(P.j2seg_rows, H.h);
+        if (packets) *packets += (uint64_t)H.ncomp * (NL + 1);
+    }
+    return PBX_OK;
+}
+
 // pbx_band_write_tiff: pbx_band_write_zarr for segment rows.  The piece's covering segment rows
 // are planned on the host first (a malformed piece never joins the band's load), then uploaded,
 // decoded and placed under the band state machine of band_load_rows.
@@ -3316,10 +3620,13 @@ int tiff_jpeg_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, c
 // With `j` (pbx_band_write_tiff_jpeg) the segments are JPEG streams: tiff_jpeg_plan, and the one
 // TSplitDst entry for one-sample segments too.
 int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
-                    int32_t spp, int32_t sample, double* kernel_ms, const pbx_tiff_jpeg* j = nullptr) {
+                    int32_t spp, int32_t sample, double* kernel_ms, const pbx_tiff_jpeg* j = nullptr,
+                    bool j2k = false) {  // j2k (pbx_band_write_tiff_j2k): JPEG 2000 codestreams, tiff_j2k_plan
     int32_t k = 0;
     if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
-    if (j) {
+    if (j2k) {
+        if (int rc = tiff_j2k_check(s, q->pixel_type, spp)) return rc;
+    } else if (j) {
         if (int rc = tiff_jpeg_check(s, j, q->pixel_type, spp)) return rc;
     } else if (int rc = tiff_segments_check(s)) {
         return rc;
@@ -3332,7 +3639,9 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     const int64_t gx = s->tiled ? ((int64_t)q->size_x + s->seg_w - 1) / s->seg_w : 1;
     const int64_t sr0 = y0 / s->seg_h, sr1 = ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h;
     ZarrPlan P;
-    if (j) {
+    if (j2k) {
+        if (int rc = tiff_j2k_plan(q->size_x, q->size_y, bpp, s, 0, P, sr0, sr1, spp, 0)) return rc;
+    } else if (j) {
         if (int rc = tiff_jpeg_plan(q->size_x, q->size_y, s, j, 0, P, sr0, sr1, spp, 0)) return rc;
     } else if (int rc = tiff_plan(q->size_x, q->size_y, bpp, !q->little_endian, s, 0, 0, P, nullptr, true, sr0, sr1, spp, 0))
         return rc;
@@ -3343,7 +3652,7 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
         const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
                                             q->size_y, s->seg_w, s->seg_h, (uint32_t)bpp, 0, 0, y0, y0 + rows}};
         std::vector<TSplitDst> sd;
-        if (spp > 1 || j) {
+        if (spp > 1 || j || j2k) {
             sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, q->pitch, q->size_x, q->size_y, y0, y0 + rows,
                                    (uint32_t)bpp, q->little_endian ? 0u : 1u, (uint32_t)spp, (uint32_t)s->predictor});
             sd[0].dev[sample] = zp[0].dev;
@@ -3364,14 +3673,17 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
 int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
                          uint64_t n_layers, const pbx_zarr_chunks* zs, const int32_t* depths,
                          uint64_t* plane_ids, double* kernel_ms, const pbx_tiff_segments* ts = nullptr,
-                         const pbx_tiff_jpeg* tj = nullptr) {  // tj: the TIFF layers are JPEG streams
+                         const pbx_tiff_jpeg* tj = nullptr,  // tj: the TIFF layers are JPEG streams
+                         bool j2k = false) {                 // j2k: they are JPEG 2000 codestreams
     std::vector<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t>> keys;
     std::vector<std::vector<ZarrWant>> want(n_layers);
     for (uint64_t k = 0; k < n; k++) {
         const pbx_plane_desc* d = &ds[k];
         if (refs[k].layer >= n_layers) return fail(PBX_E_BADARG, "plane %llu: no layer %u", (unsigned long long)k, refs[k].layer);
         if (ts) {
-            if (tj) {
+            if (j2k) {
+                if (int rc = tiff_j2k_check(&ts[refs[k].layer], d->pixel_type, depths[refs[k].layer])) return rc;
+            } else if (tj) {
                 if (int rc = tiff_jpeg_check(&ts[refs[k].layer], &tj[refs[k].layer], d->pixel_type, depths[refs[k].layer]))
                     return rc;
             } else if (int rc = tiff_segments_check(&ts[refs[k].layer])) {
@@ -3440,13 +3752,16 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
             const pbx_tiff_segments* s = &ts[l];
             const int bpp = bpp_of(d->pixel_type);
             const bool big = d->byte_order != PBX_LITTLE_ENDIAN;
-            if (tj) {
+            if (j2k) {
+                if (int rc = tiff_j2k_plan(d->size_x, d->size_y, bpp, s, in_base[l], P, 0, -1, depths[l], (uint32_t)sd.size()))
+                    return rc;
+            } else if (tj) {
                 if (int rc = tiff_jpeg_plan(d->size_x, d->size_y, s, &tj[l], in_base[l], P, 0, -1, depths[l], (uint32_t)sd.size()))
                     return rc;
             } else if (int rc = tiff_plan(d->size_x, d->size_y, bpp, big, s, in_base[l], want[l][0].plane, P, nullptr, false,
                                           0, -1, depths[l], (uint32_t)sd.size()))
                 return rc;
-            if (depths[l] > 1 || tj) {
+            if (depths[l] > 1 || tj || j2k) {
                 sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255,
                                        d->size_x, d->size_y, 0, d->size_y, (uint32_t)bpp, big && bpp > 1 ? 1u : 0u,
                                        (uint32_t)depths[l], (uint32_t)s->predictor});
@@ -3610,6 +3925,135 @@ int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows
     unpin_one(ctx, q);
     g_err = msg;
     return rc;
+}
+
+int pbx_planes_register_tiff_j2k(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
+                                 uint64_t n_layers, const pbx_tiff_segments* layers, const int32_t* samples_per_pixel,
+                                 uint64_t* plane_ids, double* kernel_ms) {
+    if (!ctx || !ds || !refs || !layers || !samples_per_pixel || !plane_ids || n == 0 || n_layers == 0)
+        return fail(PBX_E_BADARG, "null argument");
+    if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms, layers, nullptr,
+                                true);
+}
+
+int pbx_band_write_tiff_j2k(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
+                            int32_t samples_per_pixel, int32_t sample, double* kernel_ms) {
+    if (!ctx || !s) return fail(PBX_E_BADARG, "null argument");
+    int rc;
+    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
+    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
+    rc = band_write_tiff(ctx, q, y0, rows, s, samples_per_pixel, sample, kernel_ms, nullptr, true);
+    const std::string msg = g_err;
+    unpin_one(ctx, q);
+    g_err = msg;
+    return rc;
+}
+
+int pbx_test_tiff_j2k_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t pixel_type,
+                           int32_t samples_per_pixel, int32_t y0, int32_t rows, uint64_t out[4]) {
+    if (!s || !out) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = tiff_j2k_check(s, pixel_type, samples_per_pixel)) return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    if (rows < 0 || y0 < 0 || (int64_t)y0 + rows > size_y)
+        return fail(PBX_E_BADARG, "rows %d+%d outside the plane (%d rows)", y0, rows, size_y);
+    ZarrPlan P;
+    uint64_t packets = 0;
+    const bool band = rows > 0;
+    if (int rc = tiff_j2k_plan(size_x, size_y, bpp_of(pixel_type), s, 0, P, band ? y0 / s->seg_h : 0,
+                               band ? ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h : -1, samples_per_pixel, 0, &packets))
+        return rc;
+    out[0] = P.j2streams.size();
+    out[1] = P.j2blocks.size();
+    out[2] = packets;
+    out[3] = P.scratch;
+    return PBX_OK;
+}
+
+// Test hook: the whole decode on the CPU, no context and no device call: the planner's tables,
+// then the device's own serial code (tiff_j2k_dev.h: j2k_packets per stream, j2k_block per code
+// block, each block's state in heap blocks of exactly the sizes k_tiff_j2k_blocks has in LDS),
+// the inverse 5/3 lifting, the inverse RCT, level shift and clamp.  out: samples_per_pixel planes
+// of size_x * size_y samples, uint8 or host-order uint16, no pitch.
+int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t pixel_type,
+                             int32_t samples_per_pixel, void* out, uint64_t out_bytes) {
+    if (!s || !out) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = tiff_j2k_check(s, pixel_type, samples_per_pixel)) return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    const int bpp = bpp_of(pixel_type);
+    if (out_bytes != (uint64_t)size_x * size_y * bpp * samples_per_pixel) return fail(PBX_E_BADARG, "bad output size");
+    ZarrPlan P;
+    if (int rc = tiff_j2k_plan(size_x, size_y, bpp, s, 0, P, 0, -1, samples_per_pixel, 0)) return rc;
+    static const uint32_t mq[J2_MQ_STATES] = {PBX_MQ_TABLE};
+    std::vector<J2Code> code(P.j2blocks.size(), J2Code{0, 0, 0, 0});
+    std::vector<uint32_t> tt(P.j2nodes, 0);
+    for (size_t i = 0; i < P.j2streams.size(); i++)
+        if (const uint32_t e = j2k_packets(P.j2streams[i], P.j2bands.data(), s->data, tt.data(), code.data()))
+            return fail(PBX_E_BADARG, "corrupt segment stream %u (j2k, decoder code %u)", (unsigned)i, e);
+    std::vector<int32_t> scr(P.scratch / 4, 0);
+    for (size_t i = 0; i < P.j2blocks.size(); i++) {
+        const J2Block& B = P.j2blocks[i];
+        const J2Code& C = code[i];
+        const J2Stream& S = P.j2streams[B.stream];
+        const uint32_t w = B.w, h = B.h, planes = B.mb - C.zbp;
+        if (w * h > P.j2coef || (w + 2) * (h + 2) > P.j2flag) return fail(PBX_E_INTERNAL, "j2k plan: block %zu outgrows the launch", i);
+        std::vector<int32_t> mag(w * h, 0);
+        std::vector<uint8_t> flg((w + 2) * (h + 2), 0), ctx(19, 0);
+        ctx[0] = 4 << 1; ctx[17] = 3 << 1; ctx[18] = 46 << 1;
+        if (C.passes && C.zbp < B.mb && planes <= 31 && C.passes <= 3 * planes - 2 && C.off <= S.len && C.len <= S.len - C.off) {
+            // the block's bytes in a heap block of their own: a read past them is caught
+            const std::vector<uint8_t> bytes(s->data + S.src_off + C.off, s->data + S.src_off + C.off + C.len);
+            j2k_block(mag.data(), flg.data(), ctx.data(), mq, bytes.data(), C.len, w, h, B.orient, planes, C.passes);
+        }
+        for (uint32_t y = 0; y < h; y++)
+            for (uint32_t x = 0; x < w; x++)
+                scr[B.dst / 4 + (uint64_t)y * B.pitch + x] = (flg[(y + 1) * (w + 2) + x + 1] & J2F_NEG) ? -mag[y * w + x] : mag[y * w + x];
+    }
+    // T.800 F.3: one dimension in place, low-pass samples at the even places
+    auto sr = [](std::vector<int64_t>& x) {
+        const int64_t n = (int64_t)x.size();
+        if (n < 2) return;
+        auto at = [&](int64_t i) { return x[i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i]; };
+        for (int64_t i = 0; i < n; i += 2) x[i] -= (at(i - 1) + at(i + 1) + 2) >> 2;
+        for (int64_t i = 1; i < n; i += 2) x[i] += (at(i - 1) + at(i + 1)) >> 1;
+    };
+    for (const J2Comp& c : P.j2comps) {
+        int32_t* A = scr.data() + c.a / 4;
+        for (uint32_t r = 1; r <= c.levels; r++) {
+            const uint32_t sh = c.levels - r;
+            const uint32_t cw = (uint32_t)((c.w + (1ull << sh) - 1) >> sh), ch = (uint32_t)((c.h + (1ull << sh) - 1) >> sh);
+            const uint32_t lw = (cw + 1) / 2, lh = (ch + 1) / 2;
+            std::vector<int64_t> line;
+            for (uint32_t y = 0; y < ch; y++) {
+                line.assign(cw, 0);
+                for (uint32_t x = 0; x < cw; x++) line[x < lw ? 2 * x : 2 * (x - lw) + 1] = A[(uint64_t)y * c.w + x];
+                sr(line);
+                for (uint32_t x = 0; x < cw; x++) A[(uint64_t)y * c.w + x] = (int32_t)line[x];
+            }
+            for (uint32_t x = 0; x < cw; x++) {
+                line.assign(ch, 0);
+                for (uint32_t y = 0; y < ch; y++) line[y < lh ? 2 * y : 2 * (y - lh) + 1] = A[(uint64_t)y * c.w + x];
+                sr(line);
+                for (uint32_t y = 0; y < ch; y++) A[(uint64_t)y * c.w + x] = (int32_t)line[y];
+            }
+        }
+    }
+    for (const TJ2Seg& u : P.j2segs)
+        for (uint32_t y = 0; y < u.rows && (int64_t)u.y0 + y < size_y; y++)
+            for (uint32_t x = 0; x < u.w && (int64_t)u.x0 + x < size_x; x++) {
+                int64_t v[3] = {0, 0, 0};
+                for (uint32_t c = 0; c < u.ncomp; c++) v[c] = scr[u.src[c] / 4 + (uint64_t)y * u.w + x];
+                if (u.ncomp == 3 && u.rct) {
+                    const int64_t g = v[0] - ((v[1] + v[2]) >> 2), rr = v[2] + g, bb = v[1] + g;
+                    v[0] = rr; v[1] = g; v[2] = bb;
+                }
+                for (uint32_t c = 0; c < u.ncomp; c++) {
+                    const int64_t hi = (1ll << u.prec) - 1, t = std::min(hi, std::max<int64_t>(0, v[c] + (1ll << (u.prec - 1))));
+                    const uint64_t at = (uint64_t)c * size_x * size_y + (uint64_t)(u.y0 + y) * size_x + u.x0 + x;
+                    if (bpp == 1) ((uint8_t*)out)[at] = (uint8_t)t; else ((uint16_t*)out)[at] = (uint16_t)t;
+                }
+            }
+    return PBX_OK;
 }
 
 int pbx_test_tiff_jpeg_plan(const pbx_tiff_segments* s, const pbx_tiff_jpeg* jpeg, int32_t size_x, int32_t size_y,

@@ -181,7 +181,8 @@ EXPORTS = [
     "pbx_test_zarr_plan", "pbx_planes_register_tiff", "pbx_test_tiff_plan",
     "pbx_band_write_tiff", "pbx_test_tiff_band_plan", "pbx_planes_register_tiff_samples",
     "pbx_band_write_tiff_sample", "pbx_test_tiff_plan_samples", "pbx_planes_register_tiff_jpeg",
-    "pbx_band_write_tiff_jpeg", "pbx_test_tiff_jpeg_plan",
+    "pbx_band_write_tiff_jpeg", "pbx_test_tiff_jpeg_plan", "pbx_planes_register_tiff_j2k",
+    "pbx_band_write_tiff_j2k", "pbx_test_tiff_j2k_plan", "pbx_test_tiff_j2k_decode",
 ]
 
 _lib = None
@@ -298,6 +299,15 @@ def lib() -> ctypes.CDLL:
                                            ctypes.POINTER(PbxTiffJpeg), ctypes.POINTER(ctypes.c_double)]
     L.pbx_test_tiff_jpeg_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(PbxTiffJpeg), i32, i32,
                                           i32, i32, i32, ctypes.POINTER(u64)]
+    L.pbx_planes_register_tiff_j2k.argtypes = [vp, u64, ctypes.POINTER(PbxPlaneDesc),
+                                               ctypes.POINTER(PbxZarrSlice), u64,
+                                               ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(i32),
+                                               ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double)]
+    L.pbx_band_write_tiff_j2k.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxTiffSegments), i32, i32,
+                                          ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_tiff_j2k_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, i32, i32,
+                                         ctypes.POINTER(u64)]
+    L.pbx_test_tiff_j2k_decode.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, vp, u64]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -788,6 +798,8 @@ def pack_chunks(chunks: Sequence[Optional[bytes]]):
 TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
 TIFF_ZSTD = 50000
 TIFF_JPEG = 7  # through the pbx_*_tiff_jpeg calls only
+TIFF_J2K = 34712  # through the pbx_*_tiff_j2k calls only; what every Compression value below hands over as
+_TIFF_J2K_COMPRESSIONS = (33003, 33004, 33005, 34712)  # Bio-Formats' TiffCompression: JPEG-2000 / Lossy, Aperio's two
 _TIFF_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4,
                    16: 8, 17: 8, 18: 8}
 _TIFF_INT_FMT = {1: "B", 3: "H", 4: "I", 13: "I", 16: "Q", 18: "Q", 6: "b", 8: "h", 9: "i", 17: "q"}
@@ -1049,11 +1061,170 @@ def _tiff_jpeg_first_segment(path: str, ifd: dict, spp: int) -> None:
                        % (h["scan_components"], len(comps)))
 
 
+_J2K_UNSUPPORTED_MARKERS = {0x53: "COC", 0x5D: "QCC", 0x5E: "RGN", 0x5F: "POC", 0x60: "PPM", 0x61: "PPT", 0x63: "CRG"}
+
+
+def j2k_header(data: bytes, what: str) -> dict:
+    """The marker segments of a raw JPEG 2000 codestream up to SOD (no packet byte is read): width,
+    height, offsets (XOsiz, YOsiz, XTOsiz, YTOsiz), tile (XTsiz, YTsiz), components = [(precision,
+    signed, XRsiz, YRsiz)], scod, progression, layers, mct, levels, xcb, ycb (the code block's
+    exponents), style, transformation (1: the reversible 5/3), precincts = [(PPx, PPy)] per
+    resolution (15, 15 if none are declared), qstyle, guard, exponents (per sub-band), markers
+    (the codes met, in order), tile_index, tile_part, tile_parts, psot, sot and data (the offset
+    after SOD).  PbxError 400 with `what` for a JP2 file, a stream that does not start with SOC,
+    or a header cut short."""
+    import struct
+    n = len(data)
+    if data[:12] == b"\x00\x00\x00\x0cjP  \r\n\x87\n":
+        raise PbxError(400, "%s: jp2 box, not a codestream" % what)
+    if n < 2 or data[0] != 0xFF or data[1] != 0x4F:
+        raise PbxError(400, "%s does not start with SOC (JPEG 2000 codestream)" % what)
+    out = dict(markers=[], components=[], exponents=[], precincts=None, data=None, sot=None)
+    q = 2
+    while True:
+        if q + 2 > n:
+            raise PbxError(400, "%s: truncated header" % what)
+        if data[q] != 0xFF:
+            raise PbxError(400, "%s: truncated header (no marker at byte %d)" % (what, q))
+        code = data[q + 1]
+        if code == 0x93:
+            out["data"] = q + 2
+            return out
+        if code in (0xD9, 0x4F, 0x91, 0x92) or 0x30 <= code <= 0x3F:
+            raise PbxError(400, "%s: marker FF %02X in the header" % (what, code))
+        if q + 4 > n:
+            raise PbxError(400, "%s: truncated header" % what)
+        L = data[q + 2] << 8 | data[q + 3]
+        if L < 2 or q + 2 + L > n:
+            raise PbxError(400, "%s: truncated header (marker FF %02X of %d bytes)" % (what, code, L))
+        p = data[q + 4:q + 2 + L]
+        out["markers"].append(code)
+        if code == 0x51:
+            if len(p) < 36 or len(p) != 36 + 3 * (p[34] << 8 | p[35]):
+                raise PbxError(400, "%s: truncated SIZ" % what)
+            xs, ys, xo, yo, xt, yt, xto, yto = struct.unpack(">8I", p[2:34])
+            out.update(width=xs, height=ys, offsets=(xo, yo, xto, yto), tile=(xt, yt),
+                       components=[((p[36 + 3 * c] & 127) + 1, p[36 + 3 * c] >> 7, p[37 + 3 * c], p[38 + 3 * c])
+                                   for c in range(p[34] << 8 | p[35])])
+        elif code == 0x52:
+            if len(p) < 10 or len(p) != 10 + ((p[5] + 1) if p[0] & 1 else 0):
+                raise PbxError(400, "%s: truncated COD" % what)
+            out.update(scod=p[0], progression=p[1], layers=p[2] << 8 | p[3], mct=p[4], levels=p[5], xcb=p[6] + 2,
+                       ycb=p[7] + 2, style=p[8], transformation=p[9],
+                       precincts=[(b & 15, b >> 4) for b in p[10:]] if p[0] & 1 else [(15, 15)] * (p[5] + 1))
+        elif code == 0x5C:
+            if len(p) < 1:
+                raise PbxError(400, "%s: truncated QCD" % what)
+            out.update(qstyle=p[0] & 31, guard=p[0] >> 5, qcd=bytes(p[1:]), exponents=[b >> 3 for b in p[1:]])
+        elif code == 0x90:
+            if len(p) != 8:
+                raise PbxError(400, "%s: truncated SOT" % what)
+            if out["sot"] is not None:
+                raise PbxError(400, "%s: more than one tile-part" % what)
+            out.update(sot=q, tile_index=p[0] << 8 | p[1], psot=struct.unpack(">I", p[2:6])[0], tile_part=p[6],
+                       tile_parts=p[7])
+        q += 2 + L
+
+
+def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int) -> None:
+    """What the first segment's header shows of a JPEG 2000 IFD this library cannot load: PbxError
+    400 with the reason, in the C-ABI's words (which checks every segment again)."""
+    if not ifd["offsets"]:
+        return
+    with open(path, "rb") as f:
+        f.seek(ifd["offsets"][0])
+        data = f.read(ifd["counts"][0])
+    what = "%s: Compression %d: segment 0" % (path, ifd["compression"])
+    h = j2k_header(data, what)
+
+    def no(why):
+        raise PbxError(400, "%s: %s" % (what, why))
+    if not h["markers"] or h["markers"][0] != 0x51:
+        no("marker FF %02X before SIZ" % h["markers"][0] if h["markers"] else "truncated header")
+    for code in h["markers"]:
+        if code in _J2K_UNSUPPORTED_MARKERS:
+            no("%s markers are not supported" % _J2K_UNSUPPORTED_MARKERS[code])
+        if code not in (0x51, 0x52, 0x5C, 0x90, 0x64, 0x55, 0x57, 0x58):
+            no("marker FF %02X in the header" % code)
+    if any(h["offsets"]):
+        no("non-zero image or tile offsets (%d, %d; %d, %d)" % h["offsets"])
+    if h["tile"][0] < h["width"] or h["tile"][1] < h["height"]:
+        no("more than one tile (%d x %d in tiles of %d x %d)" % (h["width"], h["height"], h["tile"][0], h["tile"][1]))
+    comps = h["components"]
+    if len(comps) not in (1, 3):
+        no("%d components (1 or 3)" % len(comps))
+    for c, (prec, signed, xr, yr) in enumerate(comps):
+        if (xr, yr) != (1, 1):
+            no("subsampled components (component %d: %d x %d)" % (c, xr, yr))
+        if signed:
+            no("signed components")
+        if prec != comps[0][0]:
+            no("components of different precisions")
+    prec = comps[0][0]
+    if prec not in (8, 16):
+        no("precision %d (8 or 16)" % prec)
+    if len(comps) == 3 and prec != 8:
+        no("three components at precision 16")
+    if "levels" not in h:
+        no("no COD marker")
+    if h["scod"] & 6:
+        no("SOP or EPH markers (Scod 0x%02x)" % h["scod"])
+    if h["progression"] > 4:
+        no("bad progression order %d" % h["progression"])
+    if h["layers"] != 1:
+        no("%d quality layers (1)" % h["layers"])
+    if h["levels"] > 32:
+        no("%d decomposition levels (0 .. 32)" % h["levels"])
+    if not (2 <= h["xcb"] <= 10 and 2 <= h["ycb"] <= 10 and h["xcb"] + h["ycb"] <= 12):
+        no("bad code-block size 2^%d x 2^%d" % (h["xcb"], h["ycb"]))
+    if h["style"]:
+        no("code-block style 0x%02x (bypass, reset, termall, vertically causal, predictable termination and "
+           "segmentation symbols are not supported)" % h["style"])
+    if h["transformation"] == 0:
+        no("irreversible wavelet (9/7) is not supported")
+    if h["transformation"] != 1:
+        no("bad wavelet transformation %d" % h["transformation"])
+    if "qstyle" not in h:
+        no("no QCD marker")
+    if h["qstyle"] in (1, 2):
+        no("quantisation style %d (irreversible wavelet) is not supported" % h["qstyle"])
+    if h["qstyle"]:
+        no("bad quantisation style %d" % h["qstyle"])
+    if len(h["exponents"]) != 3 * h["levels"] + 1:
+        no("QCD of %d sub-bands for %d decomposition levels" % (len(h["exponents"]), h["levels"]))
+    if h["mct"] > 1 or (h["mct"] and len(comps) != 3):
+        no("multiple-component transform on %d component(s)" % len(comps))
+    for r, (ppx, ppy) in enumerate(h["precincts"]):
+        sh = h["levels"] - r
+        if r and (ppx == 0 or ppy == 0):
+            no("precinct exponent 0 at resolution %d" % r)
+        if -(-h["width"] >> sh) > 1 << ppx or -(-h["height"] >> sh) > 1 << ppy:
+            no("more than one precinct in resolution %d" % r)
+    if h["tile_index"]:
+        no("more than one tile (tile index %d)" % h["tile_index"])
+    if h["tile_part"] or h["tile_parts"] > 1:
+        no("more than one tile-part (%d of %d)" % (h["tile_part"], h["tile_parts"]))
+    if h["psot"]:
+        end = h["sot"] + h["psot"]
+        if end < h["data"]:
+            no("tile-part length %d ends inside its header" % h["psot"])
+        if data[end:end + 2] == b"\xff\x90":
+            no("more than one tile-part")
+    rows = ifd["seg_h"] if ifd["tiled"] else min(ifd["seg_h"], ifd["length"])
+    if (h["width"], h["height"]) != (ifd["seg_w"], rows):
+        no("SIZ size %d x %d != segment size %d x %d" % (h["width"], h["height"], ifd["seg_w"], rows))
+    if len(comps) != spp:
+        no("a stream of %d components in segments of %d samples per pixel" % (len(comps), spp))
+    if prec != bits:
+        no("precision %d on a plane of %d-bit samples" % (prec, bits))
+
+
 def _tiff_pixel_type(path: str, ifd: dict) -> int:
     """The pixel type of an IFD this library can load, else PbxError 400 with the reason.
     SamplesPerPixel 1 to 4: every sample is a channel of that type, ExtraSamples included.
-    For a Compression-7 IFD the first segment is read and its header checked too, by every
-    caller (a band spec of no rows included: its refusals are tiff_plane_spec's)."""
+    For a Compression-7 IFD, and for a JPEG 2000 one (Compression 33003 / 33004 / 33005 / 34712),
+    the first segment is read and its header checked too, by every caller (a band spec of no
+    rows included: its refusals are tiff_plane_spec's)."""
     spp = ifd["spp"]
     if spp < 1 or spp > 4:
         raise PbxError(400, "%s: SamplesPerPixel %d (1 to 4 are supported)" % (path, spp))
@@ -1078,9 +1249,25 @@ def _tiff_pixel_type(path: str, ifd: dict) -> int:
     if jpeg and pt != UINT8:
         raise PbxError(400, "%s: Compression %d (1 none, 5 LZW, 7 JPEG on 8-bit samples, 8 / 32946 deflate, 50000 zstd)"
                        % (path, ifd["compression"]))
-    if ifd["compression"] not in (1, 5, 8, 32946, TIFF_ZSTD) and not jpeg:  # (the text older callers match)
+    j2k = ifd["compression"] in _TIFF_J2K_COMPRESSIONS
+    if ifd["compression"] not in (1, 5, 8, 32946, TIFF_ZSTD) and not jpeg and not j2k:  # (the text older callers match)
         raise PbxError(400, "%s: Compression %d (1 none, 5 LZW, 8 / 32946 deflate, 50000 zstd)"
                        % (path, ifd["compression"]))
+    if j2k:
+        planar = spp > 1 and ifd.get("planar", 1) == 2
+        if pt not in (UINT8, UINT16):
+            raise PbxError(400, "%s: Compression %d (JPEG 2000) on samples that are neither uint8 nor uint16"
+                           % (path, ifd["compression"]))
+        if ifd["predictor"] != 1:
+            raise PbxError(400, "%s: Predictor %d with Compression %d (JPEG 2000 segments take 1 only)"
+                           % (path, ifd["predictor"], ifd["compression"]))
+        if ifd.get("photometric") not in (None, 0, 1, 2):
+            raise PbxError(400, "%s: PhotometricInterpretation %d with Compression %d (JPEG 2000: 0, 1 or 2)"
+                           % (path, ifd["photometric"], ifd["compression"]))
+        if spp not in (1, 3) and not planar:
+            raise PbxError(400, "%s: Compression %d (JPEG 2000) with SamplesPerPixel %d (1, or 3 chunky)"
+                           % (path, ifd["compression"], spp))
+        _tiff_j2k_first_segment(path, ifd, 1 if planar else spp, ifd["bits"])
     if jpeg:
         planar = spp > 1 and ifd.get("planar", 1) == 2
         if ifd["predictor"] != 1:
@@ -1158,10 +1345,13 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
         tables = ifd.get("jpeg_tables")
         extra["jpeg"] = dict(tables=bytes(tables) if tables is not None else None,
                              ycbcr=ifd.get("photometric") == 6 and not planar)
+    if ifd["compression"] in _TIFF_J2K_COMPRESSIONS:  # -> the pbx_*_tiff_j2k calls
+        extra["j2k"] = True
     return dict(extra, samples_per_pixel=1 if planar else spp, sample=0 if planar else sample, pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
                 big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"], seg_h=ifd["seg_h"],
                 tiled=ifd["tiled"],
-                compression=TIFF_DEFLATE if ifd["compression"] == 32946 else ifd["compression"],
+                compression=TIFF_DEFLATE if ifd["compression"] == 32946 else
+                TIFF_J2K if ifd["compression"] in _TIFF_J2K_COMPRESSIONS else ifd["compression"],
                 predictor=ifd["predictor"], segments=segments)
 
 
@@ -1613,23 +1803,29 @@ class PixelsService:
         jpeg = dict(tables = tag 347's bytes or None, ycbcr) are JPEG segments (compression 7, UINT8
         planes, samples_per_pixel 1 or 3) and go through pbx_planes_register_tiff_jpeg; a call
         that mixes them with others (a file whose pages or levels differ in compression) is two
-        registrations, the others first, undone if the JPEG one fails.  All are
+        registrations, the others first, undone if the JPEG one fails.  Specs that carry j2k = True
+        are JPEG 2000 segments (compression TIFF_J2K, UINT8 or UINT16 planes, samples_per_pixel 1
+        or 3) and go through pbx_planes_register_tiff_j2k, a registration of their own after
+        those, in the same way.  All are
         registered or none.  Returns the plane ids (and the kernels' device ms with timing=True)."""
-        jp = [p.get("jpeg") is not None for p in planes]
-        if any(jp) and not all(jp):
-            rest = [k for k, j in enumerate(jp) if not j]
-            mine = [k for k, j in enumerate(jp) if j]
-            a, ta = self.register_tiff_planes([planes[k] for k in rest], timing=True)
+        jp = [2 if p.get("j2k") else 1 if p.get("jpeg") is not None else 0 for p in planes]
+        if len(set(jp)) > 1:
+            ids = [0] * len(planes)
+            done: List[int] = []
+            t0 = t1 = 0.0
             try:
-                b, tb = self.register_tiff_planes([planes[k] for k in mine], timing=True)
+                for codec in sorted(set(jp)):
+                    mine = [k for k, j in enumerate(jp) if j == codec]
+                    got, t = self.register_tiff_planes([planes[k] for k in mine], timing=True)
+                    done += got
+                    t0, t1 = t0 + t[0], t1 + t[1]
+                    for k, pid in zip(mine, got):
+                        ids[k] = pid
             except BaseException:
-                for pid in a:
+                for pid in done:
                     self.release_plane(pid)
                 raise
-            ids = [0] * len(planes)
-            for k, pid in list(zip(rest, a)) + list(zip(mine, b)):
-                ids[k] = pid
-            return (ids, (ta[0] + tb[0], ta[1] + tb[1])) if timing else ids
+            return (ids, (t0, t1)) if timing else ids
         if any(jp) or any(p.get("samples_per_pixel", 1) != 1 for p in planes):
             return self._register_tiff_samples(planes, timing)
         n = len(planes)
@@ -1670,7 +1866,7 @@ class PixelsService:
                 if spp > 1:
                     layer_of[id(p["segments"])] = l
             elif any(layers[l].get(f) != p.get(f) for f in ("samples_per_pixel", "seg_w", "seg_h", "tiled",
-                                                             "compression", "predictor", "jpeg")):
+                                                             "compression", "predictor", "jpeg", "j2k")):
                 raise PbxError(400, "plane %d: shares its segments with plane %d but not their layout"
                                % (k, planes.index(layers[l])))
             if not (0 <= sample < 2 ** 32):
@@ -1696,7 +1892,9 @@ class PixelsService:
             spps[l] = p.get("samples_per_pixel", 1)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
-        if layers[0].get("jpeg") is not None:  # (all of them: register_tiff_planes)
+        if layers[0].get("j2k"):  # (all of them: register_tiff_planes)
+            _check(lib().pbx_planes_register_tiff_j2k(self._h, n, descs, rf, nl, sgs, spps, ids, ms))
+        elif layers[0].get("jpeg") is not None:  # (all of them)
             jps = (PbxTiffJpeg * nl)()
             for l, p in enumerate(layers):
                 keep.append(_fill_tiff_jpeg(jps[l], p["jpeg"]))
@@ -1860,7 +2058,8 @@ class PixelsService:
 
     def band_write_tiff(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
                         compression: int, predictor: int, segments, timing: bool = False,
-                        samples_per_pixel: int = 1, sample: int = 0, jpeg: Optional[Mapping] = None):
+                        samples_per_pixel: int = 1, sample: int = 0, jpeg: Optional[Mapping] = None,
+                        j2k: bool = False):
         """pbx_band_write_tiff: rows [y0, y0 + rows) of one band, decoded on the GPU from the TIFF
         segment rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 that cover them (strips, or
         rows of tiles at full width, C order: a sequence of bytes, or pack_chunks()' (data,
@@ -1875,7 +2074,10 @@ class PixelsService:
         s.compression, s.predictor, s.flags = compression, predictor, 0
         s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
         ms = (ctypes.c_double * 2)()
-        if jpeg is not None:  # JPEG segments (compression 7): a spec's `jpeg` dict, tables and ycbcr
+        if j2k:  # JPEG 2000 segments (compression TIFF_J2K): a spec's `j2k`
+            _check(lib().pbx_band_write_tiff_j2k(self._h, plane_id, y0, rows, ctypes.byref(s), samples_per_pixel,
+                                                 sample, ms))
+        elif jpeg is not None:  # JPEG segments (compression 7): a spec's `jpeg` dict, tables and ycbcr
             j = PbxTiffJpeg()
             keep = _fill_tiff_jpeg(j, jpeg)
             _check(lib().pbx_band_write_tiff_jpeg(self._h, plane_id, y0, rows, ctypes.byref(s), samples_per_pixel,
@@ -2045,7 +2247,8 @@ class PixelsService:
                                                      tsp["segments"],
                                                      samples_per_pixel=tsp.get("samples_per_pixel", 1),
                                                      sample=tsp.get("sample", 0),
-                                                     **({"jpeg": tsp["jpeg"]} if tsp.get("jpeg") is not None else {}))
+                                                     **({"jpeg": tsp["jpeg"]} if tsp.get("jpeg") is not None else {}),
+                                                     **({"j2k": True} if tsp.get("j2k") else {}))
                             elif sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
