@@ -385,9 +385,11 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * Not supported (400 by the caller or here): SamplesPerPixel > 4, Predictor 3 on integer or
  * chunky multi-sample (RGB float) data, half-precision samples, FillOrder 2, pre-6.0 (LSB-first)
  * LZW streams, PackBits / LZMA / LERC / WebP / JPEG XR and other compressions, CMYK /
- * palette colour, sub-byte or 12-bit samples.  Lossless JPEG 2000 (the reversible 5/3 path) goes
- * through the pbx_*_tiff_j2k calls further down and through no other; the irreversible 9/7 path
- * ("JPEG-2000 Lossy", Aperio SVS) is not supported.  JPEG (Compression 7, baseline, 8-bit, gray / RGB /
+ * palette colour, sub-byte or 12-bit samples.  JPEG 2000, lossless (the reversible 5/3 path) and
+ * lossy (the irreversible 9/7 path, "JPEG-2000 Lossy", Aperio's 33003 / 33005), goes through the
+ * pbx_*_tiff_j2k calls further down and through no other; Aperio's habit of YCbCr components
+ * outside the codestream is not undone (components are stored as decoded).
+ * JPEG (Compression 7, baseline, 8-bit, gray / RGB /
  * YCbCr) goes through the pbx_*_tiff_jpeg calls further down and through no other: old-style JPEG
  * (Compression 6), progressive, lossless, arithmetic-coded and 12-bit streams, YCbCr under any
  * other compression, and the Aperio habit of YCbCr data under PhotometricInterpretation 2 (stored
@@ -519,22 +521,32 @@ int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
 /* JPEG 2000 segments (TIFF Compression 33003, 33004, 33005 and 34712, which all hand over as
  * compression = PBX_TIFF_J2K; DESIGN.md section 10b "JPEG 2000 segments"): every strip or tile is
  * one raw codestream (FF4F FF51 ...) of one tile of exactly the segment's size -- TileWidth x
- * TileLength, or ImageWidth x the strip's own row count.  Only the reversible path is decoded: the
- * 5/3 wavelet, no quantisation, optionally the reversible colour transform, so the planes equal
- * the encoder's input bit for bit.  The host reads SIZ, COD and QCD only; packet headers
+ * TileLength, or ImageWidth x the strip's own row count.  Two paths, chosen per segment by its COD
+ * (layers of one registration may mix them).  The reversible one: the 5/3 wavelet, QCD style 0 (no
+ * quantisation), optionally the reversible colour transform; the planes equal the encoder's input
+ * bit for bit.  The irreversible one: the 9/7 wavelet with QCD style 1 or 2 (scalar quantisation,
+ * the steps derived from the LL band's or given per sub-band), optionally the irreversible colour
+ * transform; T.800's arithmetic in float32 -- midpoint reconstruction of what the coded passes
+ * leave open, step = 2^(P + gain - exponent) (1 + mantissa / 2048), the lifting constants of
+ * F.3.8, "+ 2^(P-1)", round half to even, clamp -- so a plane equals the rounding of the exact
+ * (float64) values except where those lie within 1/64 (8 bits) or 1/8 (16 bits) of a half, and
+ * there differs by at most 1.  OpenJPEG's output is within 1 of it at 8 bits and within 3 at 16
+ * (its decoder's own high-band constant).  The host reads SIZ, COD and QCD only; packet headers
  * (k_tiff_j2k_packets), the MQ and bit-plane decoder (k_tiff_j2k_blocks, one wave per code block),
- * the inverse wavelet (k_tiff_j2k_idwt) and the colour transform, level shift and placement
- * (k_tiff_j2k_place) run on the device.
+ * the inverse wavelet (k_tiff_j2k_idwt, k_tiff_j2k_idwt97) and the colour transform, level shift
+ * and placement (k_tiff_j2k_place) run on the device.
  * Components: 1 (samples_per_pixel 1) of precision 8 on a PBX_UINT8 plane or 16 on a PBX_UINT16
  * plane, or 3 (samples_per_pixel 3, chunky) of precision 8, stored as they are or through the
- * inverse RCT as the COD says.  0 .. 32 levels, any code-block size, all five progression orders,
+ * inverse RCT (5/3) or ICT (9/7) as the COD says.  0 .. 32 levels, any code-block size, all five progression orders,
  * one layer, one precinct per resolution, code-block style 0; COM, TLM, PLM and PLT are skipped.
  * pbx_planes_register_tiff_samples for such layers: compression must be PBX_TIFF_J2K and
  * predictor 1 (the other TIFF calls keep answering "bad compression 34712").  Keys, all-or-none,
  * staging, statuses and kernel_ms ([0] decode through the inverse wavelet, [1] placement) are
  * shared with that call.  400 on the host, before anything is uploaded, names: a jp2 box instead
- * of a codestream, a header cut short, the irreversible wavelet and quantisation styles 1 and 2,
- * more than one layer, tile or tile-part, non-zero offsets, subsampled or signed components, a
+ * of a codestream, a header cut short, the irreversible wavelet with quantisation style 0 and
+ * quantisation style 1 or 2 with the reversible one, a QCD whose length does not fit its style and
+ * the levels, more than 30 magnitude bit-planes on a 9/7 sub-band (31 on a 5/3 one), a style-1
+ * exponent that goes negative, more than one layer, tile or tile-part, non-zero offsets, subsampled or signed components, a
  * precision other than 8 or 16, three components at precision 16, 2 or more than 3 components, a
  * SIZ size that is not the segment's, any code-block style bit, SOP or EPH markers, COC / QCC /
  * POC / RGN / PPM / PPT / CRG markers, more than one precinct in a resolution.  400 from the

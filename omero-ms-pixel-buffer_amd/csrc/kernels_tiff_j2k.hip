@@ -1,5 +1,6 @@
 // kernels_tiff_j2k.hip — JPEG 2000 TIFF segments (Compression 33003 / 33004 / 33005 / 34712: one
-// reversible codestream of one tile per strip or tile; DESIGN.md §10b "JPEG 2000 segments").
+// codestream of one tile per strip or tile, reversible 5/3 or irreversible 9/7; DESIGN.md §10b
+// "JPEG 2000 segments").
 // The host has read SIZ, COD and QCD and laid out every sub-band, code block and coefficient
 // from them (tiff_j2k_plan, runtime.cpp); packet headers and code-block bytes are read here only.
 //
@@ -8,10 +9,12 @@
 //                       length checked against the stream's length before it is stored
 //   k_tiff_j2k_blocks   tier 1, one wave per code block: the MQ decoder and the three coding
 //                       passes over state in LDS, then the block's coefficients, two's
-//                       complement int32, row by row into its sub-band's rectangle
+//                       complement int32, row by row into its sub-band's rectangle (9/7:
+//                       midpoint magnitudes, dequantised, as float32)
 //   k_tiff_j2k_idwt     the inverse 5/3 lifting, one workgroup per component, level by level
-//   k_tiff_j2k_place    inverse RCT, level shift, clamp, split and placement, clipped as
-//                       k_tiff_jpeg_place clips
+//   k_tiff_j2k_idwt97   the inverse 9/7 lifting in float32, same geometry
+//   k_tiff_j2k_place    inverse RCT (9/7: ICT, rounding half to even), level shift, clamp, split
+//                       and placement, clipped as k_tiff_jpeg_place clips
 //
 // The serial halves (tiff_j2k_dev.h) are run by lane 0 of their wave; the lanes together clear
 // the state before it and store the coefficients after it.  An arithmetic decoder has one chain of
@@ -63,11 +66,21 @@ __global__ __launch_bounds__(64) void k_tiff_j2k_blocks(const J2Block* __restric
     if (lane < J2_MQ_STATES) tab[lane] = c_j2_mq[lane];
     __syncthreads();
     const uint32_t planes = (uint32_t)B.mb - C.zbp;
-    const bool ok = C.passes != 0 && C.zbp < B.mb && planes <= 31 && C.passes <= 3 * planes - 2 &&
+    const bool irr = B.irrev != 0;  // (uniform: one block per workgroup)
+    const bool ok = C.passes != 0 && C.zbp < B.mb && planes <= (irr ? 30u : 31u) && C.passes <= 3 * planes - 2 &&
                     C.off <= S.len && C.len <= S.len - C.off;
-    if (ok && lane == 0)
-        j2k_block(mag, flg, ctx, tab, src + S.src_off + C.off, C.len, w, h, B.orient, planes, C.passes);
+    if (ok && lane == 0) {
+        if (irr) j2k_block<true>(mag, flg, ctx, tab, src + S.src_off + C.off, C.len, w, h, B.orient, planes, C.passes);
+        else j2k_block<false>(mag, flg, ctx, tab, src + S.src_off + C.off, C.len, w, h, B.orient, planes, C.passes);
+    }
     __syncthreads();
+    if (irr) {  // dequantised: twice the midpoint magnitude times half the step
+        float* out = (float*)(scratch + B.dst);
+        for (uint32_t y = 0; y < h; y++)
+            for (uint32_t x = lane; x < w; x += 64)
+                out[(uint64_t)y * B.pitch + x] = j2f_dequant(mag[y * w + x], flg[(y + 1) * (w + 2) + x + 1] & J2F_NEG, B.hstep);
+        return;
+    }
     int32_t* out = (int32_t*)(scratch + B.dst);
     for (uint32_t y = 0; y < h; y++)
         for (uint32_t x = lane; x < w; x += 64) {
@@ -95,6 +108,7 @@ __global__ __launch_bounds__(J2W_THREADS) void k_tiff_j2k_idwt(const J2Comp* __r
                                                                uint8_t* __restrict__ scratch) {
     if (blockIdx.x >= n) return;
     const J2Comp c = comps[blockIdx.x];
+    if (c.irrev) return;  // k_tiff_j2k_idwt97's
     int32_t* A = (int32_t*)(scratch + c.a);
     int32_t* Bp = (int32_t*)(scratch + c.b);
     const uint64_t W = c.w;
@@ -136,6 +150,76 @@ __global__ __launch_bounds__(J2W_THREADS) void k_tiff_j2k_idwt(const J2Comp* __r
     }
 }
 
+// ------------------------------------------------------------------------------ inverse 9/7
+// T.800 F.3.8 on float planes, in k_tiff_j2k_idwt's layout: per level the rows (A's [L | H]
+// halves -> B interleaved and scaled by K / 1/K, then the four lifting steps in place in B), then
+// the columns (B -> A likewise).  Each lifting step updates the samples of one parity from their
+// neighbours of the other, so inside a step no thread reads what another writes; between steps the
+// workgroup meets at a barrier, the planes staying in HBM (a 256 x 256 tile is 256 KiB a plane,
+// above the 160 KiB of LDS, and any tile size has to work: one form, no staged variant beside it).
+// The arithmetic is tiff_j2k_dev.h's, the CPU hook's too.
+constexpr uint32_t J2W97_THREADS = 1024;
+
+// one lifting step with constant `cst` on the samples of parity `par` of every line of the cw x ch
+// region of P: lines are rows (COLS false) or columns (COLS true), each of at least 2 samples
+template <bool COLS>
+__device__ __forceinline__ void j2_lift97(float* P, uint64_t W, uint32_t cw, uint32_t ch, uint32_t par, float cst) {
+    const uint32_t len = COLS ? ch : cw, nl = COLS ? cw : ch;
+    const uint32_t cnt = (len + 1 - par) / 2;
+    const uint32_t total = nl * cnt;  // (a plane has fewer than 2^29 samples: tiff_j2k_plan)
+    for (uint32_t i = threadIdx.x; i < total; i += J2W97_THREADS) {
+        const uint32_t line = COLS ? i % nl : i / cnt, k = COLS ? i / nl : i % cnt;
+        const uint32_t p = 2 * k + par;  // < len
+        const uint32_t pm = p ? p - 1 : 1, pp = p + 1 < len ? p + 1 : len - 2;  // whole-sample symmetry
+        float* base = COLS ? P + line : P + line * W;
+        const uint64_t st = COLS ? W : 1;
+        base[p * st] = j2f_lift(base[p * st], base[pm * st], base[pp * st], cst);
+    }
+}
+
+__global__ __launch_bounds__(J2W97_THREADS) void k_tiff_j2k_idwt97(const J2Comp* __restrict__ comps, uint32_t n,
+                                                                   uint8_t* __restrict__ scratch) {
+    if (blockIdx.x >= n) return;
+    const J2Comp c = comps[blockIdx.x];
+    if (!c.irrev) return;  // k_tiff_j2k_idwt's
+    float* A = (float*)(scratch + c.a);
+    float* Bp = (float*)(scratch + c.b);
+    const uint64_t W = c.w;
+    const uint32_t NL = c.levels < 32 ? c.levels : 32;
+    auto cs = [](uint32_t k) { return k == 0 ? J2F_DELTA : k == 1 ? J2F_GAMMA : k == 2 ? J2F_BETA : J2F_ALPHA; };
+    for (uint32_t r = 1; r <= NL; r++) {
+        const uint32_t sh = NL - r;  // 0 .. 31
+        const uint32_t cw = (uint32_t)((c.w + (1ull << sh) - 1) >> sh), ch = (uint32_t)((c.h + (1ull << sh) - 1) >> sh);
+        const uint32_t lw = (cw + 1) / 2, lh = (ch + 1) / 2;  // resolution r - 1
+        if (cw == lw && ch == lh) continue;                   // 1 x 1: nothing to undo
+        const uint32_t total = ch * cw;  // < 2^29: 32-bit divisions
+        for (uint32_t i = threadIdx.x; i < total; i += J2W97_THREADS) {
+            const uint32_t y = i / cw, x = i % cw;
+            const float v = A[y * W + x];
+            const uint32_t to = x < lw ? 2 * x : 2 * (x - lw) + 1;  // < cw
+            Bp[y * W + to] = cw > 1 ? j2f_scale(v, x < lw ? J2F_K : J2F_INVK) : v;
+        }
+        __syncthreads();
+        if (cw > 1)
+            for (uint32_t k = 0; k < 4; k++) {
+                j2_lift97<false>(Bp, W, cw, ch, k & 1, cs(k));
+                __syncthreads();
+            }
+        for (uint32_t i = threadIdx.x; i < total; i += J2W97_THREADS) {
+            const uint32_t y = i / cw, x = i % cw;
+            const float v = Bp[y * W + x];
+            const uint32_t to = y < lh ? 2 * y : 2 * (y - lh) + 1;  // < ch
+            A[to * W + x] = ch > 1 ? j2f_scale(v, y < lh ? J2F_K : J2F_INVK) : v;
+        }
+        __syncthreads();
+        if (ch > 1)
+            for (uint32_t k = 0; k < 4; k++) {
+                j2_lift97<true>(A, W, cw, ch, k & 1, cs(k));
+                __syncthreads();
+            }
+    }
+}
+
 // ------------------------------------------------------------------------------ placement
 // k_tiff_jpeg_place's geometry: a workgroup of four waves per (segment, run of J2P_ROWS segment
 // rows), rows clipped to run, window and plane, only the visible width walked, a lane per pixel.
@@ -168,6 +252,32 @@ __global__ __launch_bounds__(64 * J2P_WAVES) void k_tiff_j2k_place(const TJ2Seg*
     const int32_t* p0 = (const int32_t*)(scratch + u.src[0]);
     const int32_t* p1 = (const int32_t*)(scratch + u.src[nc == 3 ? 1 : 0]);
     const int32_t* p2 = (const int32_t*)(scratch + u.src[nc == 3 ? 2 : 0]);
+    if (u.rct & J2_SEG_IRREV) {  // float planes: inverse ICT, level shift, round half to even, clamp
+        const float* f0 = (const float*)p0;
+        const float* f1 = (const float*)p1;
+        const float* f2 = (const float*)p2;
+        for (int32_t r = r0 + (int32_t)wv; r < r1; r += (int32_t)J2P_WAVES) {
+            const uint64_t at = (uint64_t)r * u.w;
+            for (uint32_t x = lane; x < vis; x += 64) {
+                float v[3];
+                v[0] = f0[at + x];
+                if (nc == 3) {
+                    v[1] = f1[at + x];
+                    v[2] = f2[at + x];
+                    if (u.rct & 1) j2f_ict(v);
+                }
+#pragma unroll
+                for (uint32_t c = 0; c < 3; c++) {
+                    if (c >= nc || !d.dev[c]) continue;
+                    uint8_t* o = d.dev[c] + (int64_t)(y0 + r) * d.pitch + ((int64_t)x0 + x) * bpp;
+                    const uint32_t s = j2f_sample(v[c], prec);
+                    if (bpp == 1) *o = (uint8_t)s;
+                    else *(uint16_t*)o = d.big_endian ? (uint16_t)(s >> 8 | s << 8) : (uint16_t)s;
+                }
+            }
+        }
+        return;
+    }
     for (int32_t r = r0 + (int32_t)wv; r < r1; r += (int32_t)J2P_WAVES) {
         const uint64_t at = (uint64_t)r * u.w;
         for (uint32_t x = lane; x < vis; x += 64) {
@@ -176,7 +286,7 @@ __global__ __launch_bounds__(64 * J2P_WAVES) void k_tiff_j2k_place(const TJ2Seg*
             if (nc == 3) {
                 v[1] = p1[at + x];
                 v[2] = p2[at + x];
-                if (u.rct) {  // G = Y - ((U + V) >> 2), R = V + G, B = U + G
+                if (u.rct & 1) {  // G = Y - ((U + V) >> 2), R = V + G, B = U + G
                     const int32_t g = (int32_t)((uint32_t)v[0] - (uint32_t)((int32_t)((uint32_t)v[1] + (uint32_t)v[2]) >> 2));
                     const int32_t rr = (int32_t)((uint32_t)v[2] + (uint32_t)g), bb = (int32_t)((uint32_t)v[1] + (uint32_t)g);
                     v[0] = rr;
@@ -198,8 +308,8 @@ __global__ __launch_bounds__(64 * J2P_WAVES) void k_tiff_j2k_place(const TJ2Seg*
 
 hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams, const J2Band* d_bands,
                                   const J2Block* d_blocks, uint32_t n_blocks, const J2Comp* d_comps, uint32_t n_comps,
-                                  uint32_t max_coef, uint32_t max_flag, uint8_t* meta, const uint8_t* src,
-                                  uint8_t* scratch, uint32_t* err) {
+                                  uint32_t n_irrev, uint32_t max_coef, uint32_t max_flag, uint8_t* meta,
+                                  const uint8_t* src, uint8_t* scratch, uint32_t* err) {
     if (!n_streams) return hipSuccess;
     J2Code* code = (J2Code*)meta;
     uint32_t* tt = (uint32_t*)(meta + sizeof(J2Code) * (uint64_t)n_blocks);
@@ -210,7 +320,10 @@ hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uin
         hipLaunchKernelGGL(k_tiff_j2k_blocks, dim3(n_blocks), dim3(64), lds, st, d_blocks, n_blocks, code, d_streams, src,
                            scratch, max_coef, max_flag);
     }
-    if (n_comps) hipLaunchKernelGGL(k_tiff_j2k_idwt, dim3(n_comps), dim3(J2W_THREADS), 0, st, d_comps, n_comps, scratch);
+    if (n_comps > n_irrev)
+        hipLaunchKernelGGL(k_tiff_j2k_idwt, dim3(n_comps), dim3(J2W_THREADS), 0, st, d_comps, n_comps, scratch);
+    if (n_irrev)
+        hipLaunchKernelGGL(k_tiff_j2k_idwt97, dim3(n_comps), dim3(J2W97_THREADS), 0, st, d_comps, n_comps, scratch);
     return hipGetLastError();
 }
 

@@ -294,13 +294,15 @@ hipError_t launch_tiff_jpeg_place(hipStream_t st, const TJpegSeg* d_segs, uint32
                                   const TSplitDst* d_dst, const uint8_t* scratch);
 
 // JPEG 2000 TIFF segments (kernels_tiff_j2k.hip; Compression 33003 / 33004 / 33005 / 34712: one
-// reversible 5/3 codestream of one tile per segment).  The host reads SIZ, COD and QCD and lays
-// out everything below from them (tiff_j2k_plan); packet headers and code-block bytes are read
-// on the device only.
+// codestream of one tile per segment, reversible 5/3 or irreversible 9/7).  The host reads SIZ,
+// COD and QCD and lays out everything below from them (tiff_j2k_plan); packet headers and
+// code-block bytes are read on the device only.
 // A component's int32 coefficients live in a plane A of w x h dwords (pitch w) with every
 // resolution's low-pass band top left: resolution r covers [0, rh_r) x [0, rw_r), rw_r =
 // ceil(w / 2^(levels - r)), its HL band right of resolution r - 1, LH below, HH diagonal.  A
 // second plane B of the same size takes the inverse wavelet's horizontal pass.
+// An irreversible (9/7) stream's planes hold float32 where a reversible one's hold int32: tier 1
+// stores each coefficient dequantised (J2Block::hstep), the wavelet and the placement read floats.
 struct J2Band {            // one sub-band of one component of one stream
     uint32_t blk0;         // its first code block in the launch's J2Block / J2Code tables
     uint32_t nbx, nby;     // the code-block grid, raster order (0 x 0: an empty band)
@@ -309,7 +311,7 @@ struct J2Band {            // one sub-band of one component of one stream
                            // zero-bit-plane tree follows it
     uint32_t nodes;        // nodes of one tree
     uint32_t tlevels;      // levels of one tree
-    uint32_t pad;
+    float hstep;           // 9/7: half the quantisation step (its blocks carry it too), else 0
 };
 static_assert(sizeof(J2Band) == 32, "J2Band is uploaded as is");
 struct J2Stream {
@@ -319,7 +321,7 @@ struct J2Stream {
     uint32_t ncomp, levels;
     uint32_t cmajor;       // packets by component then resolution (PCRL, CPRL), else by
                            // resolution then component (LRCP, RLCP, RPCL)
-    uint32_t pad;
+    uint32_t irrev;        // 1: the irreversible 9/7 path (float planes)
 };
 static_assert(sizeof(J2Stream) == 32, "J2Stream is uploaded as is");
 struct J2Block {
@@ -328,16 +330,19 @@ struct J2Block {
     uint16_t w, h;         // clipped to the band
     uint32_t stream;
     uint8_t orient, mb;    // 0 LL, 1 HL, 2 LH, 3 HH
-    uint16_t pad;
+    uint16_t irrev;        // 1: magnitudes keep the half bit below and are stored as float * hstep
+    float hstep;           // half the band's quantisation step (0 on the reversible path)
+    uint32_t pad;
 };
-static_assert(sizeof(J2Block) == 24, "J2Block is uploaded as is");
+static_assert(sizeof(J2Block) == 32, "J2Block is uploaded as is");
 struct J2Code {            // written by k_tiff_j2k_packets (zero: the block is never included)
     uint32_t off, len;     // its bytes, from J2Stream::src_off; checked against J2Stream::len
     uint32_t passes, zbp;  // zbp <= mb and passes <= 3 (mb - zbp) - 2
 };
 struct J2Comp {            // one component of one stream, for the inverse wavelet
     uint64_t a, b;         // its planes in scratch
-    uint32_t w, h, levels, pad;
+    uint32_t w, h, levels;
+    uint32_t irrev;        // 1: float planes, k_tiff_j2k_idwt97's; 0: int32 planes, k_tiff_j2k_idwt's
 };
 static_assert(sizeof(J2Comp) == 32, "J2Comp is uploaded as is");
 struct TJ2Seg {            // one stream, for the placement
@@ -345,7 +350,8 @@ struct TJ2Seg {            // one stream, for the placement
     uint32_t w, rows;      // the segment's own size in pixels (the SIZ's)
     int32_t x0, y0;        // its origin in the plane
     uint32_t ncomp;        // 1 or 3
-    uint32_t rct;          // 1: inverse reversible colour transform
+    uint32_t rct;          // bit 0: inverse colour transform (RCT, or ICT on float planes);
+                           // bit 1 (J2_SEG_IRREV): float planes of an irreversible stream
     uint32_t prec;         // 8 or 16
     uint32_t dst;          // its entry in the launch's TSplitDst table
 };
@@ -354,14 +360,16 @@ static_assert(sizeof(TJ2Seg) == 56, "TJ2Seg is uploaded as is");
 // header (a length of more than 32 bits), 3 zero bit-planes above Mb or more passes than the
 // bit-planes allow.
 enum : uint32_t { J2E_END = 1, J2E_HEADER = 2, J2E_PLANES = 3 };
+constexpr uint32_t J2_SEG_IRREV = 2;
 // k_tiff_j2k_packets (one workgroup per stream), k_tiff_j2k_blocks (one wave per code block;
 // max_coef / max_flag: the most magnitudes / flag bytes a block of the launch needs in LDS),
-// k_tiff_j2k_idwt (one workgroup per component).  `meta` holds the J2Code table (n_blocks entries)
-// and after it the tag-tree nodes, all zero.
+// k_tiff_j2k_idwt / k_tiff_j2k_idwt97 (one workgroup per component; n_irrev of the n_comps
+// components are irreversible, and a kernel none of them needs is not launched).  `meta` holds
+// the J2Code table (n_blocks entries) and after it the tag-tree nodes, all zero.
 hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams, const J2Band* d_bands,
                                   const J2Block* d_blocks, uint32_t n_blocks, const J2Comp* d_comps, uint32_t n_comps,
-                                  uint32_t max_coef, uint32_t max_flag, uint8_t* meta, const uint8_t* src,
-                                  uint8_t* scratch, uint32_t* err);
+                                  uint32_t n_irrev, uint32_t max_coef, uint32_t max_flag, uint8_t* meta,
+                                  const uint8_t* src, uint8_t* scratch, uint32_t* err);
 hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t max_rows,
                                  const TSplitDst* d_dst, const uint8_t* scratch);
 

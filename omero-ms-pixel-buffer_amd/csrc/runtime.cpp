@@ -2365,7 +2365,7 @@ struct ZarrPlan {
     std::vector<J2Comp> j2comps;
     std::vector<TJ2Seg> j2segs;
     uint64_t j2nodes = 0;
-    uint32_t j2coef = 0, j2flag = 0, j2seg_rows = 0;
+    uint32_t j2coef = 0, j2flag = 0, j2seg_rows = 0, j2irrev = 0;  // j2irrev: irreversible (9/7) j2comps
 };
 
 // A plane cut out of a layer of chunks that hold `depth` planes each: its slice of every chunk
@@ -2803,7 +2803,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = launch_tiff_jpeg_decode(st, d_js, njpeg, d_jt, d_in, d_scr, d_err + nstreams + nchecks);
     if (e == hipSuccess && d_2s)
         e = launch_tiff_j2k_decode(st, d_2s, nj2, d_2b, d_2k, (uint32_t)P.j2blocks.size(), d_2c,
-                                   (uint32_t)P.j2comps.size(), P.j2coef, P.j2flag, d_2m, d_in, d_scr,
+                                   (uint32_t)P.j2comps.size(), P.j2irrev, P.j2coef, P.j2flag, d_2m, d_in, d_scr,
                                    d_err + nstreams + nchecks + njpeg);
     if (e == hipSuccess) e = hipEventRecord(ev[1], st);
     if (e == hipSuccess && !P.chunks.empty())
@@ -3363,14 +3363,17 @@ int tiff_jpeg_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, c
 // Compression 33003 / 33004 / 33005 / 34712: every strip or tile is one raw JPEG 2000 codestream
 // (SOC SIZ COD QCD ... SOT SOD packets EOC) of one tile.  The host reads marker segments only --
 // never a packet header, never a code-block byte -- and every length is checked against the bytes
-// it lies in.  Accepted: the reversible path (5/3 wavelet, no quantisation), one layer, one
-// precinct per resolution, code-block style 0; everything else is refused by name.
+// it lies in.  Accepted: the reversible path (5/3 wavelet, QCD style 0: no quantisation) and the
+// irreversible one (9/7 wavelet, QCD style 1 or 2: scalar quantisation, derived or expounded), one
+// layer, one precinct per resolution, code-block style 0; everything else is refused by name.
 struct J2kHeader {
     uint32_t w = 0, h = 0, ncomp = 0, prec = 0;
     uint32_t prog = 0, mct = 0, levels = 0, xcb = 0, ycb = 0, guard = 0;
     bool precincts = false;
     uint8_t pp[33];     // PPx | PPy << 4 per resolution
     uint8_t exps[97];   // per sub-band, QCD order
+    bool irrev = false; // the 9/7 path
+    float step[97];     // irrev: the sub-band's quantisation step (T.800 E.1.1)
     uint64_t data = 0, end = 0;  // the packets
 };
 
@@ -3380,7 +3383,8 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
     if (len < 2 || f[0] != 0xFF || f[1] != 0x4F) return fail(PBX_E_BADARG, "%s does not start with SOC (JPEG 2000 codestream)", what);
     uint64_t q = 2, sot = 0;
     bool siz = false, cod = false, qcd = false, tile = false;
-    uint32_t nexp = 0, qstyle = 0, psot = 0;
+    uint32_t nexp = 0, qstyle = 0, psot = 0, trans = 1, nq = 0;
+    uint8_t qraw[2 * 97];  // the QCD's entries as they stand: what they mean waits for COD
     for (;;) {
         if (q + 2 > len) return fail(PBX_E_BADARG, "%s: truncated header", what);
         if (f[q] != 0xFF) return fail(PBX_E_BADARG, "%s: truncated header (no marker at byte %llu)", what, (unsigned long long)q);
@@ -3441,8 +3445,8 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
             if (p[8])
                 return fail(PBX_E_BADARG, "%s: code-block style 0x%02x (bypass, reset, termall, vertically causal, predictable "
                             "termination and segmentation symbols are not supported)", what, p[8]);
-            if (p[9] == 0) return fail(PBX_E_BADARG, "%s: irreversible wavelet (9/7) is not supported", what);
-            if (p[9] != 1) return fail(PBX_E_BADARG, "%s: bad wavelet transformation %u", what, p[9]);
+            if (p[9] > 1) return fail(PBX_E_BADARG, "%s: bad wavelet transformation %u", what, p[9]);
+            trans = p[9];
             H.precincts = scod & 1;
             if (plen != 10 + (H.precincts ? H.levels + 1 : 0)) return fail(PBX_E_BADARG, "%s: truncated COD", what);
             for (uint32_t r = 0; r <= H.levels; r++) H.pp[r] = H.precincts ? p[10 + r] : 0xFF;
@@ -3453,12 +3457,10 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
             if (plen < 1) return fail(PBX_E_BADARG, "%s: truncated QCD", what);
             qstyle = p[0] & 31;
             H.guard = p[0] >> 5;
-            if (qstyle == 1 || qstyle == 2)
-                return fail(PBX_E_BADARG, "%s: quantisation style %u (irreversible wavelet) is not supported", what, qstyle);
-            if (qstyle) return fail(PBX_E_BADARG, "%s: bad quantisation style %u", what, qstyle);
-            nexp = plen - 1;
-            if (nexp > 97) return fail(PBX_E_BADARG, "%s: QCD of %u sub-bands", what, nexp);
-            for (uint32_t k = 0; k < nexp; k++) H.exps[k] = p[1 + k] >> 3;
+            if (qstyle > 2) return fail(PBX_E_BADARG, "%s: bad quantisation style %u", what, qstyle);
+            nq = plen - 1;
+            if (nq > (qstyle ? 2u * 97u : 97u)) return fail(PBX_E_BADARG, "%s: QCD of %u sub-bands", what, qstyle ? nq / 2 : nq);
+            memcpy(qraw, p + 1, nq);
             qcd = true;
         } else if (code == 0x90) {
             if (tile) return fail(PBX_E_BADARG, "%s: more than one tile-part", what);
@@ -3481,9 +3483,45 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
     }
     if (!cod) return fail(PBX_E_BADARG, "%s: no COD marker", what);
     if (!qcd) return fail(PBX_E_BADARG, "%s: no QCD marker", what);
-    if (nexp != 3 * H.levels + 1)
+    H.irrev = trans == 0;
+    if (H.irrev && qstyle == 0)
+        return fail(PBX_E_BADARG, "%s: irreversible wavelet (9/7) with quantisation style 0 (no quantisation)", what);
+    if (!H.irrev && qstyle)
+        return fail(PBX_E_BADARG, "%s: quantisation style %u (scalar quantisation) with the reversible wavelet (5/3)", what, qstyle);
+    const uint32_t nb = 3 * H.levels + 1;
+    if (qstyle == 0) {
+        nexp = nq;
+        for (uint32_t k = 0; k < nexp && k < nb; k++) H.exps[k] = qraw[k] >> 3;
+    } else if (qstyle == 2) {
+        if (nq & 1) return fail(PBX_E_BADARG, "%s: QCD of %u bytes in 16-bit entries (style 2)", what, nq);
+        nexp = nq / 2;
+    } else {
+        if (nq != 2) return fail(PBX_E_BADARG, "%s: QCD of %u bytes for the one entry of style 1", what, nq);
+        nexp = nb;
+    }
+    if (nexp != nb)
         return fail(PBX_E_BADARG, "%s: QCD of %u sub-bands for %u decomposition levels", what, nexp, H.levels);
     if (H.mct && H.ncomp != 3) return fail(PBX_E_BADARG, "%s: multiple-component transform on %u component(s)", what, H.ncomp);
+    if (H.irrev) {
+        // T.800 E.1.1: step = 2^(R_b - eps_b) (1 + mu_b / 2^11), R_b the precision plus the band's
+        // gain (0 LL, 1 HL and LH, 2 HH); style 1 derives every band from the LL entry (E-5):
+        // eps_b = eps_0 - (levels - n_b), mu_b = mu_0, n_b the decompositions at band b
+        for (uint32_t b = 0; b < nb; b++) {
+            const uint32_t e = qstyle == 2 ? (uint32_t)qraw[2 * b] << 8 | qraw[2 * b + 1] : (uint32_t)qraw[0] << 8 | qraw[1];
+            int32_t eps = (int32_t)(e >> 11);
+            const uint32_t mu = e & 2047u;
+            if (qstyle == 1) {
+                const uint32_t nbd = b ? H.levels - ((b + 2) / 3 - 1) : H.levels;
+                eps -= (int32_t)(H.levels - nbd);
+                if (eps < 0) return fail(PBX_E_BADARG, "%s: quantisation style 1 derives exponent %d for sub-band %u", what, eps, b);
+            }
+            const uint32_t gain = b ? ((b - 1) % 3 == 2 ? 2u : 1u) : 0u;
+            H.exps[b] = (uint8_t)eps;
+            H.step[b] = ldexpf(1.0f + (float)mu / 2048.0f, (int)(H.prec + gain) - eps);
+            if (H.guard + H.exps[b] > 31)  // (the half bit below bit-plane 0 takes one of the 31)
+                return fail(PBX_E_BADARG, "%s: %u magnitude bit-planes on a 9/7 sub-band (at most 30)", what, H.guard + H.exps[b] - 1);
+        }
+    }
     for (uint32_t k = 0; k < nexp; k++)
         if (H.guard + H.exps[k] > 32)
             return fail(PBX_E_BADARG, "%s: %u magnitude bit-planes (at most 31)", what, H.guard + H.exps[k] - 1);
@@ -3561,13 +3599,14 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
         if (plane > 0x7fffffffull) return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
         const uint32_t NL = H.levels, stream = (uint32_t)P.j2streams.size();
         auto res = [&](uint32_t v, uint32_t r) { return (uint32_t)(((uint64_t)v + (1ull << (NL - r)) - 1) >> (NL - r)); };
-        TJ2Seg seg{{0, 0, 0}, H.w, H.h, x0, y0, H.ncomp, H.mct, H.prec, dst};
+        TJ2Seg seg{{0, 0, 0}, H.w, H.h, x0, y0, H.ncomp, H.mct | (H.irrev ? J2_SEG_IRREV : 0u), H.prec, dst};
         const uint32_t band0 = (uint32_t)P.j2bands.size();
         for (uint32_t c = 0; c < H.ncomp; c++) {
             const uint64_t a = P.scratch;
             P.scratch += 2 * plane;
             seg.src[c] = a;
-            P.j2comps.push_back(J2Comp{a, a + plane, H.w, H.h, NL, 0});
+            P.j2comps.push_back(J2Comp{a, a + plane, H.w, H.h, NL, H.irrev ? 1u : 0u});
+            P.j2irrev += H.irrev ? 1 : 0;
             for (uint32_t b = 0; b < 3 * NL + 1; b++) {
                 const uint32_t r = b ? (b + 2) / 3 : 0, orient = b ? (b - 1) % 3 + 1 : 0;
                 const uint32_t cw = res(H.w, r), ch = res(H.h, r);
@@ -3578,7 +3617,9 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
                 const uint32_t xcb = std::min(H.xcb, ppx - (r ? 1 : 0)), ycb = std::min(H.ycb, ppy - (r ? 1 : 0));
                 const uint32_t nbx = bw && bh ? (bw + (1u << xcb) - 1) >> xcb : 0, nby = bw && bh ? (bh + (1u << ycb) - 1) >> ycb : 0;
                 const uint32_t gexp = H.guard + H.exps[b];
-                J2Band B{(uint32_t)P.j2blocks.size(), nbx, nby, gexp ? gexp - 1 : 0, (uint32_t)P.j2nodes, 0, 0, 0};
+                J2Band B{(uint32_t)P.j2blocks.size(), nbx, nby, gexp ? gexp - 1 : 0, (uint32_t)P.j2nodes, 0, 0, 0.0f};
+                const float hstep = H.irrev ? 0.5f * H.step[b] : 0.0f;
+                B.hstep = hstep;
                 if (nbx) {
                     uint32_t wl = nbx, hl = nby;
                     for (;;) {
@@ -3598,13 +3639,13 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
                         const uint32_t ox = bx << xcb, oy = by << ycb;
                         const uint32_t w = std::min(1u << xcb, bw - ox), h = std::min(1u << ycb, bh - oy);
                         P.j2blocks.push_back(J2Block{a + 4 * ((uint64_t)(by0 + oy) * H.w + bx0 + ox), H.w, (uint16_t)w, (uint16_t)h,
-                                                     stream, (uint8_t)orient, (uint8_t)B.mb, 0});
+                                                     stream, (uint8_t)orient, (uint8_t)B.mb, (uint16_t)(H.irrev ? 1 : 0), hstep, 0});
                         P.j2coef = std::max(P.j2coef, w * h);
                         P.j2flag = std::max(P.j2flag, (w + 2) * (h + 2));
                     }
             }
         }
-        P.j2streams.push_back(J2Stream{o + in_base + H.data, (uint32_t)(H.end - H.data), band0, H.ncomp, NL, H.prog >= 3 ? 1u : 0u, 0});
+        P.j2streams.push_back(J2Stream{o + in_base + H.data, (uint32_t)(H.end - H.data), band0, H.ncomp, NL, H.prog >= 3 ? 1u : 0u, H.irrev ? 1u : 0u});
         P.j2segs.push_back(seg);
         P.j2seg_rows = std::max(P.j2seg_rows, H.h);
         if (packets) *packets += (uint64_t)H.ncomp * (NL + 1);
@@ -3973,7 +4014,9 @@ int pbx_test_tiff_j2k_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t s
 // Test hook: the whole decode on the CPU, no context and no device call: the planner's tables,
 // then the device's own serial code (tiff_j2k_dev.h: j2k_packets per stream, j2k_block per code
 // block, each block's state in heap blocks of exactly the sizes k_tiff_j2k_blocks has in LDS),
-// the inverse 5/3 lifting, the inverse RCT, level shift and clamp.  out: samples_per_pixel planes
+// the inverse 5/3 lifting, the inverse RCT, level shift and clamp; for an irreversible stream the
+// same float32 functions the kernels call (tiff_j2k_dev.h: dequantisation, the 9/7 lifting, the
+// ICT and the rounding), in the kernels' order, so that the two agree bit for bit.  out: samples_per_pixel planes
 // of size_x * size_y samples, uint8 or host-order uint16, no pitch.
 int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t pixel_type,
                              int32_t samples_per_pixel, void* out, uint64_t out_bytes) {
@@ -4000,14 +4043,24 @@ int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t
         std::vector<int32_t> mag(w * h, 0);
         std::vector<uint8_t> flg((w + 2) * (h + 2), 0), ctx(19, 0);
         ctx[0] = 4 << 1; ctx[17] = 3 << 1; ctx[18] = 46 << 1;
-        if (C.passes && C.zbp < B.mb && planes <= 31 && C.passes <= 3 * planes - 2 && C.off <= S.len && C.len <= S.len - C.off) {
+        if (C.passes && C.zbp < B.mb && planes <= (B.irrev ? 30u : 31u) && C.passes <= 3 * planes - 2 && C.off <= S.len &&
+            C.len <= S.len - C.off) {
             // the block's bytes in a heap block of their own: a read past them is caught
             const std::vector<uint8_t> bytes(s->data + S.src_off + C.off, s->data + S.src_off + C.off + C.len);
-            j2k_block(mag.data(), flg.data(), ctx.data(), mq, bytes.data(), C.len, w, h, B.orient, planes, C.passes);
+            if (B.irrev) j2k_block<true>(mag.data(), flg.data(), ctx.data(), mq, bytes.data(), C.len, w, h, B.orient, planes, C.passes);
+            else j2k_block<false>(mag.data(), flg.data(), ctx.data(), mq, bytes.data(), C.len, w, h, B.orient, planes, C.passes);
         }
         for (uint32_t y = 0; y < h; y++)
-            for (uint32_t x = 0; x < w; x++)
-                scr[B.dst / 4 + (uint64_t)y * B.pitch + x] = (flg[(y + 1) * (w + 2) + x + 1] & J2F_NEG) ? -mag[y * w + x] : mag[y * w + x];
+            for (uint32_t x = 0; x < w; x++) {
+                const bool neg = flg[(y + 1) * (w + 2) + x + 1] & J2F_NEG;
+                int32_t& to = scr[B.dst / 4 + (uint64_t)y * B.pitch + x];
+                if (B.irrev) {  // float planes where the reversible path has int32 ones
+                    const float v = j2f_dequant(mag[y * w + x], neg, B.hstep);
+                    memcpy(&to, &v, 4);
+                } else {
+                    to = neg ? -mag[y * w + x] : mag[y * w + x];
+                }
+            }
     }
     // T.800 F.3: one dimension in place, low-pass samples at the even places
     auto sr = [](std::vector<int64_t>& x) {
@@ -4019,6 +4072,29 @@ int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t
     };
     for (const J2Comp& c : P.j2comps) {
         int32_t* A = scr.data() + c.a / 4;
+        if (c.irrev) {  // the inverse 9/7 in float32, tiff_j2k_dev.h's arithmetic: k_tiff_j2k_idwt97's
+            std::vector<float> F((uint64_t)c.w * c.h), line;
+            memcpy(F.data(), A, F.size() * 4);
+            for (uint32_t r = 1; r <= c.levels; r++) {
+                const uint32_t sh = c.levels - r;
+                const uint32_t cw = (uint32_t)((c.w + (1ull << sh) - 1) >> sh), ch = (uint32_t)((c.h + (1ull << sh) - 1) >> sh);
+                const uint32_t lw = (cw + 1) / 2, lh = (ch + 1) / 2;
+                for (uint32_t y = 0; y < ch; y++) {
+                    line.assign(cw, 0.0f);
+                    for (uint32_t x = 0; x < cw; x++) line[x < lw ? 2 * x : 2 * (x - lw) + 1] = F[(uint64_t)y * c.w + x];
+                    j2f_sr97(line.data(), cw, 1);
+                    for (uint32_t x = 0; x < cw; x++) F[(uint64_t)y * c.w + x] = line[x];
+                }
+                for (uint32_t x = 0; x < cw; x++) {
+                    line.assign(ch, 0.0f);
+                    for (uint32_t y = 0; y < ch; y++) line[y < lh ? 2 * y : 2 * (y - lh) + 1] = F[(uint64_t)y * c.w + x];
+                    j2f_sr97(line.data(), ch, 1);
+                    for (uint32_t y = 0; y < ch; y++) F[(uint64_t)y * c.w + x] = line[y];
+                }
+            }
+            memcpy(A, F.data(), F.size() * 4);
+            continue;
+        }
         for (uint32_t r = 1; r <= c.levels; r++) {
             const uint32_t sh = c.levels - r;
             const uint32_t cw = (uint32_t)((c.w + (1ull << sh) - 1) >> sh), ch = (uint32_t)((c.h + (1ull << sh) - 1) >> sh);
@@ -4041,9 +4117,20 @@ int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t
     for (const TJ2Seg& u : P.j2segs)
         for (uint32_t y = 0; y < u.rows && (int64_t)u.y0 + y < size_y; y++)
             for (uint32_t x = 0; x < u.w && (int64_t)u.x0 + x < size_x; x++) {
+                if (u.rct & J2_SEG_IRREV) {  // inverse ICT, level shift, round half to even, clamp
+                    float fv[3] = {0, 0, 0};
+                    for (uint32_t c = 0; c < u.ncomp; c++) memcpy(&fv[c], &scr[u.src[c] / 4 + (uint64_t)y * u.w + x], 4);
+                    if (u.ncomp == 3 && (u.rct & 1)) j2f_ict(fv);
+                    for (uint32_t c = 0; c < u.ncomp; c++) {
+                        const uint32_t t = j2f_sample(fv[c], u.prec);
+                        const uint64_t at = (uint64_t)c * size_x * size_y + (uint64_t)(u.y0 + y) * size_x + u.x0 + x;
+                        if (bpp == 1) ((uint8_t*)out)[at] = (uint8_t)t; else ((uint16_t*)out)[at] = (uint16_t)t;
+                    }
+                    continue;
+                }
                 int64_t v[3] = {0, 0, 0};
                 for (uint32_t c = 0; c < u.ncomp; c++) v[c] = scr[u.src[c] / 4 + (uint64_t)y * u.w + x];
-                if (u.ncomp == 3 && u.rct) {
+                if (u.ncomp == 3 && (u.rct & 1)) {
                     const int64_t g = v[0] - ((v[1] + v[2]) >> 2), rr = v[2] + g, bb = v[1] + g;
                     v[0] = rr; v[1] = g; v[2] = bb;
                 }

@@ -264,7 +264,11 @@ PBX_J2K_FN J2Nbr j2nbr(const uint8_t* f, uint32_t fp) {
 
 PBX_J2K_FN int32_t j2contrib(uint32_t f) { return (f & J2F_SIG) ? ((f & J2F_NEG) ? -1 : 1) : 0; }
 
-// the coefficient at *f becomes significant in bit-plane p: its sign (table D.3), flag and bit
+// the coefficient at *f becomes significant in bit-plane p: its sign (table D.3), flag and bit.
+// IRR (the irreversible path): every magnitude carries one more bit below bit-plane 0 and is at
+// all times twice the midpoint of what the passes so far leave open: 3 * 2^p here (|q| = 2^p, the
+// planes below p unknown: 2 (2^p + 2^(p-1))), and +- 2^p at a refinement bit in bit-plane p.
+template <bool IRR>
 PBX_J2K_FN void j2sign(J2MQ& m, uint8_t* f, uint32_t fp, int32_t* mag, uint32_t p) {
     int32_t hc = j2contrib(f[-1]) + j2contrib(f[1]), vc = j2contrib(*(f - fp)) + j2contrib(f[fp]);
     hc = hc < -1 ? -1 : hc > 1 ? 1 : hc;
@@ -278,13 +282,15 @@ PBX_J2K_FN void j2sign(J2MQ& m, uint8_t* f, uint32_t fp, int32_t* mag, uint32_t 
     const uint32_t cx = hc == 1 ? (uint32_t)(12 + vc) : vc == 0 ? 9u : 10u;
     const uint32_t s = j2mq_decode(m, cx) ^ flip;
     *f = (uint8_t)(*f | J2F_SIG | (s ? J2F_NEG : 0));
-    *mag |= (int32_t)(1u << p);
+    if (IRR) *mag = (int32_t)(3u << p);
+    else *mag |= (int32_t)(1u << p);
 }
 
 // One code block of w x h coefficients (w * h <= the magnitudes' room, (w + 2) * (h + 2) <= the
 // flags': the caller checks), magnitudes and flags zero, contexts at their initial states:
 // `passes` coding passes from bit-plane planes - 1 down (1 <= planes <= 31, passes <= 3 * planes
-// - 2: the caller checks), the first a cleanup pass.
+// - 2: the caller checks), the first a cleanup pass.  IRR: planes <= 30 (3 * 2^29 fits).
+template <bool IRR>
 PBX_J2K_FN void j2k_block(int32_t* mag, uint8_t* flg, uint8_t* ctx, const uint32_t* tab, const uint8_t* codebytes,
                           uint32_t len, uint32_t w, uint32_t h, uint32_t orient, uint32_t planes, uint32_t passes) {
     J2MQ m;
@@ -307,7 +313,7 @@ PBX_J2K_FN void j2k_block(int32_t* mag, uint8_t* flg, uint8_t* ctx, const uint32
                         if (*f & J2F_SIG) continue;
                         const J2Nbr n = j2nbr(f, fp);
                         if (n.hh + n.vv + n.dd == 0) continue;
-                        if (j2mq_decode(m, j2zc(orient, n.hh, n.vv, n.dd))) j2sign(m, f, fp, m0 + (y - y0) * w, p);
+                        if (j2mq_decode(m, j2zc(orient, n.hh, n.vv, n.dd))) j2sign<IRR>(m, f, fp, m0 + (y - y0) * w, p);
                         *f |= J2F_VIS;
                     }
                 } else if (kind == 1) {  // magnitude refinement
@@ -319,7 +325,9 @@ PBX_J2K_FN void j2k_block(int32_t* mag, uint8_t* flg, uint8_t* ctx, const uint32
                             const J2Nbr n = j2nbr(f, fp);
                             cx = n.hh + n.vv + n.dd ? 15 : 14;
                         }
-                        m0[(y - y0) * w] |= (int32_t)(j2mq_decode(m, cx) << p);
+                        const uint32_t bit = j2mq_decode(m, cx);
+                        if (IRR) m0[(y - y0) * w] += bit ? (int32_t)(1u << p) : -(int32_t)(1u << p);
+                        else m0[(y - y0) * w] |= (int32_t)(bit << p);
                         *f |= J2F_REF;
                     }
                 } else {  // cleanup
@@ -335,7 +343,7 @@ PBX_J2K_FN void j2k_block(int32_t* mag, uint8_t* flg, uint8_t* ctx, const uint32
                             if (!j2mq_decode(m, 17)) continue;
                             uint32_t k = j2mq_decode(m, 18) << 1;
                             k |= j2mq_decode(m, 18);  // 0 .. 3: inside the stripe
-                            j2sign(m, f0 + k * fp, fp, m0 + k * w, p);
+                            j2sign<IRR>(m, f0 + k * fp, fp, m0 + k * w, p);
                             first = y0 + k + 1;
                         }
                     }
@@ -347,7 +355,7 @@ PBX_J2K_FN void j2k_block(int32_t* mag, uint8_t* flg, uint8_t* ctx, const uint32
                         }
                         if (*f & J2F_SIG) continue;
                         const J2Nbr n = j2nbr(f, fp);
-                        if (j2mq_decode(m, j2zc(orient, n.hh, n.vv, n.dd))) j2sign(m, f, fp, m0 + (y - y0) * w, p);
+                        if (j2mq_decode(m, j2zc(orient, n.hh, n.vv, n.dd))) j2sign<IRR>(m, f, fp, m0 + (y - y0) * w, p);
                     }
                 }
             }
@@ -358,6 +366,71 @@ PBX_J2K_FN void j2k_block(int32_t* mag, uint8_t* flg, uint8_t* ctx, const uint32
         }
         kind = kind == 2 ? 0 : kind + 1;
     }
+}
+
+// ------------------------------------------------------------------- irreversible arithmetic
+// The per-sample float32 arithmetic of the 9/7 path (T.800 E.1, F.3.8, G.3), shared by the
+// kernels and the CPU hook.  Every operation is rounded to float32 on its own (no contraction
+// into fused multiply-adds), in one fixed order, so the two agree bit for bit.
+constexpr float J2F_K = 1.230174105f, J2F_INVK = (float)(1.0 / 1.230174105);
+constexpr float J2F_DELTA = 0.443506852f, J2F_GAMMA = 0.882911075f, J2F_BETA = -0.052980118f,
+                J2F_ALPHA = -1.586134342f;
+
+// tier 1's store: m2 is twice the midpoint magnitude, hstep half the band's step
+PBX_J2K_FN float j2f_dequant(int32_t m2, bool neg, float hstep) {
+#pragma clang fp contract(off)
+    const float v = (float)m2 * hstep;
+    return neg ? -v : v;
+}
+
+PBX_J2K_FN float j2f_scale(float x, float k) {
+#pragma clang fp contract(off)
+    return x * k;
+}
+
+// one lifting update: the neighbours' sum, times the constant, subtracted
+PBX_J2K_FN float j2f_lift(float x, float a, float b, float c) {
+#pragma clang fp contract(off)
+    const float s = a + b;
+    const float t = c * s;
+    return x - t;
+}
+
+// inverse irreversible colour transform (G.3): v = Y, Cb, Cr -> R, G, B
+PBX_J2K_FN void j2f_ict(float v[3]) {
+#pragma clang fp contract(off)
+    const float y = v[0], cb = v[1], cr = v[2];
+    const float r = y + 1.402f * cr;
+    const float g0 = y - 0.34413f * cb;
+    const float g = g0 - 0.71414f * cr;
+    const float b = y + 1.772f * cb;
+    v[0] = r;
+    v[1] = g;
+    v[2] = b;
+}
+
+// level shift, round half to even, clamp to [0, 2^prec - 1]; NaN and -inf give 0, +inf the top
+PBX_J2K_FN uint32_t j2f_sample(float v, uint32_t prec) {
+#pragma clang fp contract(off)
+    const float hi = (float)((1u << prec) - 1u);
+    const float t = v + (float)(1u << (prec - 1));
+    if (!(t > 0.0f)) return 0;
+    if (t >= hi) return (uint32_t)hi;
+    return (uint32_t)__builtin_rintf(t);
+}
+
+// One dimension of the inverse 9/7 in place over x[0 .. n) with stride `st`, the low-pass samples
+// already at the even places: the CPU hook's form; k_tiff_j2k_idwt97 runs the same five steps
+// with a barrier between them.  A signal of one sample passes through.
+PBX_J2K_FN float j2f_at(const float* x, int64_t n, int64_t st, int64_t i) {
+    return x[(i < 0 ? -i : i >= n ? 2 * (n - 1) - i : i) * st];
+}
+inline void j2f_sr97(float* x, int64_t n, int64_t st) {
+    if (n < 2) return;
+    for (int64_t i = 0; i < n; i++) x[i * st] = j2f_scale(x[i * st], i & 1 ? J2F_INVK : J2F_K);
+    const float c[4] = {J2F_DELTA, J2F_GAMMA, J2F_BETA, J2F_ALPHA};
+    for (int k = 0; k < 4; k++)
+        for (int64_t i = k & 1; i < n; i += 2) x[i * st] = j2f_lift(x[i * st], j2f_at(x, n, st, i - 1), j2f_at(x, n, st, i + 1), c[k]);
 }
 
 }  // namespace pbx

@@ -1068,8 +1068,10 @@ def j2k_header(data: bytes, what: str) -> dict:
     """The marker segments of a raw JPEG 2000 codestream up to SOD (no packet byte is read): width,
     height, offsets (XOsiz, YOsiz, XTOsiz, YTOsiz), tile (XTsiz, YTsiz), components = [(precision,
     signed, XRsiz, YRsiz)], scod, progression, layers, mct, levels, xcb, ycb (the code block's
-    exponents), style, transformation (1: the reversible 5/3), precincts = [(PPx, PPy)] per
-    resolution (15, 15 if none are declared), qstyle, guard, exponents (per sub-band), markers
+    exponents), style, transformation (1: the reversible 5/3, 0: the irreversible 9/7), precincts =
+    [(PPx, PPy)] per resolution (15, 15 if none are declared), qstyle, guard, qcd (the QCD's entries
+    as bytes), exponents and mantissas (per entry: style 0 has 8-bit entries and no mantissas,
+    styles 1 and 2 have 16-bit entries, style 1 only the LL band's; j2k_steps derives the rest), markers
     (the codes met, in order), tile_index, tile_part, tile_parts, psot, sot and data (the offset
     after SOD).  PbxError 400 with `what` for a JP2 file, a stream that does not start with SOC,
     or a header cut short."""
@@ -1115,7 +1117,12 @@ def j2k_header(data: bytes, what: str) -> dict:
         elif code == 0x5C:
             if len(p) < 1:
                 raise PbxError(400, "%s: truncated QCD" % what)
-            out.update(qstyle=p[0] & 31, guard=p[0] >> 5, qcd=bytes(p[1:]), exponents=[b >> 3 for b in p[1:]])
+            out.update(qstyle=p[0] & 31, guard=p[0] >> 5, qcd=bytes(p[1:]))
+            if out["qstyle"] in (1, 2):
+                ent = [p[k] << 8 | p[k + 1] for k in range(1, len(p) - 1, 2)]
+                out.update(exponents=[e >> 11 for e in ent], mantissas=[e & 2047 for e in ent])
+            else:
+                out.update(exponents=[b >> 3 for b in p[1:]], mantissas=[])
         elif code == 0x90:
             if len(p) != 8:
                 raise PbxError(400, "%s: truncated SOT" % what)
@@ -1124,6 +1131,23 @@ def j2k_header(data: bytes, what: str) -> dict:
             out.update(sot=q, tile_index=p[0] << 8 | p[1], psot=struct.unpack(">I", p[2:6])[0], tile_part=p[6],
                        tile_parts=p[7])
         q += 2 + L
+
+
+def j2k_steps(h: dict) -> list:
+    """Per sub-band (QCD order) of an irreversible header (j2k_header's dict, its QCD length already
+    checked) the pair (exponent, quantisation step): T.800 E.1.1, step = 2^(P + gain - exponent) *
+    (1 + mantissa / 2048), the gain 0 for LL, 1 for HL and LH, 2 for HH; style 1 derives every band
+    from the LL entry, its exponent lowered by the levels the band lies above the deepest."""
+    prec, levels = h["components"][0][0], h["levels"]
+    out = []
+    for b in range(3 * levels + 1):
+        if h["qstyle"] == 2:
+            eps, mu = h["exponents"][b], h["mantissas"][b]
+        else:
+            eps, mu = h["exponents"][0] - ((b + 2) // 3 - 1 if b else 0), h["mantissas"][0]
+        gain = 0 if b == 0 else 2 if (b - 1) % 3 == 2 else 1
+        out.append((eps, 2.0 ** (prec + gain - eps) * (1 + mu / 2048.0)))
+    return out
 
 
 def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int) -> None:
@@ -1180,20 +1204,36 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int) -> None:
     if h["style"]:
         no("code-block style 0x%02x (bypass, reset, termall, vertically causal, predictable termination and "
            "segmentation symbols are not supported)" % h["style"])
-    if h["transformation"] == 0:
-        no("irreversible wavelet (9/7) is not supported")
-    if h["transformation"] != 1:
+    if h["transformation"] > 1:
         no("bad wavelet transformation %d" % h["transformation"])
     if "qstyle" not in h:
         no("no QCD marker")
-    if h["qstyle"] in (1, 2):
-        no("quantisation style %d (irreversible wavelet) is not supported" % h["qstyle"])
-    if h["qstyle"]:
+    if h["qstyle"] > 2:
         no("bad quantisation style %d" % h["qstyle"])
-    if len(h["exponents"]) != 3 * h["levels"] + 1:
-        no("QCD of %d sub-bands for %d decomposition levels" % (len(h["exponents"]), h["levels"]))
+    irrev = h["transformation"] == 0
+    if irrev and h["qstyle"] == 0:
+        no("irreversible wavelet (9/7) with quantisation style 0 (no quantisation)")
+    if not irrev and h["qstyle"]:
+        no("quantisation style %d (scalar quantisation) with the reversible wavelet (5/3)" % h["qstyle"])
+    nq = len(h["qcd"])
+    if h["qstyle"] == 2 and nq & 1:
+        no("QCD of %d bytes in 16-bit entries (style 2)" % nq)
+    if h["qstyle"] == 1 and nq != 2:
+        no("QCD of %d bytes for the one entry of style 1" % nq)
+    nexp = 3 * h["levels"] + 1 if h["qstyle"] == 1 else len(h["exponents"])
+    if nexp != 3 * h["levels"] + 1:
+        no("QCD of %d sub-bands for %d decomposition levels" % (nexp, h["levels"]))
     if h["mct"] > 1 or (h["mct"] and len(comps) != 3):
         no("multiple-component transform on %d component(s)" % len(comps))
+    if irrev:
+        for b, (eps, _) in enumerate(j2k_steps(h)):
+            if eps < 0:
+                no("quantisation style 1 derives exponent %d for sub-band %d" % (eps, b))
+            if h["guard"] + eps > 31:
+                no("%d magnitude bit-planes on a 9/7 sub-band (at most 30)" % (h["guard"] + eps - 1))
+    for eps in ([] if irrev else h["exponents"]):
+        if h["guard"] + eps > 32:
+            no("%d magnitude bit-planes (at most 31)" % (h["guard"] + eps - 1))
     for r, (ppx, ppy) in enumerate(h["precincts"]):
         sh = h["levels"] - r
         if r and (ppx == 0 or ppy == 0):
