@@ -437,7 +437,7 @@ __device__ uint32_t read_huf_tree(ZIn& in, uint32_t wb, uint32_t q, uint32_t qen
     uint32_t total = 0;
     for (uint32_t g = 0; g < nw; g += 64) {
         const uint32_t i = g + lane, w = i < nw ? zlds[wb + ZD_WGT + i] : 0u;
-        if (w > 12) return 0;
+        if (__ballot(w > 12)) return 0;  // (every lane leaves: the weights differ per lane)
         uint32_t v = w ? 1u << (w - 1) : 0u;
         for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
         total += v;
