@@ -1,9 +1,10 @@
 // tiff_j2k_dev.h — the serial halves of the JPEG 2000 decoder (kernels_tiff_j2k.hip; DESIGN.md
 // §10b "JPEG 2000 segments"): the packet-header parser of tier 2 and the bit-plane decoder of
 // tier 1, each run by one lane.  Plain C++ over pointers, so that the very same text also runs
-// on the host: pbx_test_tiff_j2k_decode (runtime.cpp) decodes with it on the CPU, each block's
-// state in heap blocks of exactly the kernel's LDS sizes, which is how the tests without a GPU
-// and the sanitizer run of scripts/tiff_j2k_plan_san.cpp reach this code.
+// on the host: pbx_test_tiff_j2k_decode (source_plan.cpp, built by the host compiler without HIP)
+// decodes with it on the CPU, each block's state in heap blocks of exactly the kernel's LDS sizes,
+// which is how the tests without a GPU and the sanitizer run of scripts/tiff_j2k_plan_san.cpp
+// reach this code.
 //
 // Safety.  Every index below comes from the planner's geometry (J2Band, J2Block), never from the
 // stream: code-block bytes steer decisions and values, not addresses.  The two exceptions are
@@ -13,9 +14,9 @@
 #pragma once
 #include <stdint.h>
 
-#include "pbx_kernels.h"
+#include "pbx_decode_types.h"
 
-#define PBX_J2K_FN __host__ __device__ __forceinline__
+#define PBX_J2K_FN PBX_HD
 
 namespace pbx {
 

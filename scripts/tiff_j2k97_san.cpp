@@ -7,13 +7,8 @@
 // either empty (every coefficient zero: every sample exactly 2^(P-1), whatever the steps) or
 // pseudo-random bytes, which decode to garbage magnitudes of up to 30 bit-planes or are refused.
 //
-// Build and run from omero-ms-pixel-buffer_amd/ after `make`:
-//   hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-omit-frame-pointer -c csrc/runtime.cpp -o lib/runtime_san.o
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I../include \
-//       -c ../scripts/tiff_j2k97_san.cpp -o lib/tiff_j2k97_san.o
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined lib/tiff_j2k97_san.o \
-//       lib/runtime_san.o lib/kernels_*.o -o lib/tiff_j2k97_san && lib/tiff_j2k97_san
+// Build and run: `make san` in omero-ms-pixel-buffer_amd/ (this file and csrc/source_plan.cpp
+// compiled with the sanitizers by g++ alone).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

@@ -8,14 +8,8 @@
 // coefficients zero, every sample 2^(P-1)) or pseudo-random bytes, which decode to garbage or are
 // refused, and must do either without touching a byte outside the planner's geometry.
 //
-// Build and run from omero-ms-pixel-buffer_amd/ after `make` (the kernels' objects are linked
-// as they are; runtime.cpp's host code and this file are compiled with the sanitizers):
-//   hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-omit-frame-pointer -c csrc/runtime.cpp -o lib/runtime_san.o
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I../include \
-//       -c ../scripts/tiff_j2k_plan_san.cpp -o lib/tiff_j2k_plan_san.o
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined lib/tiff_j2k_plan_san.o \
-//       lib/runtime_san.o lib/kernels_*.o -o lib/tiff_j2k_plan_san && lib/tiff_j2k_plan_san
+// Build and run: `make san` in omero-ms-pixel-buffer_amd/ (this file and csrc/source_plan.cpp
+// compiled with the sanitizers by g++ alone).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

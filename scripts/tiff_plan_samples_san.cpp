@@ -2,14 +2,8 @@
 // program (no Python, no device call) that runs pbx_test_tiff_plan_samples on good and malformed
 // offset tables.  The planner and its refusals are host code only.
 //
-// Build and run from omero-ms-pixel-buffer_amd/ after `make` (the kernels' objects are linked
-// as they are; runtime.cpp's host code and this file are compiled with the sanitizers):
-//   hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined \
-//       -Xarch_host -fno-omit-frame-pointer -c csrc/runtime.cpp -o lib/runtime_san.o
-//   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-omit-frame-pointer -I../include \
-//       -c ../scripts/tiff_plan_samples_san.cpp -o lib/tiff_plan_samples_san.o
-//   hipcc --offload-arch=gfx950 -fsanitize=address,undefined lib/tiff_plan_samples_san.o \
-//       lib/runtime_san.o lib/kernels_*.o -o lib/tiff_plan_samples_san && lib/tiff_plan_samples_san
+// Build and run: `make san` in omero-ms-pixel-buffer_amd/ (this file and csrc/source_plan.cpp
+// compiled with the sanitizers by g++ alone).
 #include <cstdint>
 #include <cstdio>
 #include <cstring>

@@ -42,7 +42,7 @@ def test_exports_and_sizes():
     assert (pbx.TIFF_NONE, pbx.TIFF_LZW, pbx.TIFF_DEFLATE) == (1, 5, 8)
     assert re.search(r"PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8", header)
     # the C value: the static_assert next to the planner
-    rt = open(os.path.join(os.path.dirname(HERE), "omero-ms-pixel-buffer_amd", "csrc", "runtime.cpp")).read()
+    rt = open(os.path.join(os.path.dirname(HERE), "omero-ms-pixel-buffer_amd", "csrc", "source_plan.cpp")).read()
     c_size = int(re.search(r"static_assert\(sizeof\(pbx_tiff_segments\) == (\d+)", rt).group(1))
     assert ctypes.sizeof(pbx.PbxTiffSegments) == c_size == 40
     assert pbx.PbxTiffSegments.data.offset == 24 and pbx.PbxTiffSegments.offsets.offset == 32
