@@ -398,6 +398,12 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
 enum pbx_tiff_compression { PBX_TIFF_JPEG = 7 /* through the pbx_*_tiff_jpeg calls only */,
                             PBX_TIFF_J2K = 34712 /* through the pbx_*_tiff_j2k calls only */,
                             PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8, PBX_TIFF_ZSTD = 50000 };
+/* pbx_tiff_segments.flags.  J2K_PACKETS: the full packet structure of a JPEG 2000 codestream --
+ * 1 .. 64 quality layers, any precinct sizes, SOP and EPH markers (see the JPEG 2000 calls below).
+ * Taken by pbx_planes_register_tiff_j2k, pbx_band_write_tiff_j2k and the two pbx_test_tiff_j2k_*
+ * hooks and by no other call; without it those four refuse such streams by name, as they always
+ * have. */
+#define PBX_TIFF_F_J2K_PACKETS 1
 typedef struct pbx_tiff_segments {
     int32_t seg_w, seg_h;       /* tiles: TileWidth x TileLength (edge tiles are full, padded);
                                    strips: ImageWidth x RowsPerStrip (the last strip holds only
@@ -406,7 +412,7 @@ typedef struct pbx_tiff_segments {
     int32_t compression;        /* enum pbx_tiff_compression */
     int32_t predictor;          /* 1 none, 2 horizontal differencing (integer samples only),
                                    3 floating-point (float / double planes, one sample a pixel) */
-    int32_t flags;              /* 0 */
+    int32_t flags;              /* PBX_TIFF_F_*; 0 = none */
     const uint8_t* data;        /* the segments' bytes, concatenated in C order over the grid */
     const uint64_t* offsets;    /* gx * gy + 1 offsets into data (as pbx_zarr_chunks); a strip
                                    image has gx = 1 */
@@ -539,6 +545,17 @@ int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * plane, or 3 (samples_per_pixel 3, chunky) of precision 8, stored as they are or through the
  * inverse RCT (5/3) or ICT (9/7) as the COD says.  0 .. 32 levels, any code-block size, all five progression orders,
  * one layer, one precinct per resolution, code-block style 0; COM, TLM, PLM and PLT are skipped.
+ * With flags = PBX_TIFF_F_J2K_PACKETS also: 1 .. 64 quality layers, any declared precinct sizes
+ * (precincts smaller than the code block clip it, T.800 B.7; exponent 0 at resolution 0 only), and
+ * Scod bits 1 and 2 -- an SOP marker segment may stand before a packet (its Nsop is not verified),
+ * an EPH marker must follow every packet header.  The host then writes down the stream's packets in
+ * the order its progression gives (T.800 B.12); tier 2 walks that list, and a block whose bytes lie
+ * in several packets has them copied into one run first (k_tiff_j2k_gather).  Without the flag
+ * those streams are refused by name: "N quality layers (1)", "more than one precinct in resolution
+ * R", "SOP or EPH markers".  With it: "N quality layers (1 .. 64)", "too many packets", "too many
+ * block contributions"; a missing EPH is device code 2.  Refused either way: more than one tile or
+ * tile-part, code-block style bits, COC / QCC / POC / RGN / PPM / PPT / CRG, offsets, subsampling,
+ * signed components, the JP2 wrapper.
  * pbx_planes_register_tiff_samples for such layers: compression must be PBX_TIFF_J2K and
  * predictor 1 (the other TIFF calls keep answering "bad compression 34712").  Keys, all-or-none,
  * staging, statuses and kernel_ms ([0] decode through the inverse wavelet, [1] placement) are

@@ -4,9 +4,12 @@
 // The host has read SIZ, COD and QCD and laid out every sub-band, code block and coefficient
 // from them (tiff_j2k_plan, runtime.cpp); packet headers and code-block bytes are read here only.
 //
-//   k_tiff_j2k_packets  tier 2, one wave per stream: the packet headers (tag trees, passes,
-//                       Lblock, lengths) into one J2Code per code block, every offset and
-//                       length checked against the stream's length before it is stored
+//   k_tiff_j2k_packets  tier 2, one wave per stream: the packet headers of the host's packet
+//                       list (tag trees, passes, Lblock, lengths; layers, precincts, SOP / EPH)
+//                       into one J2Code per code block, every offset and length checked against
+//                       the stream's length before it is stored
+//   k_tiff_j2k_gather   a wave per contribution of a block whose bytes lie in several packets:
+//                       copies them into the block's one run in the stream's gather area
 //   k_tiff_j2k_blocks   tier 1, one wave per code block: the MQ decoder and the three coding
 //                       passes over state in LDS, then the block's coefficients, two's
 //                       complement int32, row by row into its sub-band's rectangle (9/7:
@@ -33,13 +36,35 @@ namespace pbx {
 __constant__ uint32_t c_j2_mq[J2_MQ_STATES] = {PBX_MQ_TABLE};
 
 __global__ __launch_bounds__(64) void k_tiff_j2k_packets(const J2Stream* __restrict__ st, uint32_t n,
+                                                         const J2Packet* __restrict__ packets,
                                                          const J2Band* __restrict__ bands,
                                                          const uint8_t* __restrict__ src, uint32_t* tt, J2Code* code,
-                                                         uint32_t* __restrict__ err) {
+                                                         J2Walk* walk, J2Contrib* con, uint32_t* __restrict__ err) {
     const uint32_t si = blockIdx.x;
     if (si >= n || threadIdx.x != 0) return;
     const J2Stream S = st[si];
-    err[si] = j2k_packets(S, bands, src, tt, code);
+    err[si] = j2k_packets(S, packets, bands, src, tt, code, walk, con);
+}
+
+// One wave per entry of the contribution table (streams of one layer have none): a cleared entry
+// ends at once, another's bytes go a byte per lane, stride 64, from the packets to the block's run.
+__global__ __launch_bounds__(64) void k_tiff_j2k_gather(const J2Contrib* __restrict__ con, uint32_t n,
+                                                        const J2Code* __restrict__ code,
+                                                        const J2Block* __restrict__ blocks, uint32_t n_blocks,
+                                                        const J2Stream* __restrict__ st, uint32_t n_streams,
+                                                        const uint8_t* __restrict__ src, uint8_t* __restrict__ scratch) {
+    const uint32_t lane = threadIdx.x, gi = blockIdx.x;
+    if (gi >= n) return;
+    const J2Contrib G = con[gi];
+    if (!G.len || G.block >= n_blocks) return;
+    const uint32_t si = blocks[G.block].stream;
+    if (si >= n_streams) return;
+    const J2Stream S = st[si];
+    uint32_t from, to;
+    if (!j2k_gather_span(S, code[G.block], G, &from, &to)) return;
+    const uint8_t* in = src + S.src_off + from;
+    uint8_t* out = scratch + S.gather + to;
+    for (uint32_t i = lane; i < G.len; i += 64) out[i] = in[i];
 }
 
 // LDS: max_coef magnitudes, max_flag flag bytes (rounded up to 16), the contexts, the MQ table.
@@ -67,11 +92,11 @@ __global__ __launch_bounds__(64) void k_tiff_j2k_blocks(const J2Block* __restric
     __syncthreads();
     const uint32_t planes = (uint32_t)B.mb - C.zbp;
     const bool irr = B.irrev != 0;  // (uniform: one block per workgroup)
-    const bool ok = C.passes != 0 && C.zbp < B.mb && planes <= (irr ? 30u : 31u) && C.passes <= 3 * planes - 2 &&
-                    C.off <= S.len && C.len <= S.len - C.off;
+    const uint8_t* bytes = j2k_code_bytes(S, C, src + S.src_off, scratch + S.gather);
+    const bool ok = C.passes != 0 && C.zbp < B.mb && planes <= (irr ? 30u : 31u) && C.passes <= 3 * planes - 2 && bytes;
     if (ok && lane == 0) {
-        if (irr) j2k_block<true>(mag, flg, ctx, tab, src + S.src_off + C.off, C.len, w, h, B.orient, planes, C.passes);
-        else j2k_block<false>(mag, flg, ctx, tab, src + S.src_off + C.off, C.len, w, h, B.orient, planes, C.passes);
+        if (irr) j2k_block<true>(mag, flg, ctx, tab, bytes, C.len, w, h, B.orient, planes, C.passes);
+        else j2k_block<false>(mag, flg, ctx, tab, bytes, C.len, w, h, B.orient, planes, C.passes);
     }
     __syncthreads();
     if (irr) {  // dequantised: twice the midpoint magnitude times half the step
@@ -306,15 +331,22 @@ __global__ __launch_bounds__(64 * J2P_WAVES) void k_tiff_j2k_place(const TJ2Seg*
     }
 }
 
-hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams, const J2Band* d_bands,
-                                  const J2Block* d_blocks, uint32_t n_blocks, const J2Comp* d_comps, uint32_t n_comps,
+// meta (zeroed by the caller): a J2Code and a J2Walk per block, n_con J2Contrib, the tag-tree nodes
+hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams,
+                                  const J2Packet* d_packets, const J2Band* d_bands, const J2Block* d_blocks,
+                                  uint32_t n_blocks, uint32_t n_con, const J2Comp* d_comps, uint32_t n_comps,
                                   uint32_t n_irrev, uint32_t max_coef, uint32_t max_flag, uint8_t* meta,
                                   const uint8_t* src, uint8_t* scratch, uint32_t* err) {
     if (!n_streams) return hipSuccess;
     J2Code* code = (J2Code*)meta;
-    uint32_t* tt = (uint32_t*)(meta + sizeof(J2Code) * (uint64_t)n_blocks);
-    hipLaunchKernelGGL(k_tiff_j2k_packets, dim3(n_streams), dim3(64), 0, st, d_streams, n_streams, d_bands, src, tt,
-                       code, err);
+    J2Contrib* con = (J2Contrib*)(meta + sizeof(J2Code) * (uint64_t)n_blocks);
+    J2Walk* walk = (J2Walk*)((uint8_t*)con + sizeof(J2Contrib) * (uint64_t)n_con);
+    uint32_t* tt = (uint32_t*)((uint8_t*)walk + sizeof(J2Walk) * (uint64_t)n_blocks);
+    hipLaunchKernelGGL(k_tiff_j2k_packets, dim3(n_streams), dim3(64), 0, st, d_streams, n_streams, d_packets, d_bands,
+                       src, tt, code, walk, con, err);
+    if (n_con)
+        hipLaunchKernelGGL(k_tiff_j2k_gather, dim3(n_con), dim3(64), 0, st, con, n_con, code, d_blocks, n_blocks,
+                           d_streams, n_streams, src, scratch);
     if (n_blocks) {
         const uint32_t lds = 4 * max_coef + ((max_flag + 15) & ~15u) + J2_CTX_BYTES + J2_TAB_BYTES;
         hipLaunchKernelGGL(k_tiff_j2k_blocks, dim3(n_blocks), dim3(64), lds, st, d_blocks, n_blocks, code, d_streams, src,

@@ -171,23 +171,46 @@ struct J2Band {            // one sub-band of one component of one stream
     uint32_t blk0;         // its first code block in the launch's J2Block / J2Code tables
     uint32_t nbx, nby;     // the code-block grid, raster order (0 x 0: an empty band)
     uint32_t mb;           // magnitude bit-planes: guard bits + exponent - 1 (0 .. 31)
+    float hstep;           // 9/7: half the quantisation step (its blocks carry it too), else 0
+};
+static_assert(sizeof(J2Band) == 20, "J2Band is uploaded as is");
+// One packet (T.800 B.9) of a stream's packet list: the host runs the progression order's loops
+// (B.12.1.1 - 5) over layers, resolutions, components and precincts and writes the packets down in
+// the order the stream holds them; tier 2 walks the list.  A precinct's part of a sub-band is a
+// window into the band's code-block grid, with a pair of tag trees of its own that all the layers'
+// packets of that precinct share.
+struct J2Window {
     uint32_t tt;           // its inclusion tag tree in the launch's node table (dwords); the
                            // zero-bit-plane tree follows it
     uint32_t nodes;        // nodes of one tree
     uint32_t tlevels;      // levels of one tree
-    float hstep;           // 9/7: half the quantisation step (its blocks carry it too), else 0
+    uint32_t x0, y0;       // its first code block in the band's grid
+    uint16_t nx, ny;       // its code blocks (0 x 0: the precinct misses the band)
 };
-static_assert(sizeof(J2Band) == 32, "J2Band is uploaded as is");
+static_assert(sizeof(J2Window) == 24, "J2Window is uploaded as is");
+struct J2Packet {
+    uint32_t band;         // the first J2Band of its resolution
+    uint16_t layer;
+    uint16_t nbands;       // 1 (resolution 0) or 3
+    J2Window win[3];
+};
+static_assert(sizeof(J2Packet) == 80, "J2Packet is uploaded as is");
 struct J2Stream {
     uint64_t src_off;      // the packets (after SOD) in the upload buffer
-    uint32_t len;          // their bytes
+    uint64_t gather;       // scratch offset of its gather area (layers > 1): `len` bytes
+    uint32_t len;          // the packets' bytes
     uint32_t band0;        // component c's band b (QCD order) is J2Band band0 + c * (3 levels + 1) + b
     uint32_t ncomp, levels;
-    uint32_t cmajor;       // packets by component then resolution (PCRL, CPRL), else by
-                           // resolution then component (LRCP, RLCP, RPCL)
-    uint32_t irrev;        // 1: the irreversible 9/7 path (float planes)
+    uint32_t pk0, npk;     // its packets in the launch's J2Packet table, in stream order
+    uint32_t blk0, nblk;   // its code blocks in the launch's J2Block / J2Code / J2Walk tables
+    uint32_t con0, ncon;   // its room in the launch's J2Contrib table: nblk * layers, 0 with one layer
+    uint32_t layers;       // 1 .. 64
+    uint32_t mode;         // J2S_*
 };
-static_assert(sizeof(J2Stream) == 32, "J2Stream is uploaded as is");
+static_assert(sizeof(J2Stream) == 64, "J2Stream is uploaded as is");
+// J2Stream::mode: the irreversible 9/7 path (float planes); Scod bit 1: a packet may start with an
+// SOP marker segment; Scod bit 2: every packet header ends with an EPH marker
+enum : uint32_t { J2S_IRREV = 1, J2S_SOP = 2, J2S_EPH = 4 };
 struct J2Block {
     uint64_t dst;          // scratch offset of its first coefficient in the component's plane A
     uint32_t pitch;        // of that plane, in dwords
@@ -200,9 +223,25 @@ struct J2Block {
 };
 static_assert(sizeof(J2Block) == 32, "J2Block is uploaded as is");
 struct J2Code {            // written by k_tiff_j2k_packets (zero: the block is never included)
-    uint32_t off, len;     // its bytes, from J2Stream::src_off; checked against J2Stream::len
-    uint32_t passes, zbp;  // zbp <= mb and passes <= 3 (mb - zbp) - 2
+    uint32_t off, len;     // its bytes: one run of len bytes at off & ~J2C_GATHERED from
+                           // J2Stream::src_off, or with J2C_GATHERED from J2Stream::gather in scratch;
+                           // checked against J2Stream::len
+    uint32_t passes, zbp;  // zbp <= mb and passes <= 3 (mb - zbp) - 2, summed over the layers
 };
+constexpr uint32_t J2C_GATHERED = 0x80000000u;  // (a stream has fewer than 2^31 bytes)
+struct J2Walk {            // tier 2's state of one block between a packet's header and its data, and
+                           // from layer to layer
+    uint32_t lblock;       // Lblock - 3 | its contributions of at least one byte so far << 8
+    uint32_t pend;         // the length its header gave in this packet + 1, 0: not in this packet
+};
+// A block's bytes in one packet, for k_tiff_j2k_gather: recorded for every block of a stream of
+// several layers, then cleared (len 0) where the block has no other, which is read where it lies.
+struct J2Contrib {
+    uint32_t block;        // in the launch's tables
+    uint32_t off, len;     // from J2Stream::src_off
+    uint32_t at;           // where they go in the block's run: its bytes before this packet
+};
+static_assert(sizeof(J2Contrib) == 16, "J2Contrib is a device table");
 struct J2Comp {            // one component of one stream, for the inverse wavelet
     uint64_t a, b;         // its planes in scratch
     uint32_t w, h, levels;

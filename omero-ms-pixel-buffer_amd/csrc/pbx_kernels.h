@@ -161,14 +161,17 @@ hipError_t launch_tiff_jpeg_decode(hipStream_t st, const JStream* d_streams, uin
 hipError_t launch_tiff_jpeg_place(hipStream_t st, const TJpegSeg* d_segs, uint32_t n, uint32_t max_rows,
                                   const TSplitDst* d_dst, const uint8_t* scratch);
 
-// JPEG 2000 TIFF segments (kernels_tiff_j2k.hip; J2Stream, J2Band, J2Block, J2Comp, TJ2Seg).
-// k_tiff_j2k_packets (one workgroup per stream), k_tiff_j2k_blocks (one wave per code block;
+// JPEG 2000 TIFF segments (kernels_tiff_j2k.hip; J2Stream, J2Packet, J2Band, J2Block, J2Comp,
+// TJ2Seg).  k_tiff_j2k_packets (one workgroup per stream), k_tiff_j2k_gather (one wave per entry
+// of the contribution table, n_con of them: 0 when every stream has one layer), k_tiff_j2k_blocks (one wave per code block;
 // max_coef / max_flag: the most magnitudes / flag bytes a block of the launch needs in LDS),
 // k_tiff_j2k_idwt / k_tiff_j2k_idwt97 (one workgroup per component; n_irrev of the n_comps
 // components are irreversible, and a kernel none of them needs is not launched).  `meta` holds
-// the J2Code table (n_blocks entries) and after it the tag-tree nodes, all zero.
-hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams, const J2Band* d_bands,
-                                  const J2Block* d_blocks, uint32_t n_blocks, const J2Comp* d_comps, uint32_t n_comps,
+// the J2Code table (n_blocks entries), the J2Contrib table (n_con), the J2Walk table (n_blocks) and
+// after them the tag-tree nodes, all zero.
+hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams,
+                                  const J2Packet* d_packets, const J2Band* d_bands, const J2Block* d_blocks,
+                                  uint32_t n_blocks, uint32_t n_con, const J2Comp* d_comps, uint32_t n_comps,
                                   uint32_t n_irrev, uint32_t max_coef, uint32_t max_flag, uint8_t* meta,
                                   const uint8_t* src, uint8_t* scratch, uint32_t* err);
 hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t max_rows,

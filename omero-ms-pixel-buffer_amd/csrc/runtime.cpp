@@ -2335,7 +2335,7 @@ struct ZarrInput {
 // into the planes P.fdst_plane names.  P.jstreams (JPEG-compressed TIFF segments) are decoded by
 // k_tiff_jpeg_decode after the other decoders, their err[] entries after the checks', and
 // P.jsegs upsampled, converted and placed into the planes of `sd` by k_tiff_jpeg_place.
-// P.j2streams (JPEG 2000 TIFF segments) go through k_tiff_j2k_packets, _blocks and _idwt after
+// P.j2streams (JPEG 2000 TIFF segments) go through k_tiff_j2k_packets, _gather, _blocks and _idwt after
 // those, their err[] entries last, and P.j2segs are placed by k_tiff_j2k_place.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms,
@@ -2363,7 +2363,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     const uint32_t nchecks = (uint32_t)checks.size(), njpeg = (uint32_t)P.jstreams.size();
     const uint32_t nj2 = (uint32_t)P.j2streams.size();
     const uint32_t nerr = nstreams + nchecks + njpeg + nj2;  // err[]: streams, checks, JPEG, JPEG 2000 streams
-    const uint64_t j2meta = sizeof(J2Code) * P.j2blocks.size() + 4 * P.j2nodes;
+    const uint64_t j2meta = (sizeof(J2Code) + sizeof(J2Walk)) * P.j2blocks.size() + sizeof(J2Contrib) * P.j2cons + 4 * P.j2nodes;
     uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
     ZStream* d_st = nullptr;
     ZCheck* d_ck = nullptr;
@@ -2380,6 +2380,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     TJpegSeg* d_jp = nullptr;
     J2Stream* d_2s = nullptr;
     J2Band* d_2b = nullptr;
+    J2Packet* d_2q = nullptr;
     J2Block* d_2k = nullptr;
     J2Comp* d_2c = nullptr;
     TJ2Seg* d_2p = nullptr;
@@ -2390,7 +2391,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         // queued copies, memsets or decoders may still write these blocks on an error path;
         // the pool hands them to other streams' batches as soon as they are back
         (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_js, (void*)d_jt, (void*)d_jp, (void*)d_2s, (void*)d_2b, (void*)d_2k, (void*)d_2c, (void*)d_2p, (void*)d_2m, (void*)d_err})
+        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_js, (void*)d_jt, (void*)d_jp, (void*)d_2s, (void*)d_2b, (void*)d_2q, (void*)d_2k, (void*)d_2c, (void*)d_2p, (void*)d_2m, (void*)d_err})
             if (q) ctx->dpool.put(q);
         for (auto& x : ev) if (x) (void)hipEventDestroy(x);
     };
@@ -2413,6 +2414,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (nj2) {
         dget(d_2s, sizeof(J2Stream) * nj2);
         dget(d_2b, sizeof(J2Band) * P.j2bands.size());
+        dget(d_2q, sizeof(J2Packet) * P.j2packets.size());
         dget(d_2k, sizeof(J2Block) * P.j2blocks.size());
         dget(d_2c, sizeof(J2Comp) * P.j2comps.size());
         dget(d_2p, sizeof(TJ2Seg) * P.j2segs.size());
@@ -2478,6 +2480,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
         e = hipMemcpyAsync(d_2s, P.j2streams.data(), sizeof(J2Stream) * nj2, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_2b)
         e = hipMemcpyAsync(d_2b, P.j2bands.data(), sizeof(J2Band) * P.j2bands.size(), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && d_2q && !P.j2packets.empty())
+        e = hipMemcpyAsync(d_2q, P.j2packets.data(), sizeof(J2Packet) * P.j2packets.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_2k && !P.j2blocks.empty())
         e = hipMemcpyAsync(d_2k, P.j2blocks.data(), sizeof(J2Block) * P.j2blocks.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_2c)
@@ -2501,7 +2505,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess && d_js)
         e = launch_tiff_jpeg_decode(st, d_js, njpeg, d_jt, d_in, d_scr, d_err + nstreams + nchecks);
     if (e == hipSuccess && d_2s)
-        e = launch_tiff_j2k_decode(st, d_2s, nj2, d_2b, d_2k, (uint32_t)P.j2blocks.size(), d_2c,
+        e = launch_tiff_j2k_decode(st, d_2s, nj2, d_2q, d_2b, d_2k, (uint32_t)P.j2blocks.size(), (uint32_t)P.j2cons, d_2c,
                                    (uint32_t)P.j2comps.size(), P.j2irrev, P.j2coef, P.j2flag, d_2m, d_in, d_scr,
                                    d_err + nstreams + nchecks + njpeg);
     if (e == hipSuccess) e = hipEventRecord(ev[1], st);

@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <tuple>
 #include <utility>
 
 #include "tiff_j2k_dev.h"
@@ -745,11 +746,14 @@ int tiff_jpeg_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, c
 // it lies in.  Accepted: the reversible path (5/3 wavelet, QCD style 0: no quantisation) and the
 // irreversible one (9/7 wavelet, QCD style 1 or 2: scalar quantisation, derived or expounded), one
 // layer, one precinct per resolution, code-block style 0; everything else is refused by name.
+// With PBX_TIFF_F_J2K_PACKETS (`packets` below) also 1 .. 64 quality layers, any precinct sizes and
+// SOP / EPH markers: tiff_j2k_plan writes the stream's packets down as a list (T.800 B.12).
 namespace {
 
 struct J2kHeader {
     uint32_t w = 0, h = 0, ncomp = 0, prec = 0;
     uint32_t prog = 0, mct = 0, levels = 0, xcb = 0, ycb = 0, guard = 0;
+    uint32_t layers = 1, scod = 0;
     bool precincts = false;
     uint8_t pp[33];     // PPx | PPy << 4 per resolution
     uint8_t exps[97];   // per sub-band, QCD order
@@ -758,7 +762,7 @@ struct J2kHeader {
     uint64_t data = 0, end = 0;  // the packets
 };
 
-int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* what) {
+int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* what, bool packets) {
     static const uint8_t jp2[12] = {0, 0, 0, 12, 'j', 'P', ' ', ' ', 13, 10, 0x87, 10};
     if (len >= 12 && !memcmp(f, jp2, 12)) return fail(PBX_E_BADARG, "%s: jp2 box, not a codestream", what);
     if (len < 2 || f[0] != 0xFF || f[1] != 0x4F) return fail(PBX_E_BADARG, "%s does not start with SOC (JPEG 2000 codestream)", what);
@@ -811,11 +815,14 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
             if (cod) return fail(PBX_E_BADARG, "%s: two COD markers", what);
             if (plen < 10) return fail(PBX_E_BADARG, "%s: truncated COD", what);
             const uint32_t scod = p[0], layers = (uint32_t)p[2] << 8 | p[3];
-            if (scod & 6) return fail(PBX_E_BADARG, "%s: SOP or EPH markers (Scod 0x%02x)", what, scod);
+            if ((scod & 6) && !packets) return fail(PBX_E_BADARG, "%s: SOP or EPH markers (Scod 0x%02x)", what, scod);
             if (scod & ~7u) return fail(PBX_E_BADARG, "%s: bad Scod 0x%02x", what, scod);
             H.prog = p[1];
             if (H.prog > 4) return fail(PBX_E_BADARG, "%s: bad progression order %u", what, H.prog);
-            if (layers != 1) return fail(PBX_E_BADARG, "%s: %u quality layers (1)", what, layers);
+            if (!packets && layers != 1) return fail(PBX_E_BADARG, "%s: %u quality layers (1)", what, layers);
+            if (layers < 1 || layers > 64) return fail(PBX_E_BADARG, "%s: %u quality layers (1 .. 64)", what, layers);
+            H.layers = layers;
+            H.scod = scod;
             H.mct = p[4];
             if (H.mct > 1) return fail(PBX_E_BADARG, "%s: bad multiple-component transform %u", what, H.mct);
             H.levels = p[5];
@@ -910,7 +917,7 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
         const uint32_t ppx = H.pp[r] & 15, ppy = H.pp[r] >> 4, sh = H.levels - r;
         if (r && (!ppx || !ppy)) return fail(PBX_E_BADARG, "%s: precinct exponent 0 at resolution %u", what, r);
         const uint64_t rw = ((uint64_t)H.w + (1ull << sh) - 1) >> sh, rh = ((uint64_t)H.h + (1ull << sh) - 1) >> sh;
-        if (rw > (1ull << ppx) || rh > (1ull << ppy))
+        if (!packets && (rw > (1ull << ppx) || rh > (1ull << ppy)))
             return fail(PBX_E_BADARG, "%s: more than one precinct in resolution %u", what, r);
     }
     H.end = len;
@@ -938,7 +945,7 @@ int tiff_j2k_check(const pbx_tiff_segments* s, int32_t pixel_type, int32_t spp) 
                     s->seg_w, s->seg_h);
     if (s->compression != PBX_TIFF_J2K) return fail(PBX_E_BADARG, "bad compression %d (the JPEG 2000 calls take 34712)", s->compression);
     if (s->predictor != 1) return fail(PBX_E_BADARG, "bad predictor %d on JPEG 2000 segments (1 only)", s->predictor);
-    if (s->flags) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
+    if (s->flags & ~PBX_TIFF_F_J2K_PACKETS) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
     if (pixel_type != PBX_UINT8 && pixel_type != PBX_UINT16)
         return fail(PBX_E_BADARG, "JPEG 2000 segments on a plane that is neither uint8 nor uint16");
     if (spp != 1 && spp != 3) return fail(PBX_E_BADARG, "JPEG 2000 segments of %d samples per pixel (1 or 3)", spp);
@@ -948,9 +955,10 @@ int tiff_j2k_check(const pbx_tiff_segments* s, int32_t pixel_type, int32_t spp) 
 // Host plan of the JPEG 2000 segment rows [sr0, sr1) (sr1 < 0: all) of a uint8 / uint16 plane:
 // tiff_plan's geometry; per segment a J2Stream and a TJ2Seg, per component two int32 planes in
 // scratch (8 bytes a sample, each plane rounded up to 256 bytes) and a J2Comp, per sub-band
-// (T.800 B.5) a J2Band with its two tag trees, per code block (the band's grid anchored at 0,
-// the last column and row clipped) a J2Block that says where its coefficients go.  Everything
-// follows from SIZ, COD and QCD.
+// (T.800 B.5) a J2Band, per code block (the band's grid anchored at 0, the last column and row
+// clipped) a J2Block that says where its coefficients go, and per layer and precinct a J2Packet,
+// in the order the stream's progression puts them, with the precinct's window into each band's
+// grid and the window's two tag trees.  Everything follows from SIZ, COD and QCD.
 int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segments* s, uint64_t in_base, ZarrPlan& P,
                   int64_t sr0, int64_t sr1, int spp, uint32_t dst, uint64_t* packets) {
     if (!s->tiled && s->seg_w != size_x)
@@ -971,7 +979,7 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
         char what[48];
         snprintf(what, sizeof what, "segment %lld", (long long)i);
         J2kHeader H;
-        if (int rc = j2k_parse_header(s->data + o, len, H, what)) return rc;
+        if (int rc = j2k_parse_header(s->data + o, len, H, what, s->flags & PBX_TIFF_F_J2K_PACKETS)) return rc;
         if ((int64_t)H.w != s->seg_w || (int64_t)H.h != rows)
             return fail(PBX_E_BADARG, "%s: SIZ size %u x %u != segment size %d x %d", what, H.w, H.h, s->seg_w, rows);
         if ((int)H.ncomp != spp)
@@ -983,7 +991,11 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
         const uint32_t NL = H.levels, stream = (uint32_t)P.j2streams.size();
         auto res = [&](uint32_t v, uint32_t r) { return (uint32_t)(((uint64_t)v + (1ull << (NL - r)) - 1) >> (NL - r)); };
         TJ2Seg seg{{0, 0, 0}, H.w, H.h, x0, y0, H.ncomp, H.mct | (H.irrev ? J2_SEG_IRREV : 0u), H.prec, dst};
-        const uint32_t band0 = (uint32_t)P.j2bands.size();
+        const uint32_t band0 = (uint32_t)P.j2bands.size(), blk0 = (uint32_t)P.j2blocks.size();
+        struct Cell {  // a sub-band's code-block size and grid
+            uint32_t xcb, ycb, nbx, nby;
+        };
+        std::vector<Cell> cells;
         for (uint32_t c = 0; c < H.ncomp; c++) {
             const uint64_t a = P.scratch;
             P.scratch += 2 * plane;
@@ -997,41 +1009,121 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
                 const uint32_t bx0 = orient & 1 ? lw : 0, by0 = orient & 2 ? lh : 0;
                 const uint32_t bw = !r ? cw : orient & 1 ? cw - lw : lw, bh = !r ? ch : orient & 2 ? ch - lh : lh;
                 const uint32_t ppx = H.pp[r] & 15, ppy = H.pp[r] >> 4;
+                // (B.7: a code block is clipped to the precinct's part of the band)
                 const uint32_t xcb = std::min(H.xcb, ppx - (r ? 1 : 0)), ycb = std::min(H.ycb, ppy - (r ? 1 : 0));
                 const uint32_t nbx = bw && bh ? (bw + (1u << xcb) - 1) >> xcb : 0, nby = bw && bh ? (bh + (1u << ycb) - 1) >> ycb : 0;
                 const uint32_t gexp = H.guard + H.exps[b];
-                J2Band B{(uint32_t)P.j2blocks.size(), nbx, nby, gexp ? gexp - 1 : 0, (uint32_t)P.j2nodes, 0, 0, 0.0f};
                 const float hstep = H.irrev ? 0.5f * H.step[b] : 0.0f;
-                B.hstep = hstep;
-                if (nbx) {
-                    uint32_t wl = nbx, hl = nby;
-                    for (;;) {
-                        B.nodes += wl * hl;
-                        B.tlevels++;
-                        if (wl == 1 && hl == 1) break;
-                        wl = (wl + 1) / 2;
-                        hl = (hl + 1) / 2;
-                    }
-                }
-                P.j2nodes += 2ull * B.nodes;
-                if (P.j2blocks.size() + (uint64_t)nbx * nby > 0x3ffffffull || P.j2nodes > 0x3fffffffull)
+                if (P.j2blocks.size() + (uint64_t)nbx * nby > 0x3ffffffull)
                     return fail(PBX_E_BADARG, "segment %lld: too many code blocks", (long long)i);
-                P.j2bands.push_back(B);
+                P.j2bands.push_back(J2Band{(uint32_t)P.j2blocks.size(), nbx, nby, gexp ? gexp - 1 : 0, hstep});
+                cells.push_back(Cell{xcb, ycb, nbx, nby});
                 for (uint32_t by = 0; by < nby; by++)
                     for (uint32_t bx = 0; bx < nbx; bx++) {
                         const uint32_t ox = bx << xcb, oy = by << ycb;
                         const uint32_t w = std::min(1u << xcb, bw - ox), h = std::min(1u << ycb, bh - oy);
                         P.j2blocks.push_back(J2Block{a + 4 * ((uint64_t)(by0 + oy) * H.w + bx0 + ox), H.w, (uint16_t)w, (uint16_t)h,
-                                                     stream, (uint8_t)orient, (uint8_t)B.mb, (uint16_t)(H.irrev ? 1 : 0), hstep, 0});
+                                                     stream, (uint8_t)orient, (uint8_t)(gexp ? gexp - 1 : 0), (uint16_t)(H.irrev ? 1 : 0), hstep, 0});
                         P.j2coef = std::max(P.j2coef, w * h);
                         P.j2flag = std::max(P.j2flag, (w + 2) * (h + 2));
                     }
             }
         }
-        P.j2streams.push_back(J2Stream{o + in_base + H.data, (uint32_t)(H.end - H.data), band0, H.ncomp, NL, H.prog >= 3 ? 1u : 0u, H.irrev ? 1u : 0u});
+        // The precincts (B.6) of every component and resolution, each with its windows into the
+        // resolution's bands and their tag trees, and the key the progression order sorts it by.
+        // With no offsets and no subsampling the position loops of B.12.1.3 - 5 visit a precinct
+        // when they reach its origin on the reference grid.
+        struct Prec {
+            uint64_t yo, xo;  // its origin on the reference grid
+            uint32_t c, r;
+            J2Packet pk;
+        };
+        std::vector<Prec> precs;
+        const uint32_t nbands = 3 * NL + 1;
+        for (uint32_t c = 0; c < H.ncomp; c++)
+            for (uint32_t r = 0; r <= NL; r++) {
+                const uint32_t ppx = H.pp[r] & 15, ppy = H.pp[r] >> 4;
+                const uint64_t npx = ((uint64_t)res(H.w, r) + (1ull << ppx) - 1) >> ppx;
+                const uint64_t npy = ((uint64_t)res(H.h, r) + (1ull << ppy) - 1) >> ppy;
+                if (precs.size() + npx * npy > 0xfffffull)
+                    return fail(PBX_E_BADARG, "segment %lld: too many packets", (long long)i);
+                const uint32_t fb = r ? 3 * r - 2 : 0, nb = r ? 3 : 1;
+                for (uint64_t py = 0; py < npy; py++)
+                    for (uint64_t px = 0; px < npx; px++) {
+                        Prec q{py << (ppy + NL - r), px << (ppx + NL - r), c, r, J2Packet{band0 + c * nbands + fb, 0, (uint16_t)nb, {}}};
+                        for (uint32_t k = 0; k < nb; k++) {
+                            const Cell& g = cells[c * nbands + fb + k];
+                            // the precinct's part of the band holds 2^(pb - cb) cells a side
+                            const uint32_t sx = ppx - (r ? 1 : 0) - g.xcb, sy = ppy - (r ? 1 : 0) - g.ycb;
+                            const uint64_t x0 = px << sx, y0 = py << sy;
+                            J2Window W{(uint32_t)P.j2nodes, 0, 0, 0, 0, 0, 0};
+                            if (x0 < g.nbx && y0 < g.nby) {
+                                W.x0 = (uint32_t)x0;
+                                W.y0 = (uint32_t)y0;
+                                W.nx = (uint16_t)std::min<uint64_t>(1ull << sx, g.nbx - x0);
+                                W.ny = (uint16_t)std::min<uint64_t>(1ull << sy, g.nby - y0);
+                                uint32_t wl = W.nx, hl = W.ny;
+                                for (;;) {
+                                    W.nodes += wl * hl;
+                                    W.tlevels++;
+                                    if (wl == 1 && hl == 1) break;
+                                    wl = (wl + 1) / 2;
+                                    hl = (hl + 1) / 2;
+                                }
+                            }
+                            P.j2nodes += 2ull * W.nodes;
+                            if (P.j2nodes > 0x3fffffffull)
+                                return fail(PBX_E_BADARG, "segment %lld: too many code blocks", (long long)i);
+                            q.pk.win[k] = W;
+                        }
+                        precs.push_back(q);
+                    }
+            }
+        // (a stable sort from component, resolution, raster order: what the keys leave open)
+        auto order = [&](auto key) {
+            std::stable_sort(precs.begin(), precs.end(), [&](const Prec& a, const Prec& b) { return key(a) < key(b); });
+        };
+        if (H.prog <= 1) order([](const Prec& q) { return std::make_tuple(q.r, q.c); });                // LRCP, RLCP
+        else if (H.prog == 2) order([](const Prec& q) { return std::make_tuple(q.r, q.yo, q.xo, q.c); });  // RPCL
+        else if (H.prog == 3) order([](const Prec& q) { return std::make_tuple(q.yo, q.xo, q.c, q.r); });  // PCRL
+        else order([](const Prec& q) { return std::make_tuple(q.c, q.yo, q.xo, q.r); });                // CPRL
+        const uint64_t npk = (uint64_t)precs.size() * H.layers;
+        if (P.j2packets.size() + npk > 0xfffffull) return fail(PBX_E_BADARG, "segment %lld: too many packets", (long long)i);
+        const uint32_t pk0 = (uint32_t)P.j2packets.size();
+        auto emit = [&](size_t k0, size_t k1, uint32_t l) {
+            for (size_t k = k0; k < k1; k++) {
+                P.j2packets.push_back(precs[k].pk);
+                P.j2packets.back().layer = (uint16_t)l;
+            }
+        };
+        if (H.prog == 0) {  // the layers outermost
+            for (uint32_t l = 0; l < H.layers; l++) emit(0, precs.size(), l);
+        } else if (H.prog == 1) {  // inside the resolution
+            for (size_t k0 = 0, k1; k0 < precs.size(); k0 = k1) {
+                for (k1 = k0; k1 < precs.size() && precs[k1].r == precs[k0].r;) k1++;
+                for (uint32_t l = 0; l < H.layers; l++) emit(k0, k1, l);
+            }
+        } else {  // innermost
+            for (size_t k = 0; k < precs.size(); k++)
+                for (uint32_t l = 0; l < H.layers; l++) emit(k, k + 1, l);
+        }
+        // a stream of several layers: a contribution a block and layer at most, and a gather area
+        // of the stream's length for the blocks whose bytes lie in more than one packet
+        const uint32_t nblk = (uint32_t)P.j2blocks.size() - blk0, slen = (uint32_t)(H.end - H.data);
+        const uint64_t ncon = H.layers > 1 ? (uint64_t)nblk * H.layers : 0;
+        if (P.j2cons + ncon > 0x3ffffffull) return fail(PBX_E_BADARG, "segment %lld: too many block contributions", (long long)i);
+        uint64_t gather = 0;
+        if (ncon) {
+            gather = P.scratch;
+            P.scratch += ((uint64_t)slen + 255) & ~255ull;
+        }
+        P.j2streams.push_back(J2Stream{o + in_base + H.data, gather, slen, band0, H.ncomp, NL, pk0, (uint32_t)npk, blk0, nblk,
+                                       (uint32_t)P.j2cons, (uint32_t)ncon, H.layers,
+                                       (H.irrev ? J2S_IRREV : 0u) | (H.scod & 2 ? J2S_SOP : 0u) | (H.scod & 4 ? J2S_EPH : 0u)});
+        P.j2cons += ncon;
         P.j2segs.push_back(seg);
         P.j2seg_rows = std::max(P.j2seg_rows, H.h);
-        if (packets) *packets += (uint64_t)H.ncomp * (NL + 1);
+        if (packets) *packets += npk;
     }
     return PBX_OK;
 }
@@ -1136,11 +1228,26 @@ int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t
     if (int rc = tiff_j2k_plan(size_x, size_y, bpp, s, 0, P, 0, -1, samples_per_pixel, 0)) return rc;
     static const uint32_t mq[J2_MQ_STATES] = {PBX_MQ_TABLE};
     std::vector<J2Code> code(P.j2blocks.size(), J2Code{0, 0, 0, 0});
+    std::vector<J2Walk> walk(P.j2blocks.size(), J2Walk{0, 0});
+    std::vector<J2Contrib> con(P.j2cons, J2Contrib{0, 0, 0, 0});
     std::vector<uint32_t> tt(P.j2nodes, 0);
     for (size_t i = 0; i < P.j2streams.size(); i++)
-        if (const uint32_t e = j2k_packets(P.j2streams[i], P.j2bands.data(), s->data, tt.data(), code.data()))
+        if (const uint32_t e = j2k_packets(P.j2streams[i], P.j2packets.data(), P.j2bands.data(), s->data, tt.data(),
+                                           code.data(), walk.data(), con.data()))
             return fail(PBX_E_BADARG, "corrupt segment stream %u (j2k, decoder code %u)", (unsigned)i, e);
     std::vector<int32_t> scr(P.scratch / 4, 0);
+    // k_tiff_j2k_gather: each stream's gather area a heap block of exactly its planned size
+    std::vector<std::vector<uint8_t>> gat(P.j2streams.size());
+    for (size_t i = 0; i < P.j2streams.size(); i++)
+        if (P.j2streams[i].ncon) gat[i].assign(P.j2streams[i].len, 0);
+    for (const J2Contrib& G : con) {
+        if (!G.len || G.block >= P.j2blocks.size()) continue;
+        const uint32_t si = P.j2blocks[G.block].stream;
+        const J2Stream& S = P.j2streams[si];
+        uint32_t from, to;
+        if (!j2k_gather_span(S, code[G.block], G, &from, &to)) continue;
+        memcpy(gat[si].data() + to, s->data + S.src_off + from, G.len);
+    }
     for (size_t i = 0; i < P.j2blocks.size(); i++) {
         const J2Block& B = P.j2blocks[i];
         const J2Code& C = code[i];
@@ -1150,10 +1257,10 @@ int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t
         std::vector<int32_t> mag(w * h, 0);
         std::vector<uint8_t> flg((w + 2) * (h + 2), 0), ctx(19, 0);
         ctx[0] = 4 << 1; ctx[17] = 3 << 1; ctx[18] = 46 << 1;
-        if (C.passes && C.zbp < B.mb && planes <= (B.irrev ? 30u : 31u) && C.passes <= 3 * planes - 2 && C.off <= S.len &&
-            C.len <= S.len - C.off) {
+        const uint8_t* run = j2k_code_bytes(S, C, s->data + S.src_off, gat[B.stream].data());
+        if (C.passes && C.zbp < B.mb && planes <= (B.irrev ? 30u : 31u) && C.passes <= 3 * planes - 2 && run) {
             // the block's bytes in a heap block of their own: a read past them is caught
-            const std::vector<uint8_t> bytes(s->data + S.src_off + C.off, s->data + S.src_off + C.off + C.len);
+            const std::vector<uint8_t> bytes(run, run + C.len);
             if (B.irrev) j2k_block<true>(mag.data(), flg.data(), ctx.data(), mq, bytes.data(), C.len, w, h, B.orient, planes, C.passes);
             else j2k_block<false>(mag.data(), flg.data(), ctx.data(), mq, bytes.data(), C.len, w, h, B.orient, planes, C.passes);
         }

@@ -59,14 +59,16 @@ struct ZarrPlan {
     std::vector<JTabSet> jtabs;
     uint32_t jseg_rows = 0;
     // JPEG 2000 TIFF segments (tiff_j2k_plan): one J2Stream and one TJ2Seg per segment, a J2Comp
-    // per component of it, a J2Band per sub-band of those and a J2Block per code block; the
-    // tag-tree nodes of the launch, the largest block's LDS needs, and the tallest segment
+    // per component of it, a J2Band per sub-band of those and a J2Block per code block, a
+    // J2Packet per layer and precinct; the tag-tree nodes of the launch, the largest block's LDS needs, and the tallest segment
     std::vector<J2Stream> j2streams;
+    std::vector<J2Packet> j2packets;   // every stream's packet list, in stream order
     std::vector<J2Band> j2bands;
     std::vector<J2Block> j2blocks;
     std::vector<J2Comp> j2comps;
     std::vector<TJ2Seg> j2segs;
     uint64_t j2nodes = 0;
+    uint64_t j2cons = 0;               // entries of the J2Contrib table (streams of several layers)
     uint32_t j2coef = 0, j2flag = 0, j2seg_rows = 0, j2irrev = 0;  // j2irrev: irreversible (9/7) j2comps
 };
 

@@ -6,11 +6,12 @@
 // which is how the tests without a GPU and the sanitizer run of scripts/tiff_j2k_plan_san.cpp
 // reach this code.
 //
-// Safety.  Every index below comes from the planner's geometry (J2Band, J2Block), never from the
-// stream: code-block bytes steer decisions and values, not addresses.  The two exceptions are
+// Safety.  Every index below comes from the planner's geometry (J2Packet, J2Band, J2Block), never
+// from the stream: code-block bytes steer decisions and values, not addresses.  The exceptions are
 // checked where they are read: a run-length position is two bits inside a full stripe of four
-// rows, and a code block's offset and length are compared with the stream's length before they
-// are stored (j2k_packets) and again before they are used.
+// rows, and a code block's offsets and lengths (in the packets, and in the gather area of a stream
+// of several layers) are compared with the stream's length before they are stored (j2k_packets)
+// and again before they are used (j2k_gather_span, j2k_code_bytes).
 #pragma once
 #include <stdint.h>
 
@@ -58,13 +59,14 @@ PBX_J2K_FN uint32_t j2bit(J2Bits& s) {
     return (s.buf >> s.ct) & 1u;
 }
 
-// Tag-tree decoding (B.10.2) of leaf (bx, by) against `threshold`: is its value below it?  A node
-// is one dword, its lower bound | (its value + 1, 0 while unknown) << 16, zero before the first
-// packet.  Level l holds ceil(nbx / 2^l) x ceil(nby / 2^l) nodes, the leaves first.
-PBX_J2K_FN bool j2tag(J2Bits& s, uint32_t* tree, const J2Band& B, uint32_t bx, uint32_t by, uint32_t threshold) {
-    uint32_t low = 0, off = B.nodes, val = 0;
-    for (uint32_t l = B.tlevels; l-- > 0;) {
-        const uint32_t wl = (B.nbx + (1u << l) - 1) >> l, hl = (B.nby + (1u << l) - 1) >> l;
+// Tag-tree decoding (B.10.2) of leaf (bx, by) of a precinct's window against `threshold`: is its
+// value below it?  A node is one dword, its lower bound | (its value + 1, 0 while unknown) << 16,
+// zero before the first packet.  Level l holds ceil(nx / 2^l) x ceil(ny / 2^l) nodes, the leaves
+// first.
+PBX_J2K_FN bool j2tag(J2Bits& s, uint32_t* tree, const J2Window& W, uint32_t bx, uint32_t by, uint32_t threshold) {
+    uint32_t low = 0, off = W.nodes, val = 0;
+    for (uint32_t l = W.tlevels; l-- > 0;) {
+        const uint32_t wl = (W.nx + (1u << l) - 1) >> l, hl = (W.ny + (1u << l) - 1) >> l;
         off -= wl * hl;
         const uint32_t i = off + (by >> l) * wl + (bx >> l);
         const uint32_t node = tree[i];
@@ -79,32 +81,49 @@ PBX_J2K_FN bool j2tag(J2Bits& s, uint32_t* tree, const J2Band& B, uint32_t bx, u
     return val != 0 && val - 1 < threshold;
 }
 
-// The packet headers of one stream: code[] of its included blocks (the others stay zero: never
-// included, coefficients zero).  Returns 0 or the device error code.
-PBX_J2K_FN uint32_t j2k_packets(const J2Stream& S, const J2Band* bands, const uint8_t* src, uint32_t* tt,
-                                J2Code* code) {
+// The packets of one stream, in the order of its packet list: code[] of its included blocks (the
+// others stay zero: never included, coefficients zero), their passes and bytes summed over the
+// layers.  walk[] (zero at the start) keeps a block's Lblock and its count of contributions from
+// layer to layer.  In a stream of several layers every contribution of at least one byte is also
+// written down in con[] (S.ncon entries from S.con0, zero at the start); at the end a block with
+// more than one gets its run in the stream's gather area (J2C_GATHERED, a prefix over the stream's
+// blocks), and the entries of the others are cleared: those blocks are read where they lie.
+// Returns 0 or the device error code.
+PBX_J2K_FN uint32_t j2k_packets(const J2Stream& S, const J2Packet* packets, const J2Band* bands, const uint8_t* src,
+                                uint32_t* tt, J2Code* code, J2Walk* walk, J2Contrib* con) {
     J2Bits s{src + S.src_off, 0, S.len, 0, 0, 0};
-    const uint32_t nres = S.levels + 1, npk = S.ncomp * nres, nb = 3 * S.levels + 1;
-    for (uint32_t p = 0; p < npk; p++) {
-        const uint32_t r = S.cmajor ? p % nres : p / S.ncomp, c = S.cmajor ? p / nres : p % S.ncomp;
-        const uint32_t b0 = S.band0 + c * nb + (r ? 3 * r - 2 : 0), nbn = r ? 3 : 1;
+    uint32_t ncon = 0;
+    for (uint32_t p = 0; p < S.npk; p++) {
+        const J2Packet& K = packets[S.pk0 + p];
+        const uint32_t nbn = K.nbands <= 3 ? K.nbands : 3, layer = K.layer;
+        // B.10.1 with Scod bit 1: FF91, Lsop = 4, Nsop (not verified) may stand before the header
+        if ((S.mode & J2S_SOP) && s.end - s.pos >= 6 && s.d[s.pos] == 0xFF && s.d[s.pos + 1] == 0x91) s.pos += 6;
         s.ct = 0;
         s.buf = 0;
         const uint32_t nonempty = j2bit(s);
         if (s.err) return s.err;
         for (uint32_t k = 0; k < nbn && nonempty; k++) {
-            const J2Band B = bands[b0 + k];
-            for (uint32_t by = 0; by < B.nby; by++)
-                for (uint32_t bx = 0; bx < B.nbx; bx++) {
-                    const bool incl = j2tag(s, tt + B.tt, B, bx, by, 1);
-                    if (s.err) return s.err;
-                    if (!incl) continue;
-                    uint32_t z = 1;
-                    while (!j2tag(s, tt + B.tt + B.nodes, B, bx, by, z)) {
+            const J2Band B = bands[K.band + k];
+            const J2Window W = K.win[k];
+            for (uint32_t by = 0; by < W.ny; by++)
+                for (uint32_t bx = 0; bx < W.nx; bx++) {
+                    const uint32_t bi = B.blk0 + (W.y0 + by) * B.nbx + W.x0 + bx;
+                    J2Code C = code[bi];
+                    if (!C.passes) {  // not yet included: the inclusion tree, then the zero bit-planes
+                        const bool incl = j2tag(s, tt + W.tt, W, bx, by, layer + 1);
                         if (s.err) return s.err;
-                        if (++z > B.mb + 1) return J2E_PLANES;
+                        if (!incl) continue;
+                        uint32_t z = 1;
+                        while (!j2tag(s, tt + W.tt + W.nodes, W, bx, by, z)) {
+                            if (s.err) return s.err;
+                            if (++z > B.mb + 1) return J2E_PLANES;
+                        }
+                        C.zbp = z - 1;
+                    } else {
+                        const uint32_t incl = j2bit(s);
+                        if (s.err) return s.err;
+                        if (!incl) continue;
                     }
-                    z--;
                     uint32_t n;
                     if (!j2bit(s)) n = 1;
                     else if (!j2bit(s)) n = 2;
@@ -124,31 +143,94 @@ PBX_J2K_FN uint32_t j2k_packets(const J2Stream& S, const J2Band* bands, const ui
                         }
                     }
                     if (s.err) return s.err;
-                    if ((int32_t)n > 3 * ((int32_t)B.mb - (int32_t)z) - 2) return J2E_PLANES;
-                    uint32_t nbits = 3 + (31u - (uint32_t)__builtin_clz(n));
-                    while (j2bit(s))
+                    C.passes += n;  // (at most 164 a packet, 64 packets: no overflow)
+                    if ((int32_t)C.passes > 3 * ((int32_t)B.mb - (int32_t)C.zbp) - 2) return J2E_PLANES;
+                    // one codeword segment (code-block style 0): Lblock + floor(log2(passes added)) bits
+                    J2Walk& K2 = walk[bi];
+                    uint32_t lb = K2.lblock & 0xffu;
+                    uint32_t nbits = 3 + lb + (31u - (uint32_t)__builtin_clz(n));
+                    while (j2bit(s)) {
+                        lb++;
                         if (++nbits > 32) return J2E_HEADER;
+                    }
+                    if (nbits > 32) return J2E_HEADER;
                     uint32_t len = 0;
                     for (uint32_t i = 0; i < nbits; i++) len = len << 1 | j2bit(s);
                     if (s.err) return s.err;
                     if (len > S.len) return J2E_END;
-                    code[B.blk0 + by * B.nbx + bx] = J2Code{0, len, n, z};
+                    K2.lblock = (K2.lblock & ~0xffu) | lb;
+                    K2.pend = len + 1;
+                    code[bi] = C;
                 }
         }
         if (s.buf == 0xFF) s.pos++;  // the stuffed byte after a header that ends in FF
         if (s.pos > s.end) return J2E_END;
+        if (S.mode & J2S_EPH) {
+            if (s.end - s.pos < 2 || s.d[s.pos] != 0xFF || s.d[s.pos + 1] != 0x92) return J2E_HEADER;  // no EPH
+            s.pos += 2;
+        }
         for (uint32_t k = 0; k < nbn && nonempty; k++) {
-            const J2Band B = bands[b0 + k];
-            for (uint32_t i = 0; i < B.nbx * B.nby; i++) {
-                J2Code& C = code[B.blk0 + i];
-                if (!C.passes) continue;
-                if (C.len > s.end - s.pos) return J2E_END;
-                C.off = s.pos;
-                s.pos += C.len;
+            const J2Band B = bands[K.band + k];
+            const J2Window W = K.win[k];
+            for (uint32_t by = 0; by < W.ny; by++)
+                for (uint32_t bx = 0; bx < W.nx; bx++) {
+                    const uint32_t bi = B.blk0 + (W.y0 + by) * B.nbx + W.x0 + bx;
+                    J2Walk& K2 = walk[bi];
+                    if (!K2.pend) continue;
+                    const uint32_t len = K2.pend - 1;
+                    K2.pend = 0;
+                    if (!len) continue;
+                    if (len > s.end - s.pos) return J2E_END;
+                    J2Code& C = code[bi];
+                    if (C.len > S.len - len) return J2E_END;  // (packets do not overlap: cannot be)
+                    if (!C.len) C.off = s.pos;
+                    if (S.layers > 1) {
+                        if (ncon >= S.ncon) return J2E_HEADER;  // (one a block and layer: cannot be)
+                        con[S.con0 + ncon++] = J2Contrib{bi, s.pos, len, C.len};
+                    }
+                    K2.lblock += 1u << 8;
+                    C.len += len;
+                    s.pos += len;
+                }
+        }
+    }
+    if (S.layers > 1) {
+        uint32_t run = 0;
+        for (uint32_t bi = S.blk0; bi < S.blk0 + S.nblk; bi++)
+            if ((walk[bi].lblock >> 8) > 1) {
+                J2Code& C = code[bi];
+                if (C.len > S.len - run) return J2E_END;  // (the runs are disjoint parts of the stream)
+                C.off = run | J2C_GATHERED;
+                run += C.len;
             }
+        for (uint32_t i = 0; i < ncon; i++) {
+            J2Contrib& G = con[S.con0 + i];
+            if ((walk[G.block].lblock >> 8) <= 1) G.len = 0;
         }
     }
     return 0;
+}
+
+// k_tiff_j2k_gather's arithmetic for one contribution: where its bytes lie in the stream (*from,
+// from S.src_off) and where they go in the gather area (*to, from S.gather), both checked against
+// the stream's length, which is the gather area's too.  False: nothing to copy.
+PBX_J2K_FN bool j2k_gather_span(const J2Stream& S, const J2Code& C, const J2Contrib& G, uint32_t* from, uint32_t* to) {
+    if (!G.len || !(C.off & J2C_GATHERED)) return false;
+    const uint32_t run = C.off & ~J2C_GATHERED;
+    if (G.off > S.len || G.len > S.len - G.off) return false;
+    if (G.at > C.len || G.len > C.len - G.at) return false;
+    if (run > S.len || C.len > S.len - run) return false;
+    *from = G.off;
+    *to = run + G.at;
+    return true;
+}
+
+// Where tier 1 reads a block's bytes: base[0] the stream's packets, base[1] its gather area.
+// Null: the run does not lie inside the stream's length.
+PBX_J2K_FN const uint8_t* j2k_code_bytes(const J2Stream& S, const J2Code& C, const uint8_t* packets, const uint8_t* gather) {
+    const uint32_t off = C.off & ~J2C_GATHERED;
+    if (off > S.len || C.len > S.len - off) return nullptr;
+    return (C.off & J2C_GATHERED ? gather : packets) + off;
 }
 
 // ------------------------------------------------------------------------------ tier 1

@@ -798,6 +798,7 @@ def pack_chunks(chunks: Sequence[Optional[bytes]]):
 TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
 TIFF_ZSTD = 50000
 TIFF_JPEG = 7  # through the pbx_*_tiff_jpeg calls only
+TIFF_F_J2K_PACKETS = 1  # pbx_tiff_segments.flags: JPEG 2000 layers, precincts, SOP / EPH (the pbx_*_tiff_j2k calls only)
 TIFF_J2K = 34712  # through the pbx_*_tiff_j2k calls only; what every Compression value below hands over as
 _TIFF_J2K_COMPRESSIONS = (33003, 33004, 33005, 34712)  # Bio-Formats' TiffCompression: JPEG-2000 / Lossy, Aperio's two
 _TIFF_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4,
@@ -1150,9 +1151,11 @@ def j2k_steps(h: dict) -> list:
     return out
 
 
-def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int) -> None:
+def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int, packets: bool = False) -> None:
     """What the first segment's header shows of a JPEG 2000 IFD this library cannot load: PbxError
-    400 with the reason, in the C-ABI's words (which checks every segment again)."""
+    400 with the reason, in the C-ABI's words (which checks every segment again).  `packets`: the
+    caller hands the segments over with TIFF_F_J2K_PACKETS, which takes 1 .. 64 quality layers, any
+    precinct sizes and SOP / EPH markers."""
     if not ifd["offsets"]:
         return
     with open(path, "rb") as f:
@@ -1191,12 +1194,14 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int) -> None:
         no("three components at precision 16")
     if "levels" not in h:
         no("no COD marker")
-    if h["scod"] & 6:
+    if h["scod"] & 6 and not packets:
         no("SOP or EPH markers (Scod 0x%02x)" % h["scod"])
     if h["progression"] > 4:
         no("bad progression order %d" % h["progression"])
-    if h["layers"] != 1:
+    if h["layers"] != 1 and not packets:
         no("%d quality layers (1)" % h["layers"])
+    if not 1 <= h["layers"] <= 64:
+        no("%d quality layers (1 .. 64)" % h["layers"])
     if h["levels"] > 32:
         no("%d decomposition levels (0 .. 32)" % h["levels"])
     if not (2 <= h["xcb"] <= 10 and 2 <= h["ycb"] <= 10 and h["xcb"] + h["ycb"] <= 12):
@@ -1238,7 +1243,7 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int) -> None:
         sh = h["levels"] - r
         if r and (ppx == 0 or ppy == 0):
             no("precinct exponent 0 at resolution %d" % r)
-        if -(-h["width"] >> sh) > 1 << ppx or -(-h["height"] >> sh) > 1 << ppy:
+        if not packets and (-(-h["width"] >> sh) > 1 << ppx or -(-h["height"] >> sh) > 1 << ppy):
             no("more than one precinct in resolution %d" % r)
     if h["tile_index"]:
         no("more than one tile (tile index %d)" % h["tile_index"])
@@ -1259,12 +1264,12 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int) -> None:
         no("precision %d on a plane of %d-bit samples" % (prec, bits))
 
 
-def _tiff_pixel_type(path: str, ifd: dict) -> int:
+def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False) -> int:
     """The pixel type of an IFD this library can load, else PbxError 400 with the reason.
     SamplesPerPixel 1 to 4: every sample is a channel of that type, ExtraSamples included.
     For a Compression-7 IFD, and for a JPEG 2000 one (Compression 33003 / 33004 / 33005 / 34712),
     the first segment is read and its header checked too, by every caller (a band spec of no
-    rows included: its refusals are tiff_plane_spec's)."""
+    rows included: its refusals are tiff_plane_spec's).  j2k_packets: as tiff_plane_spec's."""
     spp = ifd["spp"]
     if spp < 1 or spp > 4:
         raise PbxError(400, "%s: SamplesPerPixel %d (1 to 4 are supported)" % (path, spp))
@@ -1307,7 +1312,7 @@ def _tiff_pixel_type(path: str, ifd: dict) -> int:
         if spp not in (1, 3) and not planar:
             raise PbxError(400, "%s: Compression %d (JPEG 2000) with SamplesPerPixel %d (1, or 3 chunky)"
                            % (path, ifd["compression"], spp))
-        _tiff_j2k_first_segment(path, ifd, 1 if planar else spp, ifd["bits"])
+        _tiff_j2k_first_segment(path, ifd, 1 if planar else spp, ifd["bits"], j2k_packets)
     if jpeg:
         planar = spp > 1 and ifd.get("planar", 1) == 2
         if ifd["predictor"] != 1:
@@ -1338,24 +1343,29 @@ def _tiff_pixel_type(path: str, ifd: dict) -> int:
 
 
 def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int, level: int = 0,
-                    sample: int = 0) -> dict:
+                    sample: int = 0, j2k_packets: bool = False) -> dict:
     """register_tiff_planes() arguments for the plane that is sample `sample` of one IFD (a
     tiff_ifds() dict, main or SubIFD): its segments are read from the file as they are, nothing
     is decoded here.  A chunky IFD (PlanarConfiguration 1) of S samples per pixel gives
     samples_per_pixel = S and all its segments, each holding all S samples; a planar one
     (PlanarConfiguration 2) an ordinary single-sample spec (samples_per_pixel = 1, sample = 0)
-    of the segments of its group `sample`.  PbxError 400 names what is not supported."""
-    return dict(_tiff_segment_rows(path, ifd, 0, None, sample), image_id=image_id, z=z, c=c, t=t, level=level)
+    of the segments of its group `sample`.  PbxError 400 names what is not supported.
+    j2k_packets (JPEG 2000 IFDs only): take streams with several quality layers, several precincts
+    in a resolution and SOP / EPH markers; the spec then carries flags = TIFF_F_J2K_PACKETS.
+    Without it such a file is refused by name, as it always was."""
+    return dict(_tiff_segment_rows(path, ifd, 0, None, sample, j2k_packets), image_id=image_id, z=z, c=c, t=t,
+                level=level)
 
 
-def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sample: int = 0) -> dict:
+def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sample: int = 0,
+                       j2k_packets: bool = False) -> dict:
     """What tiff_plane_spec and tiff_band_spec share: the IFD's pixel type, geometry and byte
     order, and segments = (data, offsets) of its segment rows [sr0, sr1) (sr1 None: to the last;
     sr1 == sr0: none, segments is None and the file is not opened), each full width, read from
     the file as they are.  A planar IFD holds spp groups of gx * gy segments, one per sample:
     the rows are those of group `sample`."""
     import numpy as np
-    pt = _tiff_pixel_type(path, ifd)
+    pt = _tiff_pixel_type(path, ifd, j2k_packets)
     spp = ifd["spp"]
     if not 0 <= sample < spp:
         raise PbxError(400, "%s: sample %d outside SamplesPerPixel %d" % (path, sample, spp))
@@ -1387,6 +1397,8 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
                              ycbcr=ifd.get("photometric") == 6 and not planar)
     if ifd["compression"] in _TIFF_J2K_COMPRESSIONS:  # -> the pbx_*_tiff_j2k calls
         extra["j2k"] = True
+        if j2k_packets:
+            extra["flags"] = TIFF_F_J2K_PACKETS
     return dict(extra, samples_per_pixel=1 if planar else spp, sample=0 if planar else sample, pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
                 big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"], seg_h=ifd["seg_h"],
                 tiled=ifd["tiled"],
@@ -1395,7 +1407,7 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
                 predictor=ifd["predictor"], segments=segments)
 
 
-def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0) -> dict:
+def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0, j2k_packets: bool = False) -> dict:
     """band_write_tiff() arguments for rows [y0, y0 + rows) of the plane that is sample `sample`
     of one IFD (a tiff_ifds() dict, main or SubIFD; samples_per_pixel and sample as
     tiff_plane_spec, and of a planar IFD only that sample's segments are read): pixel_type, size_x, size_y, big_endian (the file's byte order),
@@ -1403,12 +1415,13 @@ def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0) ->
     rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 only, each full width; exactly those byte
     ranges of the file are read.  rows == 0 reads nothing (segments is None): the geometry and
     byte order alone (of a Compression-7 IFD also segment 0, whose header decides whether the file
-    can be loaded at all).  PbxError 400 as tiff_plane_spec, and for rows outside the plane."""
+    can be loaded at all).  PbxError 400 as tiff_plane_spec, and for rows outside the plane.
+    j2k_packets: as tiff_plane_spec's."""
     if rows < 0 or y0 < 0 or y0 + rows > ifd["length"]:
         raise PbxError(400, "%s: rows %d+%d outside the image (%d rows)" % (path, y0, rows, ifd["length"]))
     sr0 = y0 // ifd["seg_h"]
     sr1 = -(-(y0 + rows) // ifd["seg_h"]) if rows else sr0
-    return dict(_tiff_segment_rows(path, ifd, sr0, sr1, sample), y0=y0, rows=rows)
+    return dict(_tiff_segment_rows(path, ifd, sr0, sr1, sample, j2k_packets), y0=y0, rows=rows)
 
 
 def _ome_layout(path: str, xml: str, samples: int = 1) -> Optional[dict]:
@@ -1483,16 +1496,17 @@ def _ome_layout(path: str, xml: str, samples: int = 1) -> Optional[dict]:
     return dict(size_z=sz, size_c=sc, size_t=st, planes=planes, pixel_type=PIXEL_TYPES.index(typ), size_xy=sxy)
 
 
-def tiff_image_layout(path: str) -> dict:
+def tiff_image_layout(path: str, j2k_packets: bool = False) -> dict:
     """What register_tiff_image and TiffSource make of a file: ifds (tiff_ifds), planes = the
     (z, c, t) of main IFD k's first sample, samples = S (SamplesPerPixel, the same in every IFD),
     size_z / size_c / size_t, pixel_type, levels (1 + SubIFDs per main IFD).  Every sample is a
     channel, ExtraSamples included: channel c lies in the IFD of (z, c - c % S, t) as sample
     c % S.  OME-TIFF: the first Image's SizeZ/C/T and DimensionOrder, IFD k = channel group k in
     that order.  Any other multi-page TIFF: page k is t = k and size_c = S (Bio-Formats'
-    BaseTiffReader puts the pages of a plain TIFF on the time axis)."""
+    BaseTiffReader puts the pages of a plain TIFF on the time axis).  j2k_packets: as
+    tiff_plane_spec's, for the header checks of JPEG 2000 IFDs."""
     ifds = tiff_ifds(path)
-    pt = _tiff_pixel_type(path, ifds[0])
+    pt = _tiff_pixel_type(path, ifds[0], j2k_packets)
     S = ifds[0]["spp"]
     ome = _ome_layout(path, ifds[0]["description"], S) if ifds[0]["description"] else None
     if ome is not None:
@@ -1508,7 +1522,7 @@ def tiff_image_layout(path: str) -> dict:
     out["samples"] = S
     first = out["ifds"][0]
     for k, d in enumerate(out["ifds"]):
-        if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d) != pt:
+        if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d, j2k_packets) != pt:
             raise PbxError(400, "%s: IFD %d differs from the first in size or pixel type" % (path, k))
         for sd in [d] + d["subifds"]:
             if sd["spp"] != S:
@@ -1906,7 +1920,7 @@ class PixelsService:
                 if spp > 1:
                     layer_of[id(p["segments"])] = l
             elif any(layers[l].get(f) != p.get(f) for f in ("samples_per_pixel", "seg_w", "seg_h", "tiled",
-                                                             "compression", "predictor", "jpeg", "j2k")):
+                                                             "compression", "predictor", "jpeg", "j2k", "flags")):
                 raise PbxError(400, "plane %d: shares its segments with plane %d but not their layout"
                                % (k, planes.index(layers[l])))
             if not (0 <= sample < 2 ** 32):
@@ -1944,7 +1958,8 @@ class PixelsService:
         del keep
         return (list(ids), (ms[0], ms[1])) if timing else list(ids)
 
-    def register_tiff_image(self, path: str, image_id: int) -> Dict[int, Dict[Tuple[int, int, int], int]]:
+    def register_tiff_image(self, path: str, image_id: int,
+                            j2k_packets: bool = True) -> Dict[int, Dict[Tuple[int, int, int], int]]:
         """A whole TIFF / OME-TIFF file -- what the ordinary PixelsService opens through
         Bio-Formats for an image without an NGFF fileset (config.yaml:18) -- in ONE set of GPU
         launches: every plane of every level (tiff_image_layout: OME-XML axes, or page k = t;
@@ -1952,19 +1967,25 @@ class PixelsService:
         per pixel gives the S channels c .. c + S - 1: a chunky one is one layer, read and
         decoded once and split into its S planes on the GPU; a planar one S single-sample
         planes.  All are registered, or none.  Returns {level: {(z, c, t): plane id}}, as
-        register_ngff_image."""
-        lay = tiff_image_layout(path)
+        register_ngff_image.  j2k_packets (default on here, where whole files are served): JPEG
+        2000 IFDs are read with tiff_plane_spec's keyword of that name."""
+        lay = tiff_image_layout(path, j2k_packets)
+
+        def plane_spec(d, *a, **kw):  # (the keyword only where it means something)
+            if j2k_packets and d["compression"] in _TIFF_J2K_COMPRESSIONS:
+                kw["j2k_packets"] = True
+            return tiff_plane_spec(path, d, *a, **kw)
         specs, keys = [], []
         for (z, c, t), ifd in zip(lay["planes"], lay["ifds"]):
             for k, d in enumerate([ifd] + ifd["subifds"]):
-                first = tiff_plane_spec(path, d, image_id, z, c, t, k)
+                first = plane_spec(d, image_id, z, c, t, k)
                 for s in range(lay["samples"]):
                     if s == 0:
                         specs.append(first)
                     elif first["samples_per_pixel"] > 1:  # chunky: the same segments object, one layer
                         specs.append(dict(first, c=c + s, sample=s))
                     else:  # planar: the sample's own segments
-                        specs.append(tiff_plane_spec(path, d, image_id, z, c + s, t, k, sample=s))
+                        specs.append(plane_spec(d, image_id, z, c + s, t, k, sample=s))
                     keys.append((k, (z, c + s, t)))
         ids = self.register_tiff_planes(specs)
         out: Dict[int, Dict[Tuple[int, int, int], int]] = {}
@@ -2099,7 +2120,7 @@ class PixelsService:
     def band_write_tiff(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
                         compression: int, predictor: int, segments, timing: bool = False,
                         samples_per_pixel: int = 1, sample: int = 0, jpeg: Optional[Mapping] = None,
-                        j2k: bool = False):
+                        j2k: bool = False, flags: int = 0):
         """pbx_band_write_tiff: rows [y0, y0 + rows) of one band, decoded on the GPU from the TIFF
         segment rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 that cover them (strips, or
         rows of tiles at full width, C order: a sequence of bytes, or pack_chunks()' (data,
@@ -2107,11 +2128,12 @@ class PixelsService:
         register_tiff_planes; the sparse plane must have been created in the file's byte order.
         With samples_per_pixel > 1 the segments are chunky and hold that many interleaved samples
         per pixel, of which only `sample` is written (pbx_band_write_tiff_sample).
+        flags: a spec's `flags` (TIFF_F_J2K_PACKETS on JPEG 2000 segments).
         With timing=True returns the decoders' and the placement's device ms."""
         data, offsets = segments if isinstance(segments, tuple) else pack_chunks(segments)
         s = PbxTiffSegments()
         s.seg_w, s.seg_h, s.tiled = seg_w, seg_h, 1 if tiled else 0
-        s.compression, s.predictor, s.flags = compression, predictor, 0
+        s.compression, s.predictor, s.flags = compression, predictor, flags
         s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
         ms = (ctypes.c_double * 2)()
         if j2k:  # JPEG 2000 segments (compression TIFF_J2K): a spec's `j2k`
@@ -2288,7 +2310,8 @@ class PixelsService:
                                                      samples_per_pixel=tsp.get("samples_per_pixel", 1),
                                                      sample=tsp.get("sample", 0),
                                                      **({"jpeg": tsp["jpeg"]} if tsp.get("jpeg") is not None else {}),
-                                                     **({"j2k": True} if tsp.get("j2k") else {}))
+                                                     **({"j2k": True} if tsp.get("j2k") else {}),
+                                                     **({"flags": tsp["flags"]} if tsp.get("flags") else {}))
                             elif sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
@@ -2713,9 +2736,10 @@ class TiffSource(PixelSource):
     loaded, each from the strips or tile rows that cover it (band_segments -> load_bands ->
     band_write_tiff).  Either way every byte of pixel data is decoded on the GPU."""
 
-    def __init__(self, images: Mapping[int, str]):
+    def __init__(self, images: Mapping[int, str], j2k_packets: bool = True):
         import threading
         self.images = dict(images)
+        self.j2k_packets = j2k_packets  # JPEG 2000 IFDs: tiff_plane_spec's keyword of that name
         self._opened: Dict[int, dict] = {}
         self._lock = threading.Lock()
 
@@ -2723,7 +2747,7 @@ class TiffSource(PixelSource):
         with self._lock:
             lay = self._opened.get(image_id)
             if lay is None:
-                lay = self._opened[image_id] = tiff_image_layout(self.images[image_id])
+                lay = self._opened[image_id] = tiff_image_layout(self.images[image_id], self.j2k_packets)
             return lay
 
     def get_pixels(self, image_id: int) -> Optional[Pixels]:
@@ -2745,16 +2769,22 @@ class TiffSource(PixelSource):
         d = self._ifd(pixels, 0, 0, 0, level)[0]
         return d["width"], d["length"]
 
+    def _j2k_kw(self, ifd: dict) -> dict:
+        """(the keyword only for a JPEG 2000 IFD: every other file is the call it always was)"""
+        return {"j2k_packets": True} if self.j2k_packets and ifd["compression"] in _TIFF_J2K_COMPRESSIONS else {}
+
     def plane_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Optional[dict]:
         ifd, sample = self._ifd(pixels, z, c, t, level)
-        return tiff_plane_spec(self.images[pixels.image_id], ifd, pixels.image_id, z, c, t, level, sample=sample)
+        return tiff_plane_spec(self.images[pixels.image_id], ifd, pixels.image_id, z, c, t, level, sample=sample,
+                               **self._j2k_kw(ifd))
 
     def band_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
                       rows: int) -> Optional[dict]:
         ifd, sample = self._ifd(pixels, z, c, t, level)
         path = self.images[pixels.image_id]
         # (sample 0 -- every single-sample file -- is the call it always was)
-        return tiff_band_spec(path, ifd, y0, rows) if sample == 0 else tiff_band_spec(path, ifd, y0, rows, sample=sample)
+        kw = self._j2k_kw(ifd)
+        return tiff_band_spec(path, ifd, y0, rows, **kw) if sample == 0 else tiff_band_spec(path, ifd, y0, rows, sample=sample, **kw)
 
     def read_rows(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int,
                   rows: int) -> bytes:
