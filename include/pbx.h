@@ -388,7 +388,8 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * palette colour, sub-byte or 12-bit samples.  JPEG 2000, lossless (the reversible 5/3 path) and
  * lossy (the irreversible 9/7 path, "JPEG-2000 Lossy", Aperio's 33003 / 33005), goes through the
  * pbx_*_tiff_j2k calls further down and through no other; Aperio's habit of YCbCr components
- * outside the codestream is not undone (components are stored as decoded).
+ * outside the codestream is undone only where the caller says so (PBX_TIFF_F_J2K_YCBCR; without it
+ * components are stored as decoded).
  * JPEG (Compression 7, baseline, 8-bit, gray / RGB /
  * YCbCr) goes through the pbx_*_tiff_jpeg calls further down and through no other: old-style JPEG
  * (Compression 6), progressive, lossless, arithmetic-coded and 12-bit streams, YCbCr under any
@@ -404,6 +405,14 @@ enum pbx_tiff_compression { PBX_TIFF_JPEG = 7 /* through the pbx_*_tiff_jpeg cal
  * hooks and by no other call; without it those four refuse such streams by name, as they always
  * have. */
 #define PBX_TIFF_F_J2K_PACKETS 1
+/* J2K_SUBSAMPLED: three components of precision 8 whose second and third are stored at half width
+ * and / or half height (XRsiz x YRsiz 2 x 1, 1 x 2 or 2 x 2, the same for both; the first 1 x 1;
+ * no multiple-component transform).  J2K_YCBCR: the three components are Y, Cb and Cr with no
+ * colour transform declared in the codestream (Aperio's 33003, PhotometricInterpretation 6) and are
+ * converted to RGB.  Both are taken by the same four calls and by no other; bit 2 (value 2) is not
+ * assigned.  See the JPEG 2000 calls below. */
+#define PBX_TIFF_F_J2K_SUBSAMPLED 4
+#define PBX_TIFF_F_J2K_YCBCR 8
 typedef struct pbx_tiff_segments {
     int32_t seg_w, seg_h;       /* tiles: TileWidth x TileLength (edge tiles are full, padded);
                                    strips: ImageWidth x RowsPerStrip (the last strip holds only
@@ -553,9 +562,31 @@ int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * in several packets has them copied into one run first (k_tiff_j2k_gather).  Without the flag
  * those streams are refused by name: "N quality layers (1)", "more than one precinct in resolution
  * R", "SOP or EPH markers".  With it: "N quality layers (1 .. 64)", "too many packets", "too many
- * block contributions"; a missing EPH is device code 2.  Refused either way: more than one tile or
- * tile-part, code-block style bits, COC / QCC / POC / RGN / PPM / PPT / CRG, offsets, subsampling,
- * signed components, the JP2 wrapper.
+ * block contributions"; a missing EPH is device code 2.
+ * With PBX_TIFF_F_J2K_SUBSAMPLED (alone or with the other flags, on both paths) also streams of
+ * three components of precision 8 whose components 1 and 2 share the sampling factors 2 x 1, 1 x 2
+ * or 2 x 2 while component 0 is 1 x 1 and the multiple-component transform is 0.  Component c then
+ * measures ceil(W / XRsiz) x ceil(H / YRsiz); its resolutions, sub-bands, code blocks, precincts,
+ * scratch planes and inverse wavelet have that size, and the packet list's position loops (T.800
+ * B.12.1.3 - 5) step by XRsiz 2^(PPx + NL - r) and YRsiz 2^(PPy + NL - r).  Upsampling is
+ * replication: plane sample (x, y) of component c is component sample (x / XRsiz, y / YRsiz), as
+ * OpenJPEG, Pillow and OpenSlide do for JPEG 2000 -- T.800 places a component sample on the
+ * reference grid at multiples of XRsiz and YRsiz and defines no chroma siting; libjpeg's triangle
+ * filter ("fancy upsampling", which the JPEG calls above use) is not used here.  Without the flag
+ * such streams are refused as ever: "subsampled components (component C: X x Y)".  With it, by
+ * name: "subsampling on a stream of one component", "subsampled first component", "sampling
+ * factors X x Y on component C (2 x 1, 1 x 2 or 2 x 2)", "chroma components of different sampling
+ * factors", "subsampled components (X x Y) with the multiple-component transform".
+ * With PBX_TIFF_F_J2K_YCBCR the three components are converted to RGB after level shift, rounding
+ * and clamp to uint8, by libjpeg's jdcolor.c 16-bit fixed point (the arithmetic of the JPEG calls'
+ * ycbcr), with or without subsampling, on both paths; only the samples a call names are stored.
+ * It needs samples_per_pixel 3 on a PBX_UINT8 plane and streams without the multiple-component
+ * transform: "YCbCr conversion (PBX_TIFF_F_J2K_YCBCR) on ..." otherwise.  Segments with either
+ * flag's property are placed by k_tiff_j2k_place_chroma.
+ * Refused either way: more than one tile or
+ * tile-part, code-block style bits, COC / QCC / POC / RGN / PPM / PPT / CRG, offsets, sampling
+ * factors other than the three above, a subsampled first component, signed components, the JP2
+ * wrapper.
  * pbx_planes_register_tiff_samples for such layers: compression must be PBX_TIFF_J2K and
  * predictor 1 (the other TIFF calls keep answering "bad compression 34712").  Keys, all-or-none,
  * staging, statuses and kernel_ms ([0] decode through the inverse wavelet, [1] placement) are

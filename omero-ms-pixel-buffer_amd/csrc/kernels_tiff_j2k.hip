@@ -18,6 +18,8 @@
 //   k_tiff_j2k_idwt97   the inverse 9/7 lifting in float32, same geometry
 //   k_tiff_j2k_place    inverse RCT (9/7: ICT, rounding half to even), level shift, clamp, split
 //                       and placement, clipped as k_tiff_jpeg_place clips
+//   k_tiff_j2k_place_chroma  the same for segments whose second and third components are
+//                       subsampled (replicated) and / or YCbCr (converted after the clamp)
 //
 // The serial halves (tiff_j2k_dev.h) are run by lane 0 of their wave; the lanes together clear
 // the state before it and store the coefficients after it.  An arithmetic decoder has one chain of
@@ -331,6 +333,57 @@ __global__ __launch_bounds__(64 * J2P_WAVES) void k_tiff_j2k_place(const TJ2Seg*
     }
 }
 
+// Segments with J2_SEG_CHROMA bits: three components of precision 8 and no colour transform in
+// the stream (tiff_j2k_plan), components 1 and 2 at half width and / or half height in planes of
+// their own pitch, and / or YCbCr.  k_tiff_j2k_place's geometry and clipping; a lane reads Y at
+// (r, x) and chroma at (r / ys, x / xs) (j2k_chroma_at: replication), shifts, rounds and clamps
+// each as k_tiff_j2k_place does, converts with J2_SEG_YCC (j2k_ycc_rgb) and stores the wanted
+// samples.  IRR: float planes.  Neighbouring lanes share a chroma dword: the loads of a wave cover
+// half the lines the luma's do.
+template <bool IRR>
+__device__ __forceinline__ void j2_place_chroma(const TJ2Seg& u, const TSplitDst& d, const uint8_t* __restrict__ scratch,
+                                                int32_t r0, int32_t r1, uint32_t vis, uint32_t lane, uint32_t wv) {
+    const uint32_t* p0 = (const uint32_t*)(scratch + u.src[0]);
+    const uint32_t* p1 = (const uint32_t*)(scratch + u.src[1]);
+    const uint32_t* p2 = (const uint32_t*)(scratch + u.src[2]);
+    for (int32_t r = r0 + (int32_t)wv; r < r1; r += (int32_t)J2P_WAVES) {
+        for (uint32_t x = lane; x < vis; x += 64) {
+            const uint64_t ac = j2k_chroma_at(1, x, (uint32_t)r, u.w, u.rct);
+            const uint32_t raw[3] = {p0[(uint64_t)r * u.w + x], p1[ac], p2[ac]};
+            uint32_t v[3];
+#pragma unroll
+            for (uint32_t c = 0; c < 3; c++) v[c] = IRR ? j2f_sample(__uint_as_float(raw[c]), 8) : j2_sample((int32_t)raw[c], 8);
+            if (u.rct & J2_SEG_YCC) j2k_ycc_rgb(v);
+#pragma unroll
+            for (uint32_t c = 0; c < 3; c++) {
+                if (!d.dev[c]) continue;
+                d.dev[c][(int64_t)(u.y0 + r) * d.pitch + (int64_t)u.x0 + x] = (uint8_t)v[c];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * J2P_WAVES) void k_tiff_j2k_place_chroma(const TJ2Seg* __restrict__ sg,
+                                                                          const TSplitDst* __restrict__ dt,
+                                                                          const uint8_t* __restrict__ scratch) {
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const TJ2Seg u = sg[blockIdx.x];
+    const TSplitDst d = dt[u.dst];
+    // (the host checked: three components of precision 8, no colour transform, a uint8 plane)
+    if (d.bpp != 1 || u.ncomp != 3 || u.prec != 8 || (u.rct & 1)) return;
+    const int32_t x0 = u.x0, y0 = u.y0, rows = (int32_t)u.rows;
+    int32_t r0 = (int32_t)(blockIdx.y * J2P_ROWS), r1 = r0 + (int32_t)J2P_ROWS;
+    const int32_t top = d.y_lo > 0 ? d.y_lo : 0, bottom = d.y_hi < d.sy ? d.y_hi : d.sy;
+    r1 = r1 < rows ? r1 : rows;
+    r0 = r0 > top - y0 ? r0 : top - y0;
+    r1 = r1 < bottom - y0 ? r1 : bottom - y0;
+    if (r0 >= r1 || x0 >= d.sx || x0 < 0 || y0 < 0) return;
+    const uint32_t wvis = (uint32_t)(d.sx - x0);
+    const uint32_t vis = wvis < u.w ? wvis : u.w;
+    if (u.rct & J2_SEG_IRREV) j2_place_chroma<true>(u, d, scratch, r0, r1, vis, lane, wv);
+    else j2_place_chroma<false>(u, d, scratch, r0, r1, vis, lane, wv);
+}
+
 // meta (zeroed by the caller): a J2Code and a J2Walk per block, n_con J2Contrib, the tag-tree nodes
 hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uint32_t n_streams,
                                   const J2Packet* d_packets, const J2Band* d_bands, const J2Block* d_blocks,
@@ -359,11 +412,16 @@ hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uin
     return hipGetLastError();
 }
 
-hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t max_rows,
+// d_segs: n segments, the n - n_chroma without J2_SEG_CHROMA bits first
+hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t n_chroma, uint32_t max_rows,
                                  const TSplitDst* d_dst, const uint8_t* scratch) {
-    if (!n || !max_rows) return hipSuccess;
-    hipLaunchKernelGGL(k_tiff_j2k_place, dim3(n, (max_rows + J2P_ROWS - 1) / J2P_ROWS), dim3(64 * J2P_WAVES), 0, st,
-                       d_segs, d_dst, scratch);
+    if (!n || !max_rows || n_chroma > n) return hipSuccess;
+    const uint32_t gy = (max_rows + J2P_ROWS - 1) / J2P_ROWS;
+    if (n > n_chroma)
+        hipLaunchKernelGGL(k_tiff_j2k_place, dim3(n - n_chroma, gy), dim3(64 * J2P_WAVES), 0, st, d_segs, d_dst, scratch);
+    if (n_chroma)
+        hipLaunchKernelGGL(k_tiff_j2k_place_chroma, dim3(n_chroma, gy), dim3(64 * J2P_WAVES), 0, st, d_segs + (n - n_chroma),
+                           d_dst, scratch);
     return hipGetLastError();
 }
 

@@ -244,17 +244,21 @@ struct J2Contrib {
 static_assert(sizeof(J2Contrib) == 16, "J2Contrib is a device table");
 struct J2Comp {            // one component of one stream, for the inverse wavelet
     uint64_t a, b;         // its planes in scratch
-    uint32_t w, h, levels;
+    uint32_t w, h, levels; // its own size: ceil(W / XRsiz) x ceil(H / YRsiz) of a subsampled one
     uint32_t irrev;        // 1: float planes, k_tiff_j2k_idwt97's; 0: int32 planes, k_tiff_j2k_idwt's
 };
 static_assert(sizeof(J2Comp) == 32, "J2Comp is uploaded as is");
 struct TJ2Seg {            // one stream, for the placement
-    uint64_t src[3];       // its components' planes A
+    uint64_t src[3];       // its components' planes A (1 and 2 of a subsampled stream: pitch ceil(w / 2)
+                           // with J2_SEG_XS2, ceil(rows / 2) rows with J2_SEG_YS2)
     uint32_t w, rows;      // the segment's own size in pixels (the SIZ's)
     int32_t x0, y0;        // its origin in the plane
     uint32_t ncomp;        // 1 or 3
     uint32_t rct;          // bit 0: inverse colour transform (RCT, or ICT on float planes);
-                           // bit 1 (J2_SEG_IRREV): float planes of an irreversible stream
+                           // bit 1 (J2_SEG_IRREV): float planes of an irreversible stream;
+                           // J2_SEG_YCC: YCbCr -> RGB after the clamp; J2_SEG_XS2 / J2_SEG_YS2:
+                           // components 1 and 2 at half width / half height.  Any of the last
+                           // three: k_tiff_j2k_place_chroma's segment, not k_tiff_j2k_place's
     uint32_t prec;         // 8 or 16
     uint32_t dst;          // its entry in the launch's TSplitDst table
 };
@@ -263,6 +267,7 @@ static_assert(sizeof(TJ2Seg) == 56, "TJ2Seg is uploaded as is");
 // header (a length of more than 32 bits), 3 zero bit-planes above Mb or more passes than the
 // bit-planes allow.
 enum : uint32_t { J2E_END = 1, J2E_HEADER = 2, J2E_PLANES = 3 };
-constexpr uint32_t J2_SEG_IRREV = 2;
+constexpr uint32_t J2_SEG_IRREV = 2, J2_SEG_YCC = 4, J2_SEG_XS2 = 0x100, J2_SEG_YS2 = 0x200;
+constexpr uint32_t J2_SEG_CHROMA = J2_SEG_YCC | J2_SEG_XS2 | J2_SEG_YS2;
 
 }  // namespace pbx

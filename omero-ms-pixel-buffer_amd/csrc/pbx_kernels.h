@@ -174,7 +174,9 @@ hipError_t launch_tiff_j2k_decode(hipStream_t st, const J2Stream* d_streams, uin
                                   uint32_t n_blocks, uint32_t n_con, const J2Comp* d_comps, uint32_t n_comps,
                                   uint32_t n_irrev, uint32_t max_coef, uint32_t max_flag, uint8_t* meta,
                                   const uint8_t* src, uint8_t* scratch, uint32_t* err);
-hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t max_rows,
+// d_segs: the n - n_chroma segments of k_tiff_j2k_place, then the n_chroma ones with J2_SEG_CHROMA
+// bits (subsampled or YCbCr components) of k_tiff_j2k_place_chroma
+hipError_t launch_tiff_j2k_place(hipStream_t st, const TJ2Seg* d_segs, uint32_t n, uint32_t n_chroma, uint32_t max_rows,
                                  const TSplitDst* d_dst, const uint8_t* scratch);
 
 }  // namespace pbx

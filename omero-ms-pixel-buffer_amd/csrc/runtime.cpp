@@ -2336,7 +2336,9 @@ struct ZarrInput {
 // k_tiff_jpeg_decode after the other decoders, their err[] entries after the checks', and
 // P.jsegs upsampled, converted and placed into the planes of `sd` by k_tiff_jpeg_place.
 // P.j2streams (JPEG 2000 TIFF segments) go through k_tiff_j2k_packets, _gather, _blocks and _idwt after
-// those, their err[] entries last, and P.j2segs are placed by k_tiff_j2k_place.
+// those, their err[] entries last, and P.j2segs are placed by k_tiff_j2k_place, those with
+// subsampled or YCbCr components (J2_SEG_CHROMA; uploaded after the others) by
+// k_tiff_j2k_place_chroma.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms,
                       const std::vector<TSplitDst>* sd = nullptr) {
@@ -2363,6 +2365,10 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     const uint32_t nchecks = (uint32_t)checks.size(), njpeg = (uint32_t)P.jstreams.size();
     const uint32_t nj2 = (uint32_t)P.j2streams.size();
     const uint32_t nerr = nstreams + nchecks + njpeg + nj2;  // err[]: streams, checks, JPEG, JPEG 2000 streams
+    std::vector<TJ2Seg> j2segs = P.j2segs;
+    const uint32_t j2chroma = (uint32_t)(j2segs.end() - std::stable_partition(j2segs.begin(), j2segs.end(), [](const TJ2Seg& u) {
+                                             return !(u.rct & J2_SEG_CHROMA);
+                                         }));
     const uint64_t j2meta = (sizeof(J2Code) + sizeof(J2Walk)) * P.j2blocks.size() + sizeof(J2Contrib) * P.j2cons + 4 * P.j2nodes;
     uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
     ZStream* d_st = nullptr;
@@ -2487,7 +2493,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess && d_2c)
         e = hipMemcpyAsync(d_2c, P.j2comps.data(), sizeof(J2Comp) * P.j2comps.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_2p)
-        e = hipMemcpyAsync(d_2p, P.j2segs.data(), sizeof(TJ2Seg) * P.j2segs.size(), hipMemcpyHostToDevice, st);
+        e = hipMemcpyAsync(d_2p, j2segs.data(), sizeof(TJ2Seg) * j2segs.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && d_2m) e = hipMemsetAsync(d_2m, 0, std::max<uint64_t>(j2meta, 256), st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
     if (e == hipSuccess) e = hipEventRecord(ev[0], st);
@@ -2525,7 +2531,7 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     if (e == hipSuccess && d_jp)
         e = launch_tiff_jpeg_place(st, d_jp, (uint32_t)P.jsegs.size(), P.jseg_rows, d_sd, d_scr);
     if (e == hipSuccess && d_2p)
-        e = launch_tiff_j2k_place(st, d_2p, (uint32_t)P.j2segs.size(), P.j2seg_rows, d_sd, d_scr);
+        e = launch_tiff_j2k_place(st, d_2p, (uint32_t)j2segs.size(), j2chroma, P.j2seg_rows, d_sd, d_scr);
     if (e == hipSuccess) e = hipEventRecord(ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     std::vector<uint32_t> err(nerr + 1, 0);

@@ -748,12 +748,15 @@ int tiff_jpeg_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, c
 // layer, one precinct per resolution, code-block style 0; everything else is refused by name.
 // With PBX_TIFF_F_J2K_PACKETS (`packets` below) also 1 .. 64 quality layers, any precinct sizes and
 // SOP / EPH markers: tiff_j2k_plan writes the stream's packets down as a list (T.800 B.12).
+// With PBX_TIFF_F_J2K_SUBSAMPLED (`subsampled` below) also three components whose second and third
+// share the sampling factors 2 x 1, 1 x 2 or 2 x 2 (the first 1 x 1, no colour transform).
 namespace {
 
 struct J2kHeader {
     uint32_t w = 0, h = 0, ncomp = 0, prec = 0;
     uint32_t prog = 0, mct = 0, levels = 0, xcb = 0, ycb = 0, guard = 0;
     uint32_t layers = 1, scod = 0;
+    uint32_t xr = 1, yr = 1;  // XRsiz, YRsiz of components 1 and 2 (component 0: 1 x 1)
     bool precincts = false;
     uint8_t pp[33];     // PPx | PPy << 4 per resolution
     uint8_t exps[97];   // per sub-band, QCD order
@@ -762,7 +765,7 @@ struct J2kHeader {
     uint64_t data = 0, end = 0;  // the packets
 };
 
-int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* what, bool packets) {
+int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* what, bool packets, bool subsampled) {
     static const uint8_t jp2[12] = {0, 0, 0, 12, 'j', 'P', ' ', ' ', 13, 10, 0x87, 10};
     if (len >= 12 && !memcmp(f, jp2, 12)) return fail(PBX_E_BADARG, "%s: jp2 box, not a codestream", what);
     if (len < 2 || f[0] != 0xFF || f[1] != 0x4F) return fail(PBX_E_BADARG, "%s does not start with SOC (JPEG 2000 codestream)", what);
@@ -801,7 +804,18 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
             if (nc != 1 && nc != 3) return fail(PBX_E_BADARG, "%s: %u components (1 or 3)", what, nc);
             for (uint32_t c = 0; c < nc; c++) {
                 const uint32_t ssiz = p[36 + 3 * c], xr = p[37 + 3 * c], yr = p[38 + 3 * c];
-                if (xr != 1 || yr != 1) return fail(PBX_E_BADARG, "%s: subsampled components (component %u: %u x %u)", what, c, xr, yr);
+                if ((xr != 1 || yr != 1) && !subsampled)
+                    return fail(PBX_E_BADARG, "%s: subsampled components (component %u: %u x %u)", what, c, xr, yr);
+                if (xr != 1 || yr != 1) {
+                    if (nc == 1) return fail(PBX_E_BADARG, "%s: subsampling on a stream of one component (%u x %u)", what, xr, yr);
+                    if (c == 0) return fail(PBX_E_BADARG, "%s: subsampled first component (%u x %u)", what, xr, yr);
+                    if (xr > 2 || yr > 2 || !xr || !yr)
+                        return fail(PBX_E_BADARG, "%s: sampling factors %u x %u on component %u (2 x 1, 1 x 2 or 2 x 2)", what, xr, yr, c);
+                }
+                if (c == 2 && (xr != H.xr || yr != H.yr))
+                    return fail(PBX_E_BADARG, "%s: chroma components of different sampling factors (%u x %u and %u x %u)", what,
+                                H.xr, H.yr, xr, yr);
+                if (c == 1) { H.xr = xr; H.yr = yr; }
                 if (ssiz & 0x80) return fail(PBX_E_BADARG, "%s: signed components", what);
                 if (c && ssiz + 1 != H.prec) return fail(PBX_E_BADARG, "%s: components of different precisions", what);
                 H.prec = ssiz + 1;
@@ -890,6 +904,8 @@ int j2k_parse_header(const uint8_t* f, uint64_t len, J2kHeader& H, const char* w
     if (nexp != nb)
         return fail(PBX_E_BADARG, "%s: QCD of %u sub-bands for %u decomposition levels", what, nexp, H.levels);
     if (H.mct && H.ncomp != 3) return fail(PBX_E_BADARG, "%s: multiple-component transform on %u component(s)", what, H.ncomp);
+    if (H.mct && (H.xr != 1 || H.yr != 1))
+        return fail(PBX_E_BADARG, "%s: subsampled components (%u x %u) with the multiple-component transform", what, H.xr, H.yr);
     if (H.irrev) {
         // T.800 E.1.1: step = 2^(R_b - eps_b) (1 + mu_b / 2^11), R_b the precision plus the band's
         // gain (0 LL, 1 HL and LH, 2 HH); style 1 derives every band from the LL entry (E-5):
@@ -945,10 +961,14 @@ int tiff_j2k_check(const pbx_tiff_segments* s, int32_t pixel_type, int32_t spp) 
                     s->seg_w, s->seg_h);
     if (s->compression != PBX_TIFF_J2K) return fail(PBX_E_BADARG, "bad compression %d (the JPEG 2000 calls take 34712)", s->compression);
     if (s->predictor != 1) return fail(PBX_E_BADARG, "bad predictor %d on JPEG 2000 segments (1 only)", s->predictor);
-    if (s->flags & ~PBX_TIFF_F_J2K_PACKETS) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
+    if (s->flags & ~(PBX_TIFF_F_J2K_PACKETS | PBX_TIFF_F_J2K_SUBSAMPLED | PBX_TIFF_F_J2K_YCBCR))
+        return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
     if (pixel_type != PBX_UINT8 && pixel_type != PBX_UINT16)
         return fail(PBX_E_BADARG, "JPEG 2000 segments on a plane that is neither uint8 nor uint16");
     if (spp != 1 && spp != 3) return fail(PBX_E_BADARG, "JPEG 2000 segments of %d samples per pixel (1 or 3)", spp);
+    if ((s->flags & PBX_TIFF_F_J2K_YCBCR) && (spp != 3 || pixel_type != PBX_UINT8))
+        return fail(PBX_E_BADARG, "YCbCr conversion (PBX_TIFF_F_J2K_YCBCR) on JPEG 2000 segments of %d sample(s) per pixel of %d bits "
+                    "(3 of 8)", spp, 8 * bpp_of(pixel_type));
     return PBX_OK;
 }
 
@@ -979,33 +999,45 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
         char what[48];
         snprintf(what, sizeof what, "segment %lld", (long long)i);
         J2kHeader H;
-        if (int rc = j2k_parse_header(s->data + o, len, H, what, s->flags & PBX_TIFF_F_J2K_PACKETS)) return rc;
+        if (int rc = j2k_parse_header(s->data + o, len, H, what, s->flags & PBX_TIFF_F_J2K_PACKETS,
+                                      s->flags & PBX_TIFF_F_J2K_SUBSAMPLED))
+            return rc;
         if ((int64_t)H.w != s->seg_w || (int64_t)H.h != rows)
             return fail(PBX_E_BADARG, "%s: SIZ size %u x %u != segment size %d x %d", what, H.w, H.h, s->seg_w, rows);
         if ((int)H.ncomp != spp)
             return fail(PBX_E_BADARG, "%s: a stream of %u components in segments of %d samples per pixel", what, H.ncomp, spp);
         if ((int)H.prec != 8 * bpp)
             return fail(PBX_E_BADARG, "%s: precision %u on a plane of %d-bit samples", what, H.prec, 8 * bpp);
-        const uint64_t plane = ((uint64_t)H.w * H.h * 4 + 255) & ~255ull;
-        if (plane > 0x7fffffffull) return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
+        const bool ycc = s->flags & PBX_TIFF_F_J2K_YCBCR;
+        if (ycc && H.mct)
+            return fail(PBX_E_BADARG, "%s: YCbCr conversion (PBX_TIFF_F_J2K_YCBCR) on a stream with the multiple-component transform", what);
+        if ((uint64_t)H.w * H.h * 4 + 255 > 0x7fffffffull) return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
         const uint32_t NL = H.levels, stream = (uint32_t)P.j2streams.size();
         auto res = [&](uint32_t v, uint32_t r) { return (uint32_t)(((uint64_t)v + (1ull << (NL - r)) - 1) >> (NL - r)); };
-        TJ2Seg seg{{0, 0, 0}, H.w, H.h, x0, y0, H.ncomp, H.mct | (H.irrev ? J2_SEG_IRREV : 0u), H.prec, dst};
+        // component c's own size: ceil(W / XRsiz) x ceil(H / YRsiz) (no offsets), 1 x 1 for component 0
+        auto cwid = [&](uint32_t c) { return c ? (H.w + H.xr - 1) / H.xr : H.w; };
+        auto chei = [&](uint32_t c) { return c ? (H.h + H.yr - 1) / H.yr : H.h; };
+        TJ2Seg seg{{0, 0, 0}, H.w, H.h, x0, y0, H.ncomp,
+                   H.mct | (H.irrev ? J2_SEG_IRREV : 0u) | (ycc ? J2_SEG_YCC : 0u) | (H.xr == 2 ? J2_SEG_XS2 : 0u) |
+                       (H.yr == 2 ? J2_SEG_YS2 : 0u),
+                   H.prec, dst};
         const uint32_t band0 = (uint32_t)P.j2bands.size(), blk0 = (uint32_t)P.j2blocks.size();
         struct Cell {  // a sub-band's code-block size and grid
             uint32_t xcb, ycb, nbx, nby;
         };
         std::vector<Cell> cells;
         for (uint32_t c = 0; c < H.ncomp; c++) {
+            const uint32_t W = cwid(c), Hc = chei(c);
+            const uint64_t plane = ((uint64_t)W * Hc * 4 + 255) & ~255ull;
             const uint64_t a = P.scratch;
             P.scratch += 2 * plane;
             seg.src[c] = a;
-            P.j2comps.push_back(J2Comp{a, a + plane, H.w, H.h, NL, H.irrev ? 1u : 0u});
+            P.j2comps.push_back(J2Comp{a, a + plane, W, Hc, NL, H.irrev ? 1u : 0u});
             P.j2irrev += H.irrev ? 1 : 0;
             for (uint32_t b = 0; b < 3 * NL + 1; b++) {
                 const uint32_t r = b ? (b + 2) / 3 : 0, orient = b ? (b - 1) % 3 + 1 : 0;
-                const uint32_t cw = res(H.w, r), ch = res(H.h, r);
-                const uint32_t lw = r ? res(H.w, r - 1) : 0, lh = r ? res(H.h, r - 1) : 0;
+                const uint32_t cw = res(W, r), ch = res(Hc, r);
+                const uint32_t lw = r ? res(W, r - 1) : 0, lh = r ? res(Hc, r - 1) : 0;
                 const uint32_t bx0 = orient & 1 ? lw : 0, by0 = orient & 2 ? lh : 0;
                 const uint32_t bw = !r ? cw : orient & 1 ? cw - lw : lw, bh = !r ? ch : orient & 2 ? ch - lh : lh;
                 const uint32_t ppx = H.pp[r] & 15, ppy = H.pp[r] >> 4;
@@ -1022,7 +1054,7 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
                     for (uint32_t bx = 0; bx < nbx; bx++) {
                         const uint32_t ox = bx << xcb, oy = by << ycb;
                         const uint32_t w = std::min(1u << xcb, bw - ox), h = std::min(1u << ycb, bh - oy);
-                        P.j2blocks.push_back(J2Block{a + 4 * ((uint64_t)(by0 + oy) * H.w + bx0 + ox), H.w, (uint16_t)w, (uint16_t)h,
+                        P.j2blocks.push_back(J2Block{a + 4 * ((uint64_t)(by0 + oy) * W + bx0 + ox), W, (uint16_t)w, (uint16_t)h,
                                                      stream, (uint8_t)orient, (uint8_t)(gexp ? gexp - 1 : 0), (uint16_t)(H.irrev ? 1 : 0), hstep, 0});
                         P.j2coef = std::max(P.j2coef, w * h);
                         P.j2flag = std::max(P.j2flag, (w + 2) * (h + 2));
@@ -1031,8 +1063,11 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
         }
         // The precincts (B.6) of every component and resolution, each with its windows into the
         // resolution's bands and their tag trees, and the key the progression order sorts it by.
-        // With no offsets and no subsampling the position loops of B.12.1.3 - 5 visit a precinct
-        // when they reach its origin on the reference grid.
+        // With no offsets the position loops of B.12.1.3 - 5, which step and test with
+        // XRsiz 2^(PPx + NL - r) and YRsiz 2^(PPy + NL - r), visit a precinct when they reach its
+        // origin on the reference grid: precinct (px, py) of a component subsampled XRsiz x YRsiz
+        // lies at (px XRsiz 2^(PPx + NL - r), py YRsiz 2^(PPy + NL - r)), inside the tile because
+        // px 2^PPx < ceil(W / (XRsiz 2^(NL - r))) means px 2^PPx XRsiz 2^(NL - r) < W.
         struct Prec {
             uint64_t yo, xo;  // its origin on the reference grid
             uint32_t c, r;
@@ -1043,14 +1078,15 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
         for (uint32_t c = 0; c < H.ncomp; c++)
             for (uint32_t r = 0; r <= NL; r++) {
                 const uint32_t ppx = H.pp[r] & 15, ppy = H.pp[r] >> 4;
-                const uint64_t npx = ((uint64_t)res(H.w, r) + (1ull << ppx) - 1) >> ppx;
-                const uint64_t npy = ((uint64_t)res(H.h, r) + (1ull << ppy) - 1) >> ppy;
+                const uint64_t npx = ((uint64_t)res(cwid(c), r) + (1ull << ppx) - 1) >> ppx;
+                const uint64_t npy = ((uint64_t)res(chei(c), r) + (1ull << ppy) - 1) >> ppy;
+                const uint64_t xr = c ? H.xr : 1, yr = c ? H.yr : 1;
                 if (precs.size() + npx * npy > 0xfffffull)
                     return fail(PBX_E_BADARG, "segment %lld: too many packets", (long long)i);
                 const uint32_t fb = r ? 3 * r - 2 : 0, nb = r ? 3 : 1;
                 for (uint64_t py = 0; py < npy; py++)
                     for (uint64_t px = 0; px < npx; px++) {
-                        Prec q{py << (ppy + NL - r), px << (ppx + NL - r), c, r, J2Packet{band0 + c * nbands + fb, 0, (uint16_t)nb, {}}};
+                        Prec q{(py << (ppy + NL - r)) * yr, (px << (ppx + NL - r)) * xr, c, r, J2Packet{band0 + c * nbands + fb, 0, (uint16_t)nb, {}}};
                         for (uint32_t k = 0; k < nb; k++) {
                             const Cell& g = cells[c * nbands + fb + k];
                             // the precinct's part of the band holds 2^(pb - cb) cells a side
@@ -1215,7 +1251,9 @@ int pbx_test_tiff_j2k_plan(const pbx_tiff_segments* s, int32_t size_x, int32_t s
 // block, each block's state in heap blocks of exactly the sizes k_tiff_j2k_blocks has in LDS),
 // the inverse 5/3 lifting, the inverse RCT, level shift and clamp; for an irreversible stream the
 // same float32 functions the kernels call (tiff_j2k_dev.h: dequantisation, the 9/7 lifting, the
-// ICT and the rounding), in the kernels' order, so that the two agree bit for bit.  out: samples_per_pixel planes
+// ICT and the rounding), in the kernels' order, so that the two agree bit for bit.  Subsampled
+// components are replicated and YCbCr ones converted by tiff_j2k_dev.h's j2k_chroma_at and
+// j2k_ycc_rgb, k_tiff_j2k_place_chroma's too.  out: samples_per_pixel planes
 // of size_x * size_y samples, uint8 or host-order uint16, no pitch.
 int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t pixel_type,
                              int32_t samples_per_pixel, void* out, uint64_t out_bytes) {
@@ -1300,23 +1338,32 @@ int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* s, int32_t size_x, int32_t
             for (uint32_t x = 0; x < u.w && (int64_t)u.x0 + x < size_x; x++) {
                 if (u.rct & J2_SEG_IRREV) {  // inverse ICT, level shift, round half to even, clamp
                     float fv[3] = {0, 0, 0};
-                    for (uint32_t c = 0; c < u.ncomp; c++) memcpy(&fv[c], &scr[u.src[c] / 4 + (uint64_t)y * u.w + x], 4);
+                    for (uint32_t c = 0; c < u.ncomp; c++) memcpy(&fv[c], &scr[u.src[c] / 4 + j2k_chroma_at(c, x, y, u.w, u.rct)], 4);
                     if (u.ncomp == 3 && (u.rct & 1)) j2f_ict(fv);
+                    uint32_t tv[3] = {0, 0, 0};
+                    for (uint32_t c = 0; c < u.ncomp; c++) tv[c] = j2f_sample(fv[c], u.prec);
+                    if (u.ncomp == 3 && (u.rct & J2_SEG_YCC)) j2k_ycc_rgb(tv);
                     for (uint32_t c = 0; c < u.ncomp; c++) {
-                        const uint32_t t = j2f_sample(fv[c], u.prec);
+                        const uint32_t t = tv[c];
                         const uint64_t at = (uint64_t)c * size_x * size_y + (uint64_t)(u.y0 + y) * size_x + u.x0 + x;
                         if (bpp == 1) ((uint8_t*)out)[at] = (uint8_t)t; else ((uint16_t*)out)[at] = (uint16_t)t;
                     }
                     continue;
                 }
                 int64_t v[3] = {0, 0, 0};
-                for (uint32_t c = 0; c < u.ncomp; c++) v[c] = scr[u.src[c] / 4 + (uint64_t)y * u.w + x];
+                for (uint32_t c = 0; c < u.ncomp; c++) v[c] = scr[u.src[c] / 4 + j2k_chroma_at(c, x, y, u.w, u.rct)];
                 if (u.ncomp == 3 && (u.rct & 1)) {
                     const int64_t g = v[0] - ((v[1] + v[2]) >> 2), rr = v[2] + g, bb = v[1] + g;
                     v[0] = rr; v[1] = g; v[2] = bb;
                 }
+                uint32_t tv[3] = {0, 0, 0};
                 for (uint32_t c = 0; c < u.ncomp; c++) {
-                    const int64_t hi = (1ll << u.prec) - 1, t = std::min(hi, std::max<int64_t>(0, v[c] + (1ll << (u.prec - 1))));
+                    const int64_t hi = (1ll << u.prec) - 1;
+                    tv[c] = (uint32_t)std::min(hi, std::max<int64_t>(0, v[c] + (1ll << (u.prec - 1))));
+                }
+                if (u.ncomp == 3 && (u.rct & J2_SEG_YCC)) j2k_ycc_rgb(tv);
+                for (uint32_t c = 0; c < u.ncomp; c++) {
+                    const uint32_t t = tv[c];
                     const uint64_t at = (uint64_t)c * size_x * size_y + (uint64_t)(u.y0 + y) * size_x + u.x0 + x;
                     if (bpp == 1) ((uint8_t*)out)[at] = (uint8_t)t; else ((uint16_t*)out)[at] = (uint16_t)t;
                 }

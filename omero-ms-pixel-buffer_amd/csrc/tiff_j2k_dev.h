@@ -516,4 +516,28 @@ inline void j2f_sr97(float* x, int64_t n, int64_t st) {
         for (int64_t i = k & 1; i < n; i += 2) x[i * st] = j2f_lift(x[i * st], j2f_at(x, n, st, i - 1), j2f_at(x, n, st, i + 1), c[k]);
 }
 
+// ------------------------------------------------------- subsampled and YCbCr components
+// The placement of a segment with J2_SEG_CHROMA bits (k_tiff_j2k_place_chroma and the CPU hook).
+// Upsampling is replication: plane sample (x, y) of component 1 or 2 is component sample
+// (x / XRsiz, y / YRsiz) -- T.800 puts a component sample on the reference grid at multiples of
+// XRsiz and YRsiz and defines no chroma siting.  Where component c's sample of pixel (x, y) of a
+// segment w pixels wide lies in its plane, in samples:
+PBX_J2K_FN uint64_t j2k_chroma_at(uint32_t c, uint32_t x, uint32_t y, uint32_t w, uint32_t rct) {
+    const uint32_t xs = c && (rct & J2_SEG_XS2) ? 1u : 0u, ys = c && (rct & J2_SEG_YS2) ? 1u : 0u;
+    const uint32_t pitch = (w + xs) >> xs;
+    return (uint64_t)(y >> ys) * pitch + (x >> xs);
+}
+
+// YCbCr -> RGB on clamped 8-bit samples, in place: libjpeg's jdcolor.c 16-bit fixed point, the
+// arithmetic of k_tiff_jpeg_place
+PBX_J2K_FN void j2k_ycc_rgb(uint32_t v[3]) {
+    const int32_t y = (int32_t)v[0], u = (int32_t)v[1] - 128, w = (int32_t)v[2] - 128;
+    const int32_t r = y + ((91881 * w + 32768) >> 16);
+    const int32_t g = y + ((-22554 * u - 46802 * w + 32768) >> 16);
+    const int32_t b = y + ((116130 * u + 32768) >> 16);
+    v[0] = (uint32_t)(r < 0 ? 0 : r > 255 ? 255 : r);
+    v[1] = (uint32_t)(g < 0 ? 0 : g > 255 ? 255 : g);
+    v[2] = (uint32_t)(b < 0 ? 0 : b > 255 ? 255 : b);
+}
+
 }  // namespace pbx

@@ -799,6 +799,8 @@ TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
 TIFF_ZSTD = 50000
 TIFF_JPEG = 7  # through the pbx_*_tiff_jpeg calls only
 TIFF_F_J2K_PACKETS = 1  # pbx_tiff_segments.flags: JPEG 2000 layers, precincts, SOP / EPH (the pbx_*_tiff_j2k calls only)
+TIFF_F_J2K_SUBSAMPLED = 4  # components 1 and 2 at half width and / or half height (the same calls only)
+TIFF_F_J2K_YCBCR = 8  # YCbCr components outside the codestream: converted to RGB (the same calls only)
 TIFF_J2K = 34712  # through the pbx_*_tiff_j2k calls only; what every Compression value below hands over as
 _TIFF_J2K_COMPRESSIONS = (33003, 33004, 33005, 34712)  # Bio-Formats' TiffCompression: JPEG-2000 / Lossy, Aperio's two
 _TIFF_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4,
@@ -1151,13 +1153,16 @@ def j2k_steps(h: dict) -> list:
     return out
 
 
-def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int, packets: bool = False) -> None:
+def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int, packets: bool = False,
+                            chroma: bool = False, ycbcr: bool = False) -> bool:
     """What the first segment's header shows of a JPEG 2000 IFD this library cannot load: PbxError
     400 with the reason, in the C-ABI's words (which checks every segment again).  `packets`: the
     caller hands the segments over with TIFF_F_J2K_PACKETS, which takes 1 .. 64 quality layers, any
-    precinct sizes and SOP / EPH markers."""
+    precinct sizes and SOP / EPH markers.  `chroma`: with TIFF_F_J2K_SUBSAMPLED where the stream
+    needs it, which takes three components whose second and third are 2 x 1, 1 x 2 or 2 x 2; the
+    answer is whether it does.  `ycbcr`: with TIFF_F_J2K_YCBCR."""
     if not ifd["offsets"]:
-        return
+        return False
     with open(path, "rb") as f:
         f.seek(ifd["offsets"][0])
         data = f.read(ifd["counts"][0])
@@ -1181,8 +1186,17 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int, packets: 
     if len(comps) not in (1, 3):
         no("%d components (1 or 3)" % len(comps))
     for c, (prec, signed, xr, yr) in enumerate(comps):
-        if (xr, yr) != (1, 1):
+        if (xr, yr) != (1, 1) and not chroma:
             no("subsampled components (component %d: %d x %d)" % (c, xr, yr))
+        if (xr, yr) != (1, 1):
+            if len(comps) == 1:
+                no("subsampling on a stream of one component (%d x %d)" % (xr, yr))
+            if c == 0:
+                no("subsampled first component (%d x %d)" % (xr, yr))
+            if (xr, yr) not in ((2, 1), (1, 2), (2, 2)):
+                no("sampling factors %d x %d on component %d (2 x 1, 1 x 2 or 2 x 2)" % (xr, yr, c))
+        if c == 2 and (xr, yr) != comps[1][2:]:
+            no("chroma components of different sampling factors (%d x %d and %d x %d)" % (comps[1][2:] + (xr, yr)))
         if signed:
             no("signed components")
         if prec != comps[0][0]:
@@ -1230,6 +1244,9 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int, packets: 
         no("QCD of %d sub-bands for %d decomposition levels" % (nexp, h["levels"]))
     if h["mct"] > 1 or (h["mct"] and len(comps) != 3):
         no("multiple-component transform on %d component(s)" % len(comps))
+    sub = len(comps) == 3 and comps[1][2:] != (1, 1)
+    if h["mct"] and sub:
+        no("subsampled components (%d x %d) with the multiple-component transform" % comps[1][2:])
     if irrev:
         for b, (eps, _) in enumerate(j2k_steps(h)):
             if eps < 0:
@@ -1262,22 +1279,32 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int, packets: 
         no("a stream of %d components in segments of %d samples per pixel" % (len(comps), spp))
     if prec != bits:
         no("precision %d on a plane of %d-bit samples" % (prec, bits))
+    if ycbcr and h["mct"]:
+        no("YCbCr conversion (PBX_TIFF_F_J2K_YCBCR) on a stream with the multiple-component transform")
+    return sub
 
 
-def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False) -> int:
+def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False, j2k_chroma: bool = False,
+                     aperio_ycbcr: bool = False, j2k_flags: Optional[list] = None) -> int:
     """The pixel type of an IFD this library can load, else PbxError 400 with the reason.
     SamplesPerPixel 1 to 4: every sample is a channel of that type, ExtraSamples included.
     For a Compression-7 IFD, and for a JPEG 2000 one (Compression 33003 / 33004 / 33005 / 34712),
     the first segment is read and its header checked too, by every caller (a band spec of no
-    rows included: its refusals are tiff_plane_spec's).  j2k_packets: as tiff_plane_spec's."""
+    rows included: its refusals are tiff_plane_spec's).  j2k_packets, j2k_chroma, aperio_ycbcr: as
+    tiff_plane_spec's; j2k_flags, a list, receives the TIFF_F_J2K_* flags a JPEG 2000 IFD's
+    segments are to be handed over with."""
     spp = ifd["spp"]
+    # a three-sample chunky JPEG 2000 IFD: YCbCr components outside the codestream
+    j2k_rgb = ifd["compression"] in _TIFF_J2K_COMPRESSIONS and spp == 3 and ifd.get("planar", 1) == 1
+    ycbcr = j2k_rgb and ((j2k_chroma and ifd.get("photometric") == 6) or (aperio_ycbcr and ifd["compression"] == 33003))
     if spp < 1 or spp > 4:
         raise PbxError(400, "%s: SamplesPerPixel %d (1 to 4 are supported)" % (path, spp))
     if spp > 1 and ifd.get("bits_count", 1) != spp:  # TIFF 6.0: one BitsPerSample value per sample
         raise PbxError(400, "%s: SamplesPerPixel %d with %d BitsPerSample value(s)"
                        % (path, spp, ifd.get("bits_count", 1)))
     jpeg = ifd["compression"] == TIFF_JPEG
-    if spp > 1 and ifd.get("photometric") not in (None, 1, 2) and not (jpeg and ifd["photometric"] == 6 and spp == 3):
+    if spp > 1 and ifd.get("photometric") not in (None, 1, 2) and not (jpeg and ifd["photometric"] == 6 and spp == 3) \
+            and not (ycbcr and ifd["photometric"] == 6 and j2k_chroma):
         raise PbxError(400, "%s: PhotometricInterpretation %d with SamplesPerPixel %d (1 BlackIsZero or 2 RGB, 6 YCbCr "
                        "with 3 samples under Compression 7; palette and CMYK are not supported)"
                        % (path, ifd["photometric"], spp))
@@ -1306,13 +1333,17 @@ def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False) -> int:
         if ifd["predictor"] != 1:
             raise PbxError(400, "%s: Predictor %d with Compression %d (JPEG 2000 segments take 1 only)"
                            % (path, ifd["predictor"], ifd["compression"]))
-        if ifd.get("photometric") not in (None, 0, 1, 2):
+        if ifd.get("photometric") not in (None, 0, 1, 2) and not (ycbcr and ifd["photometric"] == 6 and j2k_chroma):
             raise PbxError(400, "%s: PhotometricInterpretation %d with Compression %d (JPEG 2000: 0, 1 or 2)"
                            % (path, ifd["photometric"], ifd["compression"]))
         if spp not in (1, 3) and not planar:
             raise PbxError(400, "%s: Compression %d (JPEG 2000) with SamplesPerPixel %d (1, or 3 chunky)"
                            % (path, ifd["compression"], spp))
-        _tiff_j2k_first_segment(path, ifd, 1 if planar else spp, ifd["bits"], j2k_packets)
+        sub = _tiff_j2k_first_segment(path, ifd, 1 if planar else spp, ifd["bits"], j2k_packets,
+                                      bool(j2k_chroma and j2k_rgb), bool(ycbcr))
+        if j2k_flags is not None:
+            j2k_flags.append((TIFF_F_J2K_PACKETS if j2k_packets else 0) | (TIFF_F_J2K_SUBSAMPLED if sub else 0) |
+                             (TIFF_F_J2K_YCBCR if ycbcr else 0))
     if jpeg:
         planar = spp > 1 and ifd.get("planar", 1) == 2
         if ifd["predictor"] != 1:
@@ -1343,7 +1374,8 @@ def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False) -> int:
 
 
 def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int, level: int = 0,
-                    sample: int = 0, j2k_packets: bool = False) -> dict:
+                    sample: int = 0, j2k_packets: bool = False, j2k_chroma: bool = False,
+                    aperio_ycbcr: bool = False) -> dict:
     """register_tiff_planes() arguments for the plane that is sample `sample` of one IFD (a
     tiff_ifds() dict, main or SubIFD): its segments are read from the file as they are, nothing
     is decoded here.  A chunky IFD (PlanarConfiguration 1) of S samples per pixel gives
@@ -1352,20 +1384,28 @@ def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int,
     of the segments of its group `sample`.  PbxError 400 names what is not supported.
     j2k_packets (JPEG 2000 IFDs only): take streams with several quality layers, several precincts
     in a resolution and SOP / EPH markers; the spec then carries flags = TIFF_F_J2K_PACKETS.
-    Without it such a file is refused by name, as it always was."""
-    return dict(_tiff_segment_rows(path, ifd, 0, None, sample, j2k_packets), image_id=image_id, z=z, c=c, t=t,
-                level=level)
+    Without it such a file is refused by name, as it always was.
+    j2k_chroma (three-sample chunky JPEG 2000 IFDs only): take streams whose second and third
+    components are stored at half width and / or half height (2 x 1, 1 x 2 or 2 x 2; replicated on
+    the GPU), and PhotometricInterpretation 6: the components are then converted from YCbCr to RGB.
+    The spec's flags carry TIFF_F_J2K_SUBSAMPLED and / or TIFF_F_J2K_YCBCR where the IFD needs them
+    and only then.  Without it both are refused by name, as they always were.
+    aperio_ycbcr: treat Compression 33003 with three chunky samples as YCbCr whatever the
+    photometric tag says (OpenSlide's rule; off by default because the IFD does not say so)."""
+    return dict(_tiff_segment_rows(path, ifd, 0, None, sample, j2k_packets, j2k_chroma, aperio_ycbcr), image_id=image_id,
+                z=z, c=c, t=t, level=level)
 
 
 def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sample: int = 0,
-                       j2k_packets: bool = False) -> dict:
+                       j2k_packets: bool = False, j2k_chroma: bool = False, aperio_ycbcr: bool = False) -> dict:
     """What tiff_plane_spec and tiff_band_spec share: the IFD's pixel type, geometry and byte
     order, and segments = (data, offsets) of its segment rows [sr0, sr1) (sr1 None: to the last;
     sr1 == sr0: none, segments is None and the file is not opened), each full width, read from
     the file as they are.  A planar IFD holds spp groups of gx * gy segments, one per sample:
     the rows are those of group `sample`."""
     import numpy as np
-    pt = _tiff_pixel_type(path, ifd, j2k_packets)
+    j2k_flags: list = []
+    pt = _tiff_pixel_type(path, ifd, j2k_packets, j2k_chroma, aperio_ycbcr, j2k_flags)
     spp = ifd["spp"]
     if not 0 <= sample < spp:
         raise PbxError(400, "%s: sample %d outside SamplesPerPixel %d" % (path, sample, spp))
@@ -1397,8 +1437,8 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
                              ycbcr=ifd.get("photometric") == 6 and not planar)
     if ifd["compression"] in _TIFF_J2K_COMPRESSIONS:  # -> the pbx_*_tiff_j2k calls
         extra["j2k"] = True
-        if j2k_packets:
-            extra["flags"] = TIFF_F_J2K_PACKETS
+        if j2k_flags and j2k_flags[0]:
+            extra["flags"] = j2k_flags[0]
     return dict(extra, samples_per_pixel=1 if planar else spp, sample=0 if planar else sample, pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
                 big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"], seg_h=ifd["seg_h"],
                 tiled=ifd["tiled"],
@@ -1407,7 +1447,8 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
                 predictor=ifd["predictor"], segments=segments)
 
 
-def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0, j2k_packets: bool = False) -> dict:
+def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0, j2k_packets: bool = False,
+                   j2k_chroma: bool = False, aperio_ycbcr: bool = False) -> dict:
     """band_write_tiff() arguments for rows [y0, y0 + rows) of the plane that is sample `sample`
     of one IFD (a tiff_ifds() dict, main or SubIFD; samples_per_pixel and sample as
     tiff_plane_spec, and of a planar IFD only that sample's segments are read): pixel_type, size_x, size_y, big_endian (the file's byte order),
@@ -1416,12 +1457,12 @@ def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0, j2
     ranges of the file are read.  rows == 0 reads nothing (segments is None): the geometry and
     byte order alone (of a Compression-7 IFD also segment 0, whose header decides whether the file
     can be loaded at all).  PbxError 400 as tiff_plane_spec, and for rows outside the plane.
-    j2k_packets: as tiff_plane_spec's."""
+    j2k_packets, j2k_chroma, aperio_ycbcr: as tiff_plane_spec's."""
     if rows < 0 or y0 < 0 or y0 + rows > ifd["length"]:
         raise PbxError(400, "%s: rows %d+%d outside the image (%d rows)" % (path, y0, rows, ifd["length"]))
     sr0 = y0 // ifd["seg_h"]
     sr1 = -(-(y0 + rows) // ifd["seg_h"]) if rows else sr0
-    return dict(_tiff_segment_rows(path, ifd, sr0, sr1, sample, j2k_packets), y0=y0, rows=rows)
+    return dict(_tiff_segment_rows(path, ifd, sr0, sr1, sample, j2k_packets, j2k_chroma, aperio_ycbcr), y0=y0, rows=rows)
 
 
 def _ome_layout(path: str, xml: str, samples: int = 1) -> Optional[dict]:
@@ -1496,17 +1537,17 @@ def _ome_layout(path: str, xml: str, samples: int = 1) -> Optional[dict]:
     return dict(size_z=sz, size_c=sc, size_t=st, planes=planes, pixel_type=PIXEL_TYPES.index(typ), size_xy=sxy)
 
 
-def tiff_image_layout(path: str, j2k_packets: bool = False) -> dict:
+def tiff_image_layout(path: str, j2k_packets: bool = False, j2k_chroma: bool = False, aperio_ycbcr: bool = False) -> dict:
     """What register_tiff_image and TiffSource make of a file: ifds (tiff_ifds), planes = the
     (z, c, t) of main IFD k's first sample, samples = S (SamplesPerPixel, the same in every IFD),
     size_z / size_c / size_t, pixel_type, levels (1 + SubIFDs per main IFD).  Every sample is a
     channel, ExtraSamples included: channel c lies in the IFD of (z, c - c % S, t) as sample
     c % S.  OME-TIFF: the first Image's SizeZ/C/T and DimensionOrder, IFD k = channel group k in
     that order.  Any other multi-page TIFF: page k is t = k and size_c = S (Bio-Formats'
-    BaseTiffReader puts the pages of a plain TIFF on the time axis).  j2k_packets: as
-    tiff_plane_spec's, for the header checks of JPEG 2000 IFDs."""
+    BaseTiffReader puts the pages of a plain TIFF on the time axis).  j2k_packets, j2k_chroma,
+    aperio_ycbcr: as tiff_plane_spec's, for the header checks of JPEG 2000 IFDs."""
     ifds = tiff_ifds(path)
-    pt = _tiff_pixel_type(path, ifds[0], j2k_packets)
+    pt = _tiff_pixel_type(path, ifds[0], j2k_packets, j2k_chroma, aperio_ycbcr)
     S = ifds[0]["spp"]
     ome = _ome_layout(path, ifds[0]["description"], S) if ifds[0]["description"] else None
     if ome is not None:
@@ -1522,7 +1563,7 @@ def tiff_image_layout(path: str, j2k_packets: bool = False) -> dict:
     out["samples"] = S
     first = out["ifds"][0]
     for k, d in enumerate(out["ifds"]):
-        if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d, j2k_packets) != pt:
+        if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d, j2k_packets, j2k_chroma, aperio_ycbcr) != pt:
             raise PbxError(400, "%s: IFD %d differs from the first in size or pixel type" % (path, k))
         for sd in [d] + d["subifds"]:
             if sd["spp"] != S:
@@ -1958,8 +1999,8 @@ class PixelsService:
         del keep
         return (list(ids), (ms[0], ms[1])) if timing else list(ids)
 
-    def register_tiff_image(self, path: str, image_id: int,
-                            j2k_packets: bool = True) -> Dict[int, Dict[Tuple[int, int, int], int]]:
+    def register_tiff_image(self, path: str, image_id: int, j2k_packets: bool = True, j2k_chroma: bool = True,
+                            aperio_ycbcr: bool = False) -> Dict[int, Dict[Tuple[int, int, int], int]]:
         """A whole TIFF / OME-TIFF file -- what the ordinary PixelsService opens through
         Bio-Formats for an image without an NGFF fileset (config.yaml:18) -- in ONE set of GPU
         launches: every plane of every level (tiff_image_layout: OME-XML axes, or page k = t;
@@ -1968,12 +2009,14 @@ class PixelsService:
         decoded once and split into its S planes on the GPU; a planar one S single-sample
         planes.  All are registered, or none.  Returns {level: {(z, c, t): plane id}}, as
         register_ngff_image.  j2k_packets (default on here, where whole files are served): JPEG
-        2000 IFDs are read with tiff_plane_spec's keyword of that name."""
-        lay = tiff_image_layout(path, j2k_packets)
+        2000 IFDs are read with tiff_plane_spec's keyword of that name.  j2k_chroma (default on
+        here too) and aperio_ycbcr (off: the IFD does not say so): likewise."""
+        lay = tiff_image_layout(path, j2k_packets, j2k_chroma, aperio_ycbcr)
 
-        def plane_spec(d, *a, **kw):  # (the keyword only where it means something)
-            if j2k_packets and d["compression"] in _TIFF_J2K_COMPRESSIONS:
-                kw["j2k_packets"] = True
+        def plane_spec(d, *a, **kw):  # (the keywords only where they mean something)
+            if d["compression"] in _TIFF_J2K_COMPRESSIONS:
+                kw.update({k: True for k, v in (("j2k_packets", j2k_packets), ("j2k_chroma", j2k_chroma),
+                                                ("aperio_ycbcr", aperio_ycbcr)) if v})
             return tiff_plane_spec(path, d, *a, **kw)
         specs, keys = [], []
         for (z, c, t), ifd in zip(lay["planes"], lay["ifds"]):
@@ -2736,10 +2779,13 @@ class TiffSource(PixelSource):
     loaded, each from the strips or tile rows that cover it (band_segments -> load_bands ->
     band_write_tiff).  Either way every byte of pixel data is decoded on the GPU."""
 
-    def __init__(self, images: Mapping[int, str], j2k_packets: bool = True):
+    def __init__(self, images: Mapping[int, str], j2k_packets: bool = True, j2k_chroma: bool = True,
+                 aperio_ycbcr: bool = False):
         import threading
         self.images = dict(images)
-        self.j2k_packets = j2k_packets  # JPEG 2000 IFDs: tiff_plane_spec's keyword of that name
+        self.j2k_packets = j2k_packets  # JPEG 2000 IFDs: tiff_plane_spec's keywords of these names
+        self.j2k_chroma = j2k_chroma
+        self.aperio_ycbcr = aperio_ycbcr
         self._opened: Dict[int, dict] = {}
         self._lock = threading.Lock()
 
@@ -2747,7 +2793,8 @@ class TiffSource(PixelSource):
         with self._lock:
             lay = self._opened.get(image_id)
             if lay is None:
-                lay = self._opened[image_id] = tiff_image_layout(self.images[image_id], self.j2k_packets)
+                lay = self._opened[image_id] = tiff_image_layout(self.images[image_id], self.j2k_packets, self.j2k_chroma,
+                                                                  self.aperio_ycbcr)
             return lay
 
     def get_pixels(self, image_id: int) -> Optional[Pixels]:
@@ -2770,8 +2817,10 @@ class TiffSource(PixelSource):
         return d["width"], d["length"]
 
     def _j2k_kw(self, ifd: dict) -> dict:
-        """(the keyword only for a JPEG 2000 IFD: every other file is the call it always was)"""
-        return {"j2k_packets": True} if self.j2k_packets and ifd["compression"] in _TIFF_J2K_COMPRESSIONS else {}
+        """(the keywords only for a JPEG 2000 IFD: every other file is the call it always was)"""
+        if ifd["compression"] not in _TIFF_J2K_COMPRESSIONS:
+            return {}
+        return {k: True for k in ("j2k_packets", "j2k_chroma", "aperio_ycbcr") if getattr(self, k)}
 
     def plane_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Optional[dict]:
         ifd, sample = self._ifd(pixels, z, c, t, level)
