@@ -295,7 +295,18 @@ typedef struct pbx_zarr_chunks {
  * .zarray dtype's ('<' little, '>' / '|' big); source/host_data are ignored.
  * kernel_ms (may be NULL): [0] device ms of the decode kernels and the checksum kernel
  * (k_zarr_crc: crc32c chunks, gzip trailers), [1] of the placement kernel.
- * A malformed or unsupported chunk fails the whole plane with 400 (nothing registered). */
+ * A malformed or unsupported chunk fails the whole plane with 400 (nothing registered).
+ * A stream the device refuses is named "corrupt chunk stream N (codec, decoder code C)".  For
+ * zlib / gzip (k_zarr_inflate2, k_zarr_inflate; the verdicts are zlib's) C is: 10 RFC 1950
+ * header, 11 stored NLEN, 12 stored run past the input or the chunk, 13 block type 3, 14 HLIT >
+ * 286 or HDIST > 30, 15 / 19 / 20 the code-length / literal-length / distance code lengths are
+ * not a valid set (over-subscribed, or incomplete: only a literal/length or distance set whose
+ * longest code is one bit may be incomplete; 19 also when symbol 256 has no code), 16 unassigned
+ * code-length code (unreachable since 15 demands a complete code; the guard stays), 17 repeat of
+ * nothing, 18 repeat past the count, 21 unassigned literal/length code, 22 literal past the
+ * chunk, 23 length symbol 286 / 287, 24 unassigned or invalid distance code, 25 distance before
+ * the start or match past the chunk, 26 input overrun, 27 chunk not filled, 28 trailer cut,
+ * 29 Adler-32, 31 bytes after a gzip member's trailer. */
 int pbx_plane_register_zarr(pbx_ctx* ctx, const pbx_plane_desc* desc, const pbx_zarr_chunks* chunks,
                             uint64_t* plane_id, double* kernel_ms);
 /* n planes (e.g. every (z, c, t) plane of an NGFF resolution level) decoded by ONE set of

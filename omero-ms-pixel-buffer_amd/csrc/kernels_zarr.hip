@@ -296,7 +296,12 @@ struct BitIn {
     __device__ uint32_t consumed_bytes() const { return ipos - cnt / 8; }
 };
 
-// Build the table of n code lengths lens[0..n) (LDS); returns false if over-subscribed.
+// Build the table of n code lengths lens[0..n) (LDS); returns false unless they are a set zlib's
+// inflate_table accepts: not over-subscribed, and complete.  Only a set whose longest code is one
+// bit (or that has no code at all) may be incomplete, and only when !STRICT: the literal/length
+// and distance sets.  The code-length code is STRICT (an empty one is refused here; zlib reads
+// zeros from it and then misses the end-of-block code).
+template <bool STRICT = false>
 __device__ bool build_table(HTab& h, uint32_t lens /* LDS offset */, uint32_t n, uint32_t lane,
                             uint32_t next /* LDS offset of 16 counters */) {
     const uint32_t L = lane + 1;
@@ -335,7 +340,8 @@ __device__ bool build_table(HTab& h, uint32_t lens /* LDS offset */, uint32_t n,
         }
     }
     __builtin_amdgcn_wave_barrier();
-    return !over;
+    // (lanes 1..14 hold the counts of the lengths 2..15: a code longer than one bit)
+    return !over && !(left > 0 && (STRICT || __ballot(cnt != 0 && lane >= 1) != 0));
 }
 
 // Canonical decode of the code in the low bits of `bits` (>= 15 valid bits): the symbol, and
@@ -482,13 +488,13 @@ __global__ __launch_bounds__(256) void k_zarr_inflate(const ZStream* __restrict_
             }
             __builtin_amdgcn_wave_barrier();
             HTab ct{0, 0, 0, wb + ZI_LSYMS};
-            if (!build_table(ct, LENS, 19, lane, NEXT)) { bad = 15; break; }
+            if (!build_table<true>(ct, LENS, 19, lane, NEXT)) { bad = 15; break; }
             // code lengths for litlen + dist go to lens[19..] first, then move down
             uint32_t k = 0, prev = 0;
             while (k < hlit + hdist) {
                 bi.refill();
                 const int sym = decode_sym(ct, bi, lane);
-                if (sym < 0) { bad = 16; break; }
+                if (sym < 0) { bad = 16; break; }  // (a complete code has no unassigned code: kept as a guard)
                 uint32_t rep = 1, val = (uint32_t)sym;
                 if (sym == 16) {
                     if (k == 0) { bad = 17; break; }
@@ -517,6 +523,7 @@ __global__ __launch_bounds__(256) void k_zarr_inflate(const ZStream* __restrict_
                 if (lane < 32) zlds[LENS + 288 + lane] = dv;
                 __builtin_amdgcn_wave_barrier();
             }
+            if (rfl(zlds[LENS + 256]) == 0) { bad = 19; break; }  // no end-of-block code
             if (!build_table(lt, LENS, 288, lane, NEXT)) { bad = 19; break; }
             if (!build_table(dt, LENS + 288, 30, lane, NEXT)) { bad = 20; break; }
             build_lut(lt, LENS, wb + ZI_LLUT, lane);
@@ -923,12 +930,12 @@ __device__ __forceinline__ void zp_producer(const ZStream& t, const uint8_t* src
             }
             __builtin_amdgcn_wave_barrier();
             HTab ct{0, 0, 0, sb + ZP_LSYMS};
-            if (!build_table(ct, LENS, 19, lane, NEXT)) { bad = 15; break; }
+            if (!build_table<true>(ct, LENS, 19, lane, NEXT)) { bad = 15; break; }
             uint32_t k = 0, prev = 0;
             while (k < hlit + hdist) {
                 bi.refill();
                 const int sym = decode_sym(ct, bi, lane);
-                if (sym < 0) { bad = 16; break; }
+                if (sym < 0) { bad = 16; break; }  // (a complete code has no unassigned code: kept as a guard)
                 uint32_t rep = 1, val = (uint32_t)sym;
                 if (sym == 16) {
                     if (k == 0) { bad = 17; break; }
@@ -956,6 +963,7 @@ __device__ __forceinline__ void zp_producer(const ZStream& t, const uint8_t* src
                 if (lane < 32) zlds[LENS + 288 + lane] = dv;
                 __builtin_amdgcn_wave_barrier();
             }
+            if (rfl(zlds[LENS + 256]) == 0) { bad = 19; break; }  // no end-of-block code
             if (!build_table(lt, LENS, 288, lane, NEXT)) { bad = 19; break; }
             if (!build_table(dt, LENS + 288, 30, lane, NEXT)) { bad = 20; break; }
         }
