@@ -2067,19 +2067,66 @@ int band_write(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const void* dat
     });
 }
 
+// The scratch of one decode launch on stream `st`: blocks of the context's device pool, the
+// launch's three events and the first HIP error (`e`; nothing is allocated or queued after one).
+// It goes away as the launch's function returns, on every path: the stream is drained first
+// (queued copies, memsets or decoders may still write the blocks, and the pool hands them to
+// other streams' batches as soon as they are back), then the blocks return, then the events.
+struct LaunchScratch {
+    pbx_ctx* ctx;
+    hipStream_t st;
+    hipError_t e = hipSuccess;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    std::vector<void*> blocks;
+    LaunchScratch(pbx_ctx* c, hipStream_t s) : ctx(c), st(s) {}
+    LaunchScratch(const LaunchScratch&) = delete;
+    ~LaunchScratch() {
+        (void)hipStreamSynchronize(st);
+        for (void* q : blocks) ctx->dpool.put(q);
+        for (auto& x : ev) if (x) (void)hipEventDestroy(x);
+    }
+    // a block of `bytes` (256 at least), contents undefined
+    uint8_t* raw(size_t bytes) {
+        if (e != hipSuccess) return nullptr;
+        void* q = ctx->dpool.get(std::max<size_t>(bytes, 256), &e);
+        if (q) blocks.push_back(q);
+        return (uint8_t*)q;
+    }
+    // a block for the table `v`, and its upload queued (an empty table: the block alone)
+    template <class T>
+    T* table(const std::vector<T>& v) {
+        T* d = (T*)raw(sizeof(T) * v.size());
+        if (d && !v.empty()) e = hipMemcpyAsync(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, st);
+        return d;
+    }
+    template <class T>
+    T* table_if(bool wanted, const std::vector<T>& v) { return wanted ? table(v) : nullptr; }
+    void events() {
+        for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
+    }
+};
+
+// The band-write entry points: pins the READY plane `id` (a 409 from the pin reads "not a sparse
+// plane", as band_of_rows says of a plane without bands), runs write(plane) and unpins it; the
+// thread's last error stays the write's.
+template <class Write>
+int with_sparse_plane(pbx_ctx* ctx, uint64_t id, Write&& write) {
+    int rc;
+    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
+    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
+    rc = write(q);
+    const std::string msg = last_error();
+    unpin_one(ctx, q);
+    last_error() = msg;
+    return rc;
+}
+
 }  // namespace
 extern "C" {
 
 int pbx_band_write(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const void* data, uint64_t bytes) {
     if (!ctx) return fail(PBX_E_BADARG, "null ctx");
-    int rc;
-    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
-    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
-    rc = band_write(ctx, q, y0, rows, data, bytes);
-    const std::string msg = last_error();
-    unpin_one(ctx, q);
-    last_error() = msg;
-    return rc;
+    return with_sparse_plane(ctx, id, [&](Plane* q) { return band_write(ctx, q, y0, rows, data, bytes); });
 }
 
 int pbx_band_abort(pbx_ctx* ctx, uint64_t id, int32_t y0) {
@@ -2322,262 +2369,119 @@ struct ZarrInput {
     uint64_t len;   // `used` rounded up to 16: the rest is zeroed
 };
 
-// One decode launch on stream `st`: uploads the chunk bytes `in` (in_bytes in all), runs the
-// decoders of P's streams and places P's chunks into the destinations `zp` (plane or band
-// bases and their row windows), then waits for it all.  The launch scratch (input, decoded
-// chunks, tables) comes from the context's device pool and goes back to it.  400 for a stream
-// a decoder rejects; rows already placed are then the caller's to discard.  P.unpred (TIFF
-// segments stored with Predictor = 2) is undone in scratch between the decoders and the placement;
-// P.uplace (the same for a band write) is un-predicted and placed into zp[0] by one kernel after
-// the decoders, and k_zarr_place is launched only if P has chunks.  P.split (multi-sample TIFF
-// segments) is un-predicted and split into the planes of `sd` by k_tiff_split_place.  P.fplace
-// (TIFF segments stored with Predictor = 3) is un-predicted and placed by k_tiff_fpunpred_place
-// into the planes P.fdst_plane names.  P.jstreams (JPEG-compressed TIFF segments) are decoded by
-// k_tiff_jpeg_decode after the other decoders, their err[] entries after the checks', and
-// P.jsegs upsampled, converted and placed into the planes of `sd` by k_tiff_jpeg_place.
-// P.j2streams (JPEG 2000 TIFF segments) go through k_tiff_j2k_packets, _gather, _blocks and _idwt after
-// those, their err[] entries last, and P.j2segs are placed by k_tiff_j2k_place, those with
-// subsampled or YCbCr components (J2_SEG_CHROMA; uploaded after the others) by
-// k_tiff_j2k_place_chroma.
+// One decode launch on stream `st`: uploads the chunk or segment bytes `in` (in_bytes in all,
+// each input's tail zeroed to 16 bytes, 4096 zero bytes of over-read slack after the last) and
+// the tables of P, runs the decoders, places what they decoded into the destinations `zp` (plane
+// or band bases and their row windows) and `sd` (the TSplitDst entries that split, JPEG and JPEG
+// 2000 segments name), then waits for it all.  LaunchLayout says which tables go up beside P's own
+// and where in err[] each decoder reports; LaunchScratch holds the device blocks.  What runs
+// follows from what P holds, in this order on the stream:
+//   the crc32c checks (uploaded bytes), the stream decoders by kind, the gzip CRC-32 checks (decoded
+//   bytes), k_tiff_unpred (P.unpred), the JPEG decoder (P.jstreams), the JPEG 2000 chain
+//   (P.j2streams)                                                       -- kernel_ms[0]
+//   k_zarr_place (P.chunks), k_tiff_unpred_place into zp[0] (P.uplace), k_tiff_split_place
+//   (P.split), k_tiff_fpunpred_place into the planes P.fdst_plane names (P.fplace),
+//   k_tiff_jpeg_place (P.jsegs), k_tiff_j2k_place and _place_chroma (P.j2segs)  -- kernel_ms[1]
+// 400 (launch_errors) for a stream a decoder or a check rejects; rows already placed are then the
+// caller's to discard.
 int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std::vector<ZPlane>& zp,
                       const std::vector<ZarrInput>& in, uint64_t in_bytes, int32_t max_cy, double* kernel_ms,
                       const std::vector<TSplitDst>* sd = nullptr) {
-    if ((!P.split.empty() || !P.jsegs.empty() || !P.j2segs.empty()) && (!sd || sd->empty()))
+    const bool unpred = !P.unpred.empty(), uplace = !P.uplace.empty(), split = !P.split.empty();
+    const bool fplace = !P.fplace.empty(), jpeg = !P.jstreams.empty(), j2k = !P.j2streams.empty();
+    if ((split || !P.jsegs.empty() || !P.j2segs.empty()) && (!sd || sd->empty()))
         return fail(PBX_E_INTERNAL, "zarr decode: split segments without destinations");
-    uint32_t counts[ZS_NKINDS], nstreams = 0;
-    std::vector<ZStream> all;
-    for (uint32_t k = 0; k < ZS_NKINDS; k++) {
-        counts[k] = (uint32_t)P.kind[k].size();
-        nstreams += counts[k];
-        all.insert(all.end(), P.kind[k].begin(), P.kind[k].end());
-    }
-    // checks by polynomial, short ranges (a wave each) before long ones (a workgroup each)
-    std::vector<ZCheck> checks;
-    uint32_t ck_first[ZK_NPOLY], ck_wave[ZK_NPOLY], ck_n[ZK_NPOLY];
-    for (uint32_t k = 0; k < ZK_NPOLY; k++) {
-        const uint32_t split = zarr_crc_split();
-        ck_first[k] = (uint32_t)checks.size();
-        for (const ZCheck& c : P.checks[k]) if (c.len < split) checks.push_back(c);
-        ck_wave[k] = (uint32_t)checks.size() - ck_first[k];
-        for (const ZCheck& c : P.checks[k]) if (c.len >= split) checks.push_back(c);
-        ck_n[k] = (uint32_t)checks.size() - ck_first[k];
-    }
-    const uint32_t nchecks = (uint32_t)checks.size(), njpeg = (uint32_t)P.jstreams.size();
-    const uint32_t nj2 = (uint32_t)P.j2streams.size();
-    const uint32_t nerr = nstreams + nchecks + njpeg + nj2;  // err[]: streams, checks, JPEG, JPEG 2000 streams
-    std::vector<TJ2Seg> j2segs = P.j2segs;
-    const uint32_t j2chroma = (uint32_t)(j2segs.end() - std::stable_partition(j2segs.begin(), j2segs.end(), [](const TJ2Seg& u) {
-                                             return !(u.rct & J2_SEG_CHROMA);
-                                         }));
-    const uint64_t j2meta = (sizeof(J2Code) + sizeof(J2Walk)) * P.j2blocks.size() + sizeof(J2Contrib) * P.j2cons + 4 * P.j2nodes;
-    uint8_t *d_in = nullptr, *d_scr = nullptr, *d_lit = nullptr;
-    ZStream* d_st = nullptr;
-    ZCheck* d_ck = nullptr;
-    ZChunk* d_ch = nullptr;
-    ZPlane* d_pl = nullptr;
-    TUnpred* d_up = nullptr;
-    TPlace* d_tp = nullptr;
-    TPlace* d_sp = nullptr;
-    TSplitDst* d_sd = nullptr;
-    TPlace* d_fp = nullptr;
-    TPlaceDst* d_fd = nullptr;
-    JStream* d_js = nullptr;
-    JTabSet* d_jt = nullptr;
-    TJpegSeg* d_jp = nullptr;
-    J2Stream* d_2s = nullptr;
-    J2Band* d_2b = nullptr;
-    J2Packet* d_2q = nullptr;
-    J2Block* d_2k = nullptr;
-    J2Comp* d_2c = nullptr;
-    TJ2Seg* d_2p = nullptr;
-    uint8_t* d_2m = nullptr;
-    uint32_t* d_err = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    auto cleanup = [&] {
-        // queued copies, memsets or decoders may still write these blocks on an error path;
-        // the pool hands them to other streams' batches as soon as they are back
-        (void)hipStreamSynchronize(st);
-        for (void* q : {(void*)d_in, (void*)d_scr, (void*)d_lit, (void*)d_st, (void*)d_ck, (void*)d_ch, (void*)d_pl, (void*)d_up, (void*)d_tp, (void*)d_sp, (void*)d_sd, (void*)d_fp, (void*)d_fd, (void*)d_js, (void*)d_jt, (void*)d_jp, (void*)d_2s, (void*)d_2b, (void*)d_2q, (void*)d_2k, (void*)d_2c, (void*)d_2p, (void*)d_2m, (void*)d_err})
-            if (q) ctx->dpool.put(q);
-        for (auto& x : ev) if (x) (void)hipEventDestroy(x);
-    };
-    hipError_t e = hipSuccess;
-    auto dget = [&](auto*& ptr, size_t bytes) {
-        if (e != hipSuccess) return;
-        ptr = (std::remove_reference_t<decltype(ptr)>)ctx->dpool.get(std::max<size_t>(bytes, 256), &e);
-    };
-    dget(d_in, in_bytes + 4096);  // decoder window over-read slack
-    if (P.scratch) dget(d_scr, P.scratch);
-    if (counts[ZS_ZSTD]) dget(d_lit, zstd_scratch_bytes(counts[ZS_ZSTD]));
-    if (nstreams) dget(d_st, sizeof(ZStream) * nstreams);
-    if (nchecks) dget(d_ck, sizeof(ZCheck) * nchecks);
-    dget(d_ch, sizeof(ZChunk) * P.chunks.size());
-    dget(d_pl, sizeof(ZPlane) * zp.size());
-    if (!P.unpred.empty()) dget(d_up, sizeof(TUnpred) * P.unpred.size());
-    if (!P.uplace.empty()) dget(d_tp, sizeof(TPlace) * P.uplace.size());
-    if (!P.split.empty()) dget(d_sp, sizeof(TPlace) * P.split.size());
-    if (!P.split.empty() || njpeg || nj2) dget(d_sd, sizeof(TSplitDst) * sd->size());
-    if (nj2) {
-        dget(d_2s, sizeof(J2Stream) * nj2);
-        dget(d_2b, sizeof(J2Band) * P.j2bands.size());
-        dget(d_2q, sizeof(J2Packet) * P.j2packets.size());
-        dget(d_2k, sizeof(J2Block) * P.j2blocks.size());
-        dget(d_2c, sizeof(J2Comp) * P.j2comps.size());
-        dget(d_2p, sizeof(TJ2Seg) * P.j2segs.size());
-        dget(d_2m, j2meta);
-    }
-    if (njpeg) {
-        dget(d_js, sizeof(JStream) * njpeg);
-        dget(d_jt, sizeof(JTabSet) * P.jtabs.size());
-        dget(d_jp, sizeof(TJpegSeg) * P.jsegs.size());
-    }
+    const LaunchLayout L(P, zarr_crc_split());
     std::vector<TPlaceDst> fd = P.fdst;  // Predictor = 3: the destinations of this launch
     for (size_t i = 0; i < fd.size(); i++) {
         const ZPlane& z = zp[P.fdst_plane[i]];
         fd[i].dev = z.dev; fd[i].pitch = z.pitch; fd[i].sx = z.sx; fd[i].sy = z.sy;
         fd[i].y_lo = z.y_lo; fd[i].y_hi = z.y_hi;
     }
-    if (!P.fplace.empty()) {
-        dget(d_fp, sizeof(TPlace) * P.fplace.size());
-        dget(d_fd, sizeof(TPlaceDst) * fd.size());
-    }
-    dget(d_err, sizeof(uint32_t) * (nerr + 1));
-    for (auto& x : ev) if (e == hipSuccess) e = hipEventCreate(&x);
-    if (e != hipSuccess) {
-        cleanup();
-        return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
-    }
+    LaunchScratch S(ctx, st);
+    hipError_t& e = S.e;
+    uint8_t* d_in = S.raw(in_bytes + 4096);  // decoder window over-read slack
+    uint8_t* d_scr = P.scratch ? S.raw(P.scratch) : nullptr;
+    uint8_t* d_lit = L.counts[ZS_ZSTD] ? S.raw(zstd_scratch_bytes(L.counts[ZS_ZSTD])) : nullptr;
+    uint8_t* d_2m = j2k ? S.raw(L.j2meta) : nullptr;
+    uint32_t* d_err = (uint32_t*)S.raw(sizeof(uint32_t) * (L.nerr + 1));
+    S.events();
+    if (e != hipSuccess) return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
     for (size_t k = 0; k < in.size() && e == hipSuccess; k++) {
-        if (in[k].used) {
-            if (int rc = upload_staged(ctx, d_in + in[k].base, in[k].data, in[k].used, st)) {
-                cleanup();
-                return rc;
-            }
-        }
+        if (in[k].used)
+            if (int rc = upload_staged(ctx, d_in + in[k].base, in[k].data, in[k].used, st)) return rc;
         if (in[k].len > in[k].used) e = hipMemsetAsync(d_in + in[k].base + in[k].used, 0, in[k].len - in[k].used, st);
     }
     if (e == hipSuccess) e = hipMemsetAsync(d_in + in_bytes, 0, 4096, st);
-    if (e == hipSuccess && nstreams)
-        e = hipMemcpyAsync(d_st, all.data(), sizeof(ZStream) * nstreams, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nchecks)
-        e = hipMemcpyAsync(d_ck, checks.data(), sizeof(ZCheck) * nchecks, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && !P.chunks.empty())
-        e = hipMemcpyAsync(d_ch, P.chunks.data(), sizeof(ZChunk) * P.chunks.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_pl, zp.data(), sizeof(ZPlane) * zp.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_up)
-        e = hipMemcpyAsync(d_up, P.unpred.data(), sizeof(TUnpred) * P.unpred.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_tp)
-        e = hipMemcpyAsync(d_tp, P.uplace.data(), sizeof(TPlace) * P.uplace.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_sp)
-        e = hipMemcpyAsync(d_sp, P.split.data(), sizeof(TPlace) * P.split.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_sd)
-        e = hipMemcpyAsync(d_sd, sd->data(), sizeof(TSplitDst) * sd->size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_fp)
-        e = hipMemcpyAsync(d_fp, P.fplace.data(), sizeof(TPlace) * P.fplace.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_fd)
-        e = hipMemcpyAsync(d_fd, fd.data(), sizeof(TPlaceDst) * fd.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_js)
-        e = hipMemcpyAsync(d_js, P.jstreams.data(), sizeof(JStream) * njpeg, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_jt)
-        e = hipMemcpyAsync(d_jt, P.jtabs.data(), sizeof(JTabSet) * P.jtabs.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_jp)
-        e = hipMemcpyAsync(d_jp, P.jsegs.data(), sizeof(TJpegSeg) * P.jsegs.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_2s)
-        e = hipMemcpyAsync(d_2s, P.j2streams.data(), sizeof(J2Stream) * nj2, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_2b)
-        e = hipMemcpyAsync(d_2b, P.j2bands.data(), sizeof(J2Band) * P.j2bands.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_2q && !P.j2packets.empty())
-        e = hipMemcpyAsync(d_2q, P.j2packets.data(), sizeof(J2Packet) * P.j2packets.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_2k && !P.j2blocks.empty())
-        e = hipMemcpyAsync(d_2k, P.j2blocks.data(), sizeof(J2Block) * P.j2blocks.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_2c)
-        e = hipMemcpyAsync(d_2c, P.j2comps.data(), sizeof(J2Comp) * P.j2comps.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_2p)
-        e = hipMemcpyAsync(d_2p, j2segs.data(), sizeof(TJ2Seg) * j2segs.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && d_2m) e = hipMemsetAsync(d_2m, 0, std::max<uint64_t>(j2meta, 256), st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (nerr + 1), st);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+    ZStream* d_st = S.table_if(L.nstreams, L.streams);
+    ZCheck* d_ck = S.table_if(L.nchecks, L.checks);
+    ZChunk* d_ch = S.table(P.chunks);
+    ZPlane* d_pl = S.table(zp);
+    TUnpred* d_up = S.table_if(unpred, P.unpred);
+    TPlace* d_tp = S.table_if(uplace, P.uplace);
+    TPlace* d_sp = S.table_if(split, P.split);
+    TSplitDst* d_sd = split || jpeg || j2k ? S.table(*sd) : nullptr;
+    TPlace* d_fp = S.table_if(fplace, P.fplace);
+    TPlaceDst* d_fd = S.table_if(fplace, fd);
+    JStream* d_js = S.table_if(jpeg, P.jstreams);
+    JTabSet* d_jt = S.table_if(jpeg, P.jtabs);
+    TJpegSeg* d_jp = S.table_if(jpeg, P.jsegs);
+    J2Stream* d_2s = S.table_if(j2k, P.j2streams);
+    J2Band* d_2b = S.table_if(j2k, P.j2bands);
+    J2Packet* d_2q = S.table_if(j2k, P.j2packets);
+    J2Block* d_2k = S.table_if(j2k, P.j2blocks);
+    J2Comp* d_2c = S.table_if(j2k, P.j2comps);
+    TJ2Seg* d_2p = S.table_if(j2k, L.j2segs);
+    if (e == hipSuccess && j2k) e = hipMemsetAsync(d_2m, 0, std::max<uint64_t>(L.j2meta, 256), st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(uint32_t) * (L.nerr + 1), st);
+    if (e == hipSuccess) e = hipEventRecord(S.ev[0], st);
     // the crc32c codec's checks read the uploaded bytes only (nothing of the decode); the gzip
     // trailers' read the decoded chunks, before anything is placed
     auto crc = [&](uint32_t k) {
-        return ck_n[k] ? launch_zarr_crc(st, d_ck + ck_first[k], ck_wave[k], ck_n[k], k, d_in, d_scr,
-                                         d_err + nstreams + ck_first[k])
-                       : hipSuccess;
+        return L.ck_n[k] ? launch_zarr_crc(st, d_ck + L.ck_first[k], L.ck_wave[k], L.ck_n[k], k, d_in, d_scr,
+                                           d_err + L.err_checks + L.ck_first[k])
+                         : hipSuccess;
     };
     if (e == hipSuccess) e = crc(ZK_CRC32C);
-    if (e == hipSuccess) e = launch_zarr_decode(st, d_st, counts, d_in, d_scr, d_lit, d_err);
+    if (e == hipSuccess) e = launch_zarr_decode(st, d_st, L.counts, d_in, d_scr, d_lit, d_err + L.err_streams);
     if (e == hipSuccess) e = crc(ZK_CRC32);
-    if (e == hipSuccess && d_up) e = launch_tiff_unpred(st, d_up, (uint32_t)P.unpred.size(), P.unpred_rows, d_scr);
-    if (e == hipSuccess && d_js)
-        e = launch_tiff_jpeg_decode(st, d_js, njpeg, d_jt, d_in, d_scr, d_err + nstreams + nchecks);
-    if (e == hipSuccess && d_2s)
-        e = launch_tiff_j2k_decode(st, d_2s, nj2, d_2q, d_2b, d_2k, (uint32_t)P.j2blocks.size(), (uint32_t)P.j2cons, d_2c,
+    if (e == hipSuccess && unpred) e = launch_tiff_unpred(st, d_up, (uint32_t)P.unpred.size(), P.unpred_rows, d_scr);
+    if (e == hipSuccess && jpeg) e = launch_tiff_jpeg_decode(st, d_js, L.njpeg, d_jt, d_in, d_scr, d_err + L.err_jpeg);
+    if (e == hipSuccess && j2k)
+        e = launch_tiff_j2k_decode(st, d_2s, L.nj2, d_2q, d_2b, d_2k, (uint32_t)P.j2blocks.size(), (uint32_t)P.j2cons, d_2c,
                                    (uint32_t)P.j2comps.size(), P.j2irrev, P.j2coef, P.j2flag, d_2m, d_in, d_scr,
-                                   d_err + nstreams + nchecks + njpeg);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], st);
+                                   d_err + L.err_j2k);
+    if (e == hipSuccess) e = hipEventRecord(S.ev[1], st);
     if (e == hipSuccess && !P.chunks.empty())
         e = launch_zarr_place(st, d_ch, (uint32_t)P.chunks.size(), d_pl, max_cy, d_scr, d_in);
-    if (e == hipSuccess && d_tp) {
+    if (e == hipSuccess && uplace) {
         const ZPlane& z = zp[0];
         e = launch_tiff_unpred_place(st, d_tp, (uint32_t)P.uplace.size(), P.uplace_rows,
                                      TPlaceDst{z.dev, z.pitch, z.sx, z.sy, z.y_lo, z.y_hi, z.bpp,
                                                P.uplace_big_endian ? 1u : 0u},
                                      d_scr, d_in);
     }
-    if (e == hipSuccess && d_sp)
+    if (e == hipSuccess && split)
         e = launch_tiff_split_place(st, d_sp, (uint32_t)P.split.size(), P.split_rows, d_sd, d_scr, d_in);
-    if (e == hipSuccess && d_fp)
+    if (e == hipSuccess && fplace)
         e = launch_tiff_fpunpred_place(st, d_fp, (uint32_t)P.fplace.size(), P.fplace_rows, d_fd, d_scr, d_in);
-    if (e == hipSuccess && d_jp)
+    if (e == hipSuccess && jpeg)
         e = launch_tiff_jpeg_place(st, d_jp, (uint32_t)P.jsegs.size(), P.jseg_rows, d_sd, d_scr);
-    if (e == hipSuccess && d_2p)
-        e = launch_tiff_j2k_place(st, d_2p, (uint32_t)j2segs.size(), j2chroma, P.j2seg_rows, d_sd, d_scr);
-    if (e == hipSuccess) e = hipEventRecord(ev[2], st);
+    if (e == hipSuccess && j2k)
+        e = launch_tiff_j2k_place(st, d_2p, (uint32_t)L.j2segs.size(), L.j2chroma, P.j2seg_rows, d_sd, d_scr);
+    if (e == hipSuccess) e = hipEventRecord(S.ev[2], st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    std::vector<uint32_t> err(nerr + 1, 0);
-    if (e == hipSuccess && nerr)
-        e = hipMemcpy(err.data(), d_err, sizeof(uint32_t) * nerr, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        cleanup();
-        return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
-    }
-    for (uint32_t s = 0; s < nstreams; s++)
-        if (err[s]) {
-            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd", "gzip", "lzw"};
-            uint32_t k = 0, first = 0;
-            while (s >= first + counts[k]) first += counts[k++];
-            cleanup();
-            return fail(PBX_E_BADARG, "corrupt chunk stream %u (%s, decoder code %u)", s, names[k], err[s]);
-        }
-    for (uint32_t s = 0; s < nchecks; s++)
-        if (err[nstreams + s]) {
-            const ZCheck c = checks[s];
-            cleanup();
-            return fail(PBX_E_BADARG, "chunk checksum mismatch: the %s of %u bytes is not 0x%08x",
-                        c.poly == ZK_CRC32C ? "crc32c" : "gzip CRC-32", c.len, c.expect);
-        }
-    for (uint32_t s = 0; s < njpeg; s++)
-        if (const uint32_t code = err[nstreams + nchecks + s]) {
-            static const char* why[6] = {"", "entropy data ends before the last MCU", "a code that is in no table",
-                                         "a run that passes coefficient 63", "a DC size > 11 or an AC size > 10",
-                                         "a restart marker missing, out of sequence or misplaced"};
-            cleanup();
-            return fail(PBX_E_BADARG, "corrupt segment stream %u (jpeg, decoder code %u: %s)", s, code,
-                        code < 6 ? why[code] : "?");
-        }
-    for (uint32_t s = 0; s < nj2; s++)
-        if (const uint32_t code = err[nstreams + nchecks + njpeg + s]) {
-            cleanup();
-            return fail(PBX_E_BADARG, "corrupt segment stream %u (j2k, decoder code %u)", s, code);
-        }
+    std::vector<uint32_t> err(L.nerr + 1, 0);
+    if (e == hipSuccess && L.nerr) e = hipMemcpy(err.data(), d_err, sizeof(uint32_t) * L.nerr, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
+    if (int rc = launch_errors(L, err.data())) return rc;
     if (kernel_ms) {
         float a = 0, b = 0;
-        (void)hipEventElapsedTime(&a, ev[0], ev[1]);
-        (void)hipEventElapsedTime(&b, ev[1], ev[2]);
+        (void)hipEventElapsedTime(&a, S.ev[0], S.ev[1]);
+        (void)hipEventElapsedTime(&b, S.ev[1], S.ev[2]);
         kernel_ms[0] = a;
         kernel_ms[1] = b;
     }
-    cleanup();
     return PBX_OK;
 }
 
@@ -2591,14 +2495,13 @@ int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     if (int rc = zarr_chunks_check(z)) return rc;
     if (int rc = zarr_slice_check(depth, slice)) return rc;
     const int bpp = bpp_of(q->pixel_type);
-    const int64_t gx = (q->size_x + z->chunk_x - 1) / z->chunk_x;
-    const int64_t cy0 = y0 / z->chunk_y, cy1 = ((int64_t)y0 + rows + z->chunk_y - 1) / z->chunk_y;
+    const SourceGrid g = source_grid(z, q->size_x, q->size_y, y0, rows);
     ZarrPlan P;
-    if (int rc = zarr_plan(q->size_x, z, bpp, 0, cy0, cy1, depth, {ZarrWant{(uint32_t)slice, 0}}, y0,
+    if (int rc = zarr_plan(q->size_x, z, bpp, 0, g.r0, g.r1, depth, {ZarrWant{(uint32_t)slice, 0}}, y0,
                            (int64_t)y0 + rows, P))
         return rc;
-    const uint64_t used = z->offsets[gx * (cy1 - cy0)], len = (used + 15) & ~15ull;
-    const std::vector<ZarrInput> in{ZarrInput{z->data, used, 0, len}};
+    const uint64_t len = (g.used + 15) & ~15ull;
+    const std::vector<ZarrInput> in{ZarrInput{z->data, g.used, 0, len}};
     return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
         // rows keep their plane index: the destination is the band's virtual base, as in the
         // tile kernels (pitch and the allocation are 256-byte aligned, so is the base)
@@ -2609,47 +2512,31 @@ int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     });
 }
 
-// pbx_band_write_tiff: pbx_band_write_zarr for segment rows.  The piece's covering segment rows
-// are planned on the host first (a malformed piece never joins the band's load), then uploaded,
-// decoded and placed under the band state machine of band_load_rows.
-// With spp > 1 the segments are chunky and only component `sample` is written (the others'
-// destinations are null).
-// With `j` (pbx_band_write_tiff_jpeg) the segments are JPEG streams: tiff_jpeg_plan, and the one
-// TSplitDst entry for one-sample segments too.
-int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
-                    int32_t spp, int32_t sample, double* kernel_ms, const pbx_tiff_jpeg* j = nullptr,
-                    bool j2k = false) {  // j2k (pbx_band_write_tiff_j2k): JPEG 2000 codestreams, tiff_j2k_plan
+// pbx_band_write_tiff and its _sample, _jpeg and _j2k forms: pbx_band_write_zarr for segment
+// rows.  The piece's covering segment rows are checked and planned on the host first by the
+// codec `c` names (a malformed piece never joins the band's load), then uploaded, decoded and
+// placed under the band state machine of band_load_rows.  With spp > 1 the segments are chunky
+// and only component `sample` is written (the others' destinations are null); those, and JPEG and
+// JPEG 2000 segments of any spp, reach the band through the launch's one TSplitDst entry.
+int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const TiffCodec& c, int32_t spp,
+                    int32_t sample, double* kernel_ms) {
     int32_t k = 0;
     if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
-    if (j2k) {
-        if (int rc = tiff_j2k_check(s, q->pixel_type, spp)) return rc;
-    } else if (j) {
-        if (int rc = tiff_jpeg_check(s, j, q->pixel_type, spp)) return rc;
-    } else if (int rc = tiff_segments_check(s)) {
-        return rc;
-    }
-    if (int rc = tiff_samples_check(spp, sample, bpp_of(q->pixel_type))) return rc;
-    if (s->predictor == 2 && (q->pixel_type == PBX_FLOAT || q->pixel_type == PBX_DOUBLE))
-        return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)q->id);
-    if (int rc = tiff_fp_predictor_check(s, q->pixel_type)) return rc;
+    if (int rc = tiff_codec_check(c, q->pixel_type, spp, sample, q->id)) return rc;
+    const pbx_tiff_segments* s = c.s;
     const int bpp = bpp_of(q->pixel_type);
-    const int64_t gx = s->tiled ? ((int64_t)q->size_x + s->seg_w - 1) / s->seg_w : 1;
-    const int64_t sr0 = y0 / s->seg_h, sr1 = ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h;
+    const SourceGrid g = source_grid(s, q->size_x, q->size_y, y0, rows);
     ZarrPlan P;
-    if (j2k) {
-        if (int rc = tiff_j2k_plan(q->size_x, q->size_y, bpp, s, 0, P, sr0, sr1, spp, 0)) return rc;
-    } else if (j) {
-        if (int rc = tiff_jpeg_plan(q->size_x, q->size_y, s, j, 0, P, sr0, sr1, spp, 0)) return rc;
-    } else if (int rc = tiff_plan(q->size_x, q->size_y, bpp, !q->little_endian, s, 0, 0, P, nullptr, true, sr0, sr1, spp, 0))
+    if (int rc = tiff_codec_plan(c, q->size_x, q->size_y, bpp, !q->little_endian, 0, 0, P, true, g.r0, g.r1, spp, 0))
         return rc;
-    const uint64_t used = s->offsets[gx * (sr1 - sr0)], len = (used + 15) & ~15ull;
-    const std::vector<ZarrInput> in{ZarrInput{s->data, used, 0, len}};
+    const uint64_t len = (g.used + 15) & ~15ull;
+    const std::vector<ZarrInput> in{ZarrInput{s->data, g.used, 0, len}};
     return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
         // rows keep their plane index: the destination is the band's virtual base
         const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
                                             q->size_y, s->seg_w, s->seg_h, (uint32_t)bpp, 0, 0, y0, y0 + rows}};
         std::vector<TSplitDst> sd;
-        if (spp > 1 || j || j2k) {
+        if (spp > 1 || c.jpeg || c.j2k) {
             sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, q->pitch, q->size_x, q->size_y, y0, y0 + rows,
                                    (uint32_t)bpp, q->little_endian ? 0u : 1u, (uint32_t)spp, (uint32_t)s->predictor});
             sd[0].dev[sample] = zp[0].dev;
@@ -2659,46 +2546,67 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_
     });
 }
 
-// pbx_planes_register_zarr (layer k = plane k, one plane per chunk) and its deep form: plane k
-// is slice refs[k].slice of the chunks of layer zs[refs[k].layer], which hold depths[layer]
-// planes each.  A layer's chunks are planned, uploaded and decoded once; its planes follow one
-// another in the ZChunk table.  With `ts` the layers are TIFF segments instead (zs unused, one
-// plane per layer): pbx_planes_register_tiff shares the keys, the all-or-none registration, the
-// staging and the launches.  A TIFF layer with depths[layer] = S > 1 holds chunky segments of S
-// samples per pixel (pbx_planes_register_tiff_samples): its planes are the samples refs[k].slice,
-// each at most once, all split out of the one decode by k_tiff_split_place.
+// The TIFF layers of a registration as its entry point took them: layer l's segments and codec
+// (no `s`: the layers are Zarr chunks).
+struct TiffLayers {
+    const pbx_tiff_segments* s = nullptr;
+    const pbx_tiff_jpeg* jpeg = nullptr;  // the layers are JPEG streams: their tables
+    bool j2k = false;                     // they are JPEG 2000 codestreams
+    explicit operator bool() const { return s != nullptr; }
+    TiffCodec operator[](uint64_t l) const { return TiffCodec{&s[l], jpeg ? &jpeg[l] : nullptr, j2k}; }
+};
+
+int64_t plane_pitch(int32_t size_x, int bpp) { return ((int64_t)size_x * bpp + 255) & ~(int64_t)255; }
+
+// Fills `p` as the whole resident plane `d` describes, not yet allocated.
+void plane_from_desc(const pbx_plane_desc& d, Plane& p) {
+    const int bpp = bpp_of(d.pixel_type);
+    p.image_id = d.image_id; p.z = d.z; p.c = d.c; p.t = d.t; p.res = d.resolution;
+    p.pixel_type = d.pixel_type; p.size_x = d.size_x; p.size_y = d.size_y;
+    p.little_endian = d.byte_order == PBX_LITTLE_ENDIAN && bpp > 1;
+    p.pitch = plane_pitch(d.size_x, bpp);
+    p.bytes = (size_t)p.pitch * d.size_y + 256;
+    p.band_rows = d.size_y;
+}
+
+// A failure exit of a registration: the planes' HBM goes back, the thread's last error stays.
+int release_planes(pbx_ctx* ctx, std::vector<Plane>& ps, int rc) {
+    const std::string msg = last_error();
+    for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
+    last_error() = msg;
+    return rc;
+}
+
+// The plane registrations from chunks or segments.  Plane k is slice refs[k].slice of layer
+// refs[k].layer; a layer is planned, uploaded and decoded once, and one launch
+// (zarr_decode_place) serves the whole call: all planes are registered or none.
+// Zarr layers (zs; pbx_planes_register_zarr: layer k = plane k, one plane per chunk, and its deep
+// form): the chunks of a layer hold depths[layer] planes each, and its planes follow one another
+// in the ZChunk table.
+// TIFF layers (ts; pbx_planes_register_tiff and its _samples, _jpeg and _j2k forms): a layer with
+// depths[layer] = S > 1 holds chunky segments of S samples per pixel, and its planes are the
+// samples refs[k].slice, each at most once.  Those, and JPEG and JPEG 2000 layers of any S, get
+// an entry in the launch's TSplitDst table, through which the placement kernels split them.
 int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
                          uint64_t n_layers, const pbx_zarr_chunks* zs, const int32_t* depths,
-                         uint64_t* plane_ids, double* kernel_ms, const pbx_tiff_segments* ts = nullptr,
-                         const pbx_tiff_jpeg* tj = nullptr,  // tj: the TIFF layers are JPEG streams
-                         bool j2k = false) {                 // j2k: they are JPEG 2000 codestreams
+                         uint64_t* plane_ids, double* kernel_ms, const TiffLayers& ts) {
     std::vector<std::tuple<int64_t, int32_t, int32_t, int32_t, int32_t>> keys;
     std::vector<std::vector<ZarrWant>> want(n_layers);
     for (uint64_t k = 0; k < n; k++) {
         const pbx_plane_desc* d = &ds[k];
-        if (refs[k].layer >= n_layers) return fail(PBX_E_BADARG, "plane %llu: no layer %u", (unsigned long long)k, refs[k].layer);
+        const uint32_t l = refs[k].layer;
+        if (l >= n_layers) return fail(PBX_E_BADARG, "plane %llu: no layer %u", (unsigned long long)k, l);
         if (ts) {
-            if (j2k) {
-                if (int rc = tiff_j2k_check(&ts[refs[k].layer], d->pixel_type, depths[refs[k].layer])) return rc;
-            } else if (tj) {
-                if (int rc = tiff_jpeg_check(&ts[refs[k].layer], &tj[refs[k].layer], d->pixel_type, depths[refs[k].layer]))
-                    return rc;
-            } else if (int rc = tiff_segments_check(&ts[refs[k].layer])) {
-                return rc;
-            }
-            if (ts[refs[k].layer].predictor == 2 && (d->pixel_type == PBX_FLOAT || d->pixel_type == PBX_DOUBLE))
-                return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)k);
-            if (int rc = tiff_fp_predictor_check(&ts[refs[k].layer], d->pixel_type)) return rc;
-            if (int rc = tiff_samples_check(depths[refs[k].layer], refs[k].slice, bpp_of(d->pixel_type))) return rc;
-            for (const ZarrWant& w : want[refs[k].layer])
+            if (int rc = tiff_codec_check(ts[l], d->pixel_type, depths[l], refs[k].slice, k)) return rc;
+            for (const ZarrWant& w : want[l])
                 if (w.slice == refs[k].slice)
                     return fail(PBX_E_BADARG, "planes %u and %llu both name sample %u of layer %u", w.plane,
-                                (unsigned long long)k, refs[k].slice, refs[k].layer);
+                                (unsigned long long)k, refs[k].slice, l);
         } else {
-            if (int rc = zarr_chunks_check(&zs[refs[k].layer])) return rc;
-            if (int rc = zarr_slice_check(depths[refs[k].layer], refs[k].slice)) return rc;
+            if (int rc = zarr_chunks_check(&zs[l])) return rc;
+            if (int rc = zarr_slice_check(depths[l], refs[k].slice)) return rc;
         }
-        want[refs[k].layer].push_back(ZarrWant{refs[k].slice, (uint32_t)k});
+        want[l].push_back(ZarrWant{refs[k].slice, (uint32_t)k});
         if (!bpp_of(d->pixel_type)) return fail(PBX_E_BADARG, "bad pixel type %d", d->pixel_type);
         if (d->size_x <= 0 || d->size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
         if (d->resolution < 0) return fail(PBX_E_BADARG, "bad resolution");
@@ -2714,6 +2622,8 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
                 return fail(PBX_E_BADARG, "planes of layer %llu disagree on size, type or byte order", (unsigned long long)l);
         }
     }
+    std::vector<Plane> ps(n);
+    for (uint64_t k = 0; k < n; k++) plane_from_desc(ds[k], ps[k]);
     {
         auto sorted = keys;
         std::sort(sorted.begin(), sorted.end());
@@ -2728,87 +2638,59 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
                     return fail(PBX_E_BADARG, "planes of image %lld disagree on type or size",
                                 (long long)ds[a].image_id);
         std::lock_guard<std::mutex> g(ctx->reg_mu);
-        for (uint64_t k = 0; k < n; k++) {  // early: a taken key fails before any decoding
-            Plane p;
-            p.image_id = ds[k].image_id; p.z = ds[k].z; p.c = ds[k].c; p.t = ds[k].t;
-            p.res = ds[k].resolution; p.pixel_type = ds[k].pixel_type;
-            p.size_x = ds[k].size_x; p.size_y = ds[k].size_y;
+        for (const Plane& p : ps)  // early: a taken key fails before any decoding
             if (int rc = registry_check(ctx, p)) return rc;
-        }
     }
     // host plan: metadata of every chunk of every plane, one upload buffer, one scratch
     ZarrPlan P;
     std::vector<uint64_t> in_base(n_layers + 1, 0);
     std::vector<ZarrInput> in(n_layers);
     int32_t max_cy = 0;
-    std::vector<TSplitDst> sd;        // one per multi-sample TIFF layer ...
+    std::vector<TSplitDst> sd;        // one per TIFF layer that is split ...
     std::vector<uint64_t> sd_layer;   // ... and which layer that is
     for (uint64_t l = 0; l < n_layers; l++) {
         const pbx_plane_desc* d = &ds[want[l][0].plane];
+        const int bpp = bpp_of(d->pixel_type);
+        SourceGrid g;
+        const uint8_t* data;
         if (ts) {
-            const pbx_tiff_segments* s = &ts[l];
-            const int bpp = bpp_of(d->pixel_type);
+            const TiffCodec c = ts[l];
             const bool big = d->byte_order != PBX_LITTLE_ENDIAN;
-            if (j2k) {
-                if (int rc = tiff_j2k_plan(d->size_x, d->size_y, bpp, s, in_base[l], P, 0, -1, depths[l], (uint32_t)sd.size()))
-                    return rc;
-            } else if (tj) {
-                if (int rc = tiff_jpeg_plan(d->size_x, d->size_y, s, &tj[l], in_base[l], P, 0, -1, depths[l], (uint32_t)sd.size()))
-                    return rc;
-            } else if (int rc = tiff_plan(d->size_x, d->size_y, bpp, big, s, in_base[l], want[l][0].plane, P, nullptr, false,
-                                          0, -1, depths[l], (uint32_t)sd.size()))
+            if (int rc = tiff_codec_plan(c, d->size_x, d->size_y, bpp, big, in_base[l], want[l][0].plane, P, false, 0, -1,
+                                         depths[l], (uint32_t)sd.size()))
                 return rc;
-            if (depths[l] > 1 || tj || j2k) {
-                sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255,
+            if (depths[l] > 1 || c.jpeg || c.j2k) {
+                sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, plane_pitch(d->size_x, bpp),
                                        d->size_x, d->size_y, 0, d->size_y, (uint32_t)bpp, big && bpp > 1 ? 1u : 0u,
-                                       (uint32_t)depths[l], (uint32_t)s->predictor});
+                                       (uint32_t)depths[l], (uint32_t)c.s->predictor});
                 sd_layer.push_back(l);
             }
-            const int64_t gx = s->tiled ? ((int64_t)d->size_x + s->seg_w - 1) / s->seg_w : 1;
-            const int64_t gy = ((int64_t)d->size_y + s->seg_h - 1) / s->seg_h;
-            in_base[l + 1] = in_base[l] + ((s->offsets[gx * gy] + 15) & ~15ull);
-            in[l] = ZarrInput{s->data, s->offsets[gx * gy], in_base[l], in_base[l + 1] - in_base[l]};
-            max_cy = std::max(max_cy, std::min(s->seg_h, d->size_y));
-            continue;
+            g = source_grid(c.s, d->size_x, d->size_y);
+            data = c.s->data;
+            max_cy = std::max(max_cy, std::min(c.s->seg_h, d->size_y));
+        } else {
+            const pbx_zarr_chunks* z = &zs[l];
+            g = source_grid(z, d->size_x, d->size_y);
+            if (int rc = zarr_plan(d->size_x, z, bpp, in_base[l], 0, g.r1, depths[l], want[l], 0, g.r1 * z->chunk_y, P))
+                return rc;
+            data = z->data;
+            max_cy = std::max(max_cy, z->chunk_y);
         }
-        const pbx_zarr_chunks* z = &zs[l];
-        const int64_t gx = (d->size_x + z->chunk_x - 1) / z->chunk_x, gy = (d->size_y + z->chunk_y - 1) / z->chunk_y;
-        if (int rc = zarr_plan(d->size_x, z, bpp_of(d->pixel_type), in_base[l], 0, gy, depths[l], want[l], 0,
-                               gy * z->chunk_y, P))
-            return rc;
-        in_base[l + 1] = in_base[l] + ((z->offsets[gx * gy] + 15) & ~15ull);
-        in[l] = ZarrInput{z->data, z->offsets[gx * gy], in_base[l], in_base[l + 1] - in_base[l]};
-        max_cy = std::max(max_cy, z->chunk_y);
+        in_base[l + 1] = in_base[l] + ((g.used + 15) & ~15ull);
+        in[l] = ZarrInput{data, g.used, in_base[l], in_base[l + 1] - in_base[l]};
     }
     if (ensure_device(ctx)) return PBX_E_INTERNAL;
-    std::vector<Plane> ps(n);
     std::vector<ZPlane> zp(n);
     for (uint64_t k = 0; k < n; k++) {
-        const pbx_plane_desc* d = &ds[k];
-        const int bpp = bpp_of(d->pixel_type);
-        Plane& p = ps[k];
-        p.image_id = d->image_id; p.z = d->z; p.c = d->c; p.t = d->t; p.res = d->resolution;
-        p.pixel_type = d->pixel_type; p.size_x = d->size_x; p.size_y = d->size_y;
-        p.little_endian = d->byte_order == PBX_LITTLE_ENDIAN && bpp > 1;
-        p.pitch = ((int64_t)d->size_x * bpp + 255) & ~(int64_t)255;
-        p.bytes = (size_t)p.pitch * d->size_y + 256;
-        p.band_rows = d->size_y;
-        if (ts) {
-            const pbx_tiff_segments& s = ts[refs[k].layer];
-            zp[k] = ZPlane{nullptr, p.pitch, d->size_x, d->size_y, s.seg_w, s.seg_h, (uint32_t)bpp, 0, 0, 0, d->size_y};
-            continue;
-        }
-        const pbx_zarr_chunks& z = zs[refs[k].layer];
-        zp[k] = ZPlane{nullptr, p.pitch, d->size_x, d->size_y, z.chunk_x, z.chunk_y,
-                       (uint32_t)bpp, 0, zarr_fill(z.fill_bits, bpp, p.little_endian), 0, d->size_y};
+        const Plane& p = ps[k];
+        const uint32_t l = refs[k].layer;
+        const int bpp = bpp_of(p.pixel_type);
+        zp[k] = ZPlane{nullptr, p.pitch, p.size_x, p.size_y, ts ? ts.s[l].seg_w : zs[l].chunk_x,
+                       ts ? ts.s[l].seg_h : zs[l].chunk_y, (uint32_t)bpp, 0,
+                       ts ? 0 : zarr_fill(zs[l].fill_bits, bpp, p.little_endian), 0, p.size_y};
     }
     for (uint64_t k = 0; k < n; k++) {
-        if (int rc = plane_alloc(ctx, ps[k].bytes, &ps[k].dev)) {
-            const std::string msg = last_error();
-            for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
-            last_error() = msg;
-            return rc;
-        }
+        if (int rc = plane_alloc(ctx, ps[k].bytes, &ps[k].dev)) return release_planes(ctx, ps, rc);
         zp[k].dev = ps[k].dev;
     }
     for (size_t i = 0; i < sd.size(); i++)
@@ -2819,18 +2701,10 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
     int rc = e == hipSuccess ? zarr_decode_place(ctx, ctx->stream, P, zp, in, in_base[n_layers], max_cy, kernel_ms, &sd)
                              : fail(PBX_E_INTERNAL, "zarr decode: %s", hipGetErrorString(e));
     if (rc) {
-        const std::string msg = last_error();
         (void)hipStreamSynchronize(ctx->stream);
-        for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
-        last_error() = msg;
-        return rc;
+        return release_planes(ctx, ps, rc);
     }
-    if (int rc = registry_insert(ctx, ps, plane_ids)) {  // keys re-checked at insertion
-        const std::string msg = last_error();
-        for (Plane& p : ps) plane_free(ctx, p.dev, p.bytes);
-        last_error() = msg;
-        return rc;
-    }
+    if (int rc = registry_insert(ctx, ps, plane_ids)) return release_planes(ctx, ps, rc);  // keys re-checked at insertion
     return PBX_OK;
 }
 
@@ -2843,7 +2717,7 @@ int pbx_planes_register_zarr(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     std::vector<pbx_zarr_slice> refs(n);
     for (uint64_t k = 0; k < n; k++) refs[k] = pbx_zarr_slice{(uint32_t)k, 0};
     const std::vector<int32_t> depths(n, 1);
-    return register_zarr_layers(ctx, n, ds, refs.data(), n, zs, depths.data(), plane_ids, kernel_ms);
+    return register_zarr_layers(ctx, n, ds, refs.data(), n, zs, depths.data(), plane_ids, kernel_ms, TiffLayers{});
 }
 
 int pbx_planes_register_zarr_deep(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
@@ -2852,7 +2726,7 @@ int pbx_planes_register_zarr_deep(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc
     if (!ctx || !ds || !refs || !layers || !chunk_planes || !plane_ids || n == 0 || n_layers == 0)
         return fail(PBX_E_BADARG, "null argument");
     if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
-    return register_zarr_layers(ctx, n, ds, refs, n_layers, layers, chunk_planes, plane_ids, kernel_ms);
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, layers, chunk_planes, plane_ids, kernel_ms, TiffLayers{});
 }
 
 int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_tiff_segments* segs,
@@ -2862,7 +2736,8 @@ int pbx_planes_register_tiff(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds,
     std::vector<pbx_zarr_slice> refs(n);
     for (uint64_t k = 0; k < n; k++) refs[k] = pbx_zarr_slice{(uint32_t)k, 0};
     const std::vector<int32_t> depths(n, 1);
-    return register_zarr_layers(ctx, n, ds, refs.data(), n, nullptr, depths.data(), plane_ids, kernel_ms, segs);
+    return register_zarr_layers(ctx, n, ds, refs.data(), n, nullptr, depths.data(), plane_ids, kernel_ms,
+                                TiffLayers{segs, nullptr, false});
 }
 
 int pbx_planes_register_tiff_samples(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
@@ -2871,7 +2746,8 @@ int pbx_planes_register_tiff_samples(pbx_ctx* ctx, uint64_t n, const pbx_plane_d
     if (!ctx || !ds || !refs || !layers || !samples_per_pixel || !plane_ids || n == 0 || n_layers == 0)
         return fail(PBX_E_BADARG, "null argument");
     if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
-    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms, layers);
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms,
+                                TiffLayers{layers, nullptr, false});
 }
 
 int pbx_planes_register_tiff_jpeg(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
@@ -2880,20 +2756,16 @@ int pbx_planes_register_tiff_jpeg(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc
     if (!ctx || !ds || !refs || !layers || !samples_per_pixel || !jpeg || !plane_ids || n == 0 || n_layers == 0)
         return fail(PBX_E_BADARG, "null argument");
     if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
-    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms, layers, jpeg);
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms,
+                                TiffLayers{layers, jpeg, false});
 }
 
 int pbx_band_write_tiff_jpeg(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
                              int32_t samples_per_pixel, int32_t sample, const pbx_tiff_jpeg* jpeg, double* kernel_ms) {
     if (!ctx || !s || !jpeg) return fail(PBX_E_BADARG, "null argument");
-    int rc;
-    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
-    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
-    rc = band_write_tiff(ctx, q, y0, rows, s, samples_per_pixel, sample, kernel_ms, jpeg);
-    const std::string msg = last_error();
-    unpin_one(ctx, q);
-    last_error() = msg;
-    return rc;
+    return with_sparse_plane(ctx, id, [&](Plane* q) {
+        return band_write_tiff(ctx, q, y0, rows, TiffCodec{s, jpeg, false}, samples_per_pixel, sample, kernel_ms);
+    });
 }
 
 int pbx_planes_register_tiff_j2k(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
@@ -2902,21 +2774,16 @@ int pbx_planes_register_tiff_j2k(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc*
     if (!ctx || !ds || !refs || !layers || !samples_per_pixel || !plane_ids || n == 0 || n_layers == 0)
         return fail(PBX_E_BADARG, "null argument");
     if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
-    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms, layers, nullptr,
-                                true);
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, samples_per_pixel, plane_ids, kernel_ms,
+                                TiffLayers{layers, nullptr, true});
 }
 
 int pbx_band_write_tiff_j2k(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
                             int32_t samples_per_pixel, int32_t sample, double* kernel_ms) {
     if (!ctx || !s) return fail(PBX_E_BADARG, "null argument");
-    int rc;
-    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
-    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
-    rc = band_write_tiff(ctx, q, y0, rows, s, samples_per_pixel, sample, kernel_ms, nullptr, true);
-    const std::string msg = last_error();
-    unpin_one(ctx, q);
-    last_error() = msg;
-    return rc;
+    return with_sparse_plane(ctx, id, [&](Plane* q) {
+        return band_write_tiff(ctx, q, y0, rows, TiffCodec{s, nullptr, true}, samples_per_pixel, sample, kernel_ms);
+    });
 }
 
 int pbx_plane_register_zarr(pbx_ctx* ctx, const pbx_plane_desc* d, const pbx_zarr_chunks* z,
@@ -2927,14 +2794,7 @@ int pbx_plane_register_zarr(pbx_ctx* ctx, const pbx_plane_desc* d, const pbx_zar
 int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
                              int32_t depth, int32_t slice, double* kernel_ms) {
     if (!ctx || !z) return fail(PBX_E_BADARG, "null argument");
-    int rc;
-    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
-    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
-    rc = band_write_zarr(ctx, q, y0, rows, z, depth, slice, kernel_ms);
-    const std::string msg = last_error();
-    unpin_one(ctx, q);
-    last_error() = msg;
-    return rc;
+    return with_sparse_plane(ctx, id, [&](Plane* q) { return band_write_zarr(ctx, q, y0, rows, z, depth, slice, kernel_ms); });
 }
 
 int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
@@ -2945,14 +2805,9 @@ int pbx_band_write_zarr(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, con
 int pbx_band_write_tiff_sample(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
                                int32_t samples_per_pixel, int32_t sample, double* kernel_ms) {
     if (!ctx || !s) return fail(PBX_E_BADARG, "null argument");
-    int rc;
-    Plane* q = pin_id(ctx, id, 1u << PS_READY, &rc);
-    if (!q) return rc == PBX_E_EXISTS ? fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id) : rc;
-    rc = band_write_tiff(ctx, q, y0, rows, s, samples_per_pixel, sample, kernel_ms);
-    const std::string msg = last_error();
-    unpin_one(ctx, q);
-    last_error() = msg;
-    return rc;
+    return with_sparse_plane(ctx, id, [&](Plane* q) {
+        return band_write_tiff(ctx, q, y0, rows, TiffCodec{s, nullptr, false}, samples_per_pixel, sample, kernel_ms);
+    });
 }
 
 int pbx_band_write_tiff(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,

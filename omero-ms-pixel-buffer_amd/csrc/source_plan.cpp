@@ -1164,6 +1164,92 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
     return PBX_OK;
 }
 
+// ------------------------------------------------------------------ one codec, one launch
+int tiff_codec_check(const TiffCodec& c, int32_t pixel_type, int32_t spp, int64_t sample, uint64_t plane_label) {
+    if (int rc = c.j2k    ? tiff_j2k_check(c.s, pixel_type, spp)
+                 : c.jpeg ? tiff_jpeg_check(c.s, c.jpeg, pixel_type, spp)
+                          : tiff_segments_check(c.s))
+        return rc;
+    if (c.s->predictor == 2 && (pixel_type == PBX_FLOAT || pixel_type == PBX_DOUBLE))
+        return fail(PBX_E_BADARG, "plane %llu: predictor 2 on floating-point samples", (unsigned long long)plane_label);
+    if (int rc = tiff_fp_predictor_check(c.s, pixel_type)) return rc;
+    return tiff_samples_check(spp, sample, bpp_of(pixel_type));
+}
+
+int tiff_codec_plan(const TiffCodec& c, int32_t size_x, int32_t size_y, int bpp, bool big_endian, uint64_t in_base,
+                    uint32_t plane, ZarrPlan& P, bool band, int64_t sr0, int64_t sr1, int spp, uint32_t dst) {
+    if (c.j2k) return tiff_j2k_plan(size_x, size_y, bpp, c.s, in_base, P, sr0, sr1, spp, dst);
+    if (c.jpeg) return tiff_jpeg_plan(size_x, size_y, c.s, c.jpeg, in_base, P, sr0, sr1, spp, dst);
+    return tiff_plan(size_x, size_y, bpp, big_endian, c.s, in_base, plane, P, nullptr, band, sr0, sr1, spp, dst);
+}
+
+SourceGrid source_grid(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t y0, int32_t rows) {
+    const int64_t gx = s->tiled ? ((int64_t)size_x + s->seg_w - 1) / s->seg_w : 1;
+    const int64_t r0 = y0 / s->seg_h, r1 = ((int64_t)y0 + (rows < 0 ? size_y : rows) + s->seg_h - 1) / s->seg_h;
+    return SourceGrid{gx, r0, r1, s->offsets[gx * (r1 - r0)]};
+}
+
+SourceGrid source_grid(const pbx_zarr_chunks* z, int32_t size_x, int32_t size_y, int32_t y0, int32_t rows) {
+    const int64_t gx = ((int64_t)size_x + z->chunk_x - 1) / z->chunk_x;
+    const int64_t r0 = y0 / z->chunk_y, r1 = ((int64_t)y0 + (rows < 0 ? size_y : rows) + z->chunk_y - 1) / z->chunk_y;
+    return SourceGrid{gx, r0, r1, z->offsets[gx * (r1 - r0)]};
+}
+
+LaunchLayout::LaunchLayout(const ZarrPlan& P, uint32_t crc_split) : j2segs(P.j2segs) {
+    for (uint32_t k = 0; k < ZS_NKINDS; k++) {
+        counts[k] = (uint32_t)P.kind[k].size();
+        streams.insert(streams.end(), P.kind[k].begin(), P.kind[k].end());
+    }
+    for (uint32_t k = 0; k < ZK_NPOLY; k++) {
+        ck_first[k] = (uint32_t)checks.size();
+        for (const ZCheck& c : P.checks[k]) if (c.len < crc_split) checks.push_back(c);
+        ck_wave[k] = (uint32_t)checks.size() - ck_first[k];
+        for (const ZCheck& c : P.checks[k]) if (c.len >= crc_split) checks.push_back(c);
+        ck_n[k] = (uint32_t)checks.size() - ck_first[k];
+    }
+    j2chroma = (uint32_t)(j2segs.end() - std::stable_partition(j2segs.begin(), j2segs.end(), [](const TJ2Seg& u) {
+                              return !(u.rct & J2_SEG_CHROMA);
+                          }));
+    j2meta = (sizeof(J2Code) + sizeof(J2Walk)) * P.j2blocks.size() + sizeof(J2Contrib) * P.j2cons + 4 * P.j2nodes;
+    nstreams = (uint32_t)streams.size();
+    nchecks = (uint32_t)checks.size();
+    njpeg = (uint32_t)P.jstreams.size();
+    nj2 = (uint32_t)P.j2streams.size();
+    err_streams = 0;
+    err_checks = err_streams + nstreams;
+    err_jpeg = err_checks + nchecks;
+    err_j2k = err_jpeg + njpeg;
+    nerr = err_j2k + nj2;
+}
+
+int launch_errors(const LaunchLayout& L, const uint32_t* err) {
+    for (uint32_t s = 0; s < L.nstreams; s++)
+        if (const uint32_t code = err[L.err_streams + s]) {
+            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd", "gzip", "lzw"};
+            uint32_t k = 0, first = 0;
+            while (s >= first + L.counts[k]) first += L.counts[k++];
+            return fail(PBX_E_BADARG, "corrupt chunk stream %u (%s, decoder code %u)", s, names[k], code);
+        }
+    for (uint32_t s = 0; s < L.nchecks; s++)
+        if (err[L.err_checks + s]) {
+            const ZCheck& c = L.checks[s];
+            return fail(PBX_E_BADARG, "chunk checksum mismatch: the %s of %u bytes is not 0x%08x",
+                        c.poly == ZK_CRC32C ? "crc32c" : "gzip CRC-32", c.len, c.expect);
+        }
+    for (uint32_t s = 0; s < L.njpeg; s++)
+        if (const uint32_t code = err[L.err_jpeg + s]) {
+            static const char* why[6] = {"", "entropy data ends before the last MCU", "a code that is in no table",
+                                         "a run that passes coefficient 63", "a DC size > 11 or an AC size > 10",
+                                         "a restart marker missing, out of sequence or misplaced"};
+            return fail(PBX_E_BADARG, "corrupt segment stream %u (jpeg, decoder code %u: %s)", s, code,
+                        code < 6 ? why[code] : "?");
+        }
+    for (uint32_t s = 0; s < L.nj2; s++)
+        if (const uint32_t code = err[L.err_j2k + s])
+            return fail(PBX_E_BADARG, "corrupt segment stream %u (j2k, decoder code %u)", s, code);
+    return PBX_OK;
+}
+
 }  // namespace pbx
 
 // ------------------------------------------------------------------ test hooks (include/pbx.h)

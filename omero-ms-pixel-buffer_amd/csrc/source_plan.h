@@ -100,4 +100,52 @@ int tiff_j2k_check(const pbx_tiff_segments* s, int32_t pixel_type, int32_t spp);
 int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segments* s, uint64_t in_base, ZarrPlan& P,
                   int64_t sr0, int64_t sr1, int spp, uint32_t dst, uint64_t* packets = nullptr);
 
+// How a pbx_tiff_segments is compressed, as the entry point that took it says: its streams are
+// JPEG 2000 codestreams (j2k), JPEG streams with the tables of `jpeg`, or else what
+// s->compression names.
+struct TiffCodec {
+    const pbx_tiff_segments* s;
+    const pbx_tiff_jpeg* jpeg;
+    bool j2k;
+};
+// The codec's own check (tiff_j2k_check, tiff_jpeg_check or tiff_segments_check), then what holds
+// for all three: no Predictor = 2 on float / double, tiff_fp_predictor_check, tiff_samples_check.
+// `plane_label` is the number messages call the plane by.
+int tiff_codec_check(const TiffCodec& c, int32_t pixel_type, int32_t spp, int64_t sample, uint64_t plane_label);
+// tiff_j2k_plan, tiff_jpeg_plan or tiff_plan of segment rows [sr0, sr1) (sr1 < 0: all) with the
+// arguments each takes; `dst` is the layer's entry in the launch's TSplitDst table.
+int tiff_codec_plan(const TiffCodec& c, int32_t size_x, int32_t size_y, int bpp, bool big_endian, uint64_t in_base,
+                    uint32_t plane, ZarrPlan& P, bool band, int64_t sr0, int64_t sr1, int spp, uint32_t dst);
+
+// The segments (chunks) that cover rows [y0, y0 + rows) (rows < 0: every row) of a plane of
+// size_x x size_y: gx across, rows [r0, r1) of the grid, and the bytes those gx * (r1 - r0) streams
+// take in `data`, which holds them alone (offsets[gx * (r1 - r0)]).
+struct SourceGrid {
+    int64_t gx, r0, r1;
+    uint64_t used;
+};
+SourceGrid source_grid(const pbx_tiff_segments* s, int32_t size_x, int32_t size_y, int32_t y0 = 0, int32_t rows = -1);
+SourceGrid source_grid(const pbx_zarr_chunks* z, int32_t size_x, int32_t size_y, int32_t y0 = 0, int32_t rows = -1);
+
+// What one decode launch uploads of a finished plan and where its decoders report: the tables
+// that are not the plan's own vectors, and the layout of err[].
+struct LaunchLayout {
+    uint32_t counts[ZS_NKINDS];  // streams by kind
+    std::vector<ZStream> streams;  // P.kind[0], P.kind[1], ... one after another
+    // checks by polynomial, and within one the ranges shorter than the CRC split length (a wave
+    // each) before the others (a workgroup each): polynomial k has ck_n[k] checks from
+    // ck_first[k], the first ck_wave[k] of them short
+    std::vector<ZCheck> checks;
+    uint32_t ck_first[ZK_NPOLY], ck_wave[ZK_NPOLY], ck_n[ZK_NPOLY];
+    std::vector<TJ2Seg> j2segs;  // P.j2segs, those with J2_SEG_CHROMA after the others (stable)
+    uint32_t j2chroma;           // how many those are
+    uint64_t j2meta;             // bytes of the J2Code, J2Walk and J2Contrib tables and the tag-tree nodes
+    // err[]: a dword per stream, per check (in `checks` order), per JPEG stream and per JPEG 2000 stream
+    uint32_t nstreams, nchecks, njpeg, nj2;
+    uint32_t err_streams, err_checks, err_jpeg, err_j2k, nerr;
+    LaunchLayout(const ZarrPlan& P, uint32_t crc_split);
+};
+// The first non-zero entry of a launch's err[] (nerr dwords) as the 400 it stands for, or PBX_OK.
+int launch_errors(const LaunchLayout& L, const uint32_t* err);
+
 }  // namespace pbx

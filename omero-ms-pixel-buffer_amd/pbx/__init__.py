@@ -115,6 +115,39 @@ def _fill_tiff_jpeg(j: "PbxTiffJpeg", jpeg: Mapping) -> object:
     return buf
 
 
+def _fill_plane_desc(d: "PbxPlaneDesc", spec: Mapping) -> None:
+    """pbx_plane_desc from a plane spec (image_id, z, c, t, pixel_type, size_x, size_y[, level,
+    big_endian]); it points at nothing."""
+    d.image_id, d.z, d.c, d.t = spec["image_id"], spec["z"], spec["c"], spec["t"]
+    d.resolution = spec.get("level", 0)
+    d.pixel_type, d.size_x, d.size_y = spec["pixel_type"], spec["size_x"], spec["size_y"]
+    d.byte_order = BIG_ENDIAN if spec.get("big_endian", True) else LITTLE_ENDIAN
+
+
+def _fill_tiff_segments(s: "PbxTiffSegments", spec: Mapping) -> list:
+    """pbx_tiff_segments from a spec (seg_w, seg_h, tiled, compression, segments[, predictor,
+    flags]); returns the arrays the struct points into, to be kept alive over the call."""
+    seg = spec["segments"]
+    data, offsets = seg if isinstance(seg, tuple) else pack_chunks(seg)
+    s.seg_w, s.seg_h, s.tiled = spec["seg_w"], spec["seg_h"], 1 if spec["tiled"] else 0
+    s.compression, s.predictor, s.flags = spec["compression"], spec.get("predictor", 1), spec.get("flags", 0)
+    s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
+    return [offsets, data]
+
+
+def _fill_zarr_chunks(zc: "PbxZarrChunks", spec: Mapping) -> list:
+    """pbx_zarr_chunks from a spec (chunk_x, chunk_y, codec, chunks[, fill_bits, crc32c]); returns
+    the arrays the struct points into, to be kept alive over the call."""
+    if spec["codec"] not in ZARR_CODECS:
+        raise PbxError(400, "unsupported Zarr compressor %r" % (spec["codec"],))
+    chunks = spec["chunks"]
+    data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
+    zc.chunk_x, zc.chunk_y, zc.codec = spec["chunk_x"], spec["chunk_y"], ZARR_CODECS[spec["codec"]]
+    zc.flags = ZARR_F_CRC32C if spec.get("crc32c") else 0
+    zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, spec.get("fill_bits", 0)
+    return [offsets, data]
+
+
 class PbxZarrSlice(ctypes.Structure):
     _fields_ = [("layer", ctypes.c_uint32), ("slice", ctypes.c_uint32)]
 
@@ -1770,20 +1803,8 @@ class PixelsService:
         zcs = (PbxZarrChunks * n)()
         keep = []
         for k, p in enumerate(planes):
-            if p["codec"] not in ZARR_CODECS:
-                raise PbxError(400, "unsupported Zarr compressor %r" % (p["codec"],))
-            chunks = p["chunks"]
-            data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
-            keep += [offsets, data]
-            d = descs[k]
-            d.image_id, d.z, d.c, d.t = p["image_id"], p["z"], p["c"], p["t"]
-            d.resolution = p.get("level", 0)
-            d.pixel_type, d.size_x, d.size_y = p["pixel_type"], p["size_x"], p["size_y"]
-            d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
-            zc = zcs[k]
-            zc.chunk_x, zc.chunk_y, zc.codec = p["chunk_x"], p["chunk_y"], ZARR_CODECS[p["codec"]]
-            zc.flags = ZARR_F_CRC32C if p.get("crc32c") else 0
-            zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, p.get("fill_bits", 0)
+            keep += _fill_zarr_chunks(zcs[k], p)
+            _fill_plane_desc(descs[k], p)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
         _check(lib().pbx_planes_register_zarr(self._h, n, descs, zcs, ids, ms))
@@ -1804,24 +1825,12 @@ class PixelsService:
         depths = (ctypes.c_int32 * max(nl, 1))()
         keep = []
         for k, p in enumerate(planes):
-            d = descs[k]
-            d.image_id, d.z, d.c, d.t = p["image_id"], p["z"], p["c"], p["t"]
-            d.resolution = p.get("level", 0)
-            d.pixel_type, d.size_x, d.size_y = p["pixel_type"], p["size_x"], p["size_y"]
-            d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
+            _fill_plane_desc(descs[k], p)
             if not (0 <= refs[k][0] < 2 ** 32 and 0 <= refs[k][1] < 2 ** 32):
                 raise PbxError(400, "plane %d: bad layer or slice %r" % (k, tuple(refs[k])))
             rf[k].layer, rf[k].slice = refs[k]
         for k, l in enumerate(layers):
-            if l["codec"] not in ZARR_CODECS:
-                raise PbxError(400, "unsupported Zarr compressor %r" % (l["codec"],))
-            chunks = l["chunks"]
-            data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
-            keep += [offsets, data]
-            zc = zcs[k]
-            zc.chunk_x, zc.chunk_y, zc.codec = l["chunk_x"], l["chunk_y"], ZARR_CODECS[l["codec"]]
-            zc.flags = ZARR_F_CRC32C if l.get("crc32c") else 0
-            zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, l.get("fill_bits", 0)
+            keep += _fill_zarr_chunks(zcs[k], l)
             depths[k] = l.get("chunk_planes", 1)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
@@ -1928,18 +1937,8 @@ class PixelsService:
         sgs = (PbxTiffSegments * n)()
         keep = []
         for k, p in enumerate(planes):
-            seg = p["segments"]
-            data, offsets = seg if isinstance(seg, tuple) else pack_chunks(seg)
-            keep += [offsets, data]
-            d = descs[k]
-            d.image_id, d.z, d.c, d.t = p["image_id"], p["z"], p["c"], p["t"]
-            d.resolution = p.get("level", 0)
-            d.pixel_type, d.size_x, d.size_y = p["pixel_type"], p["size_x"], p["size_y"]
-            d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
-            s = sgs[k]
-            s.seg_w, s.seg_h, s.tiled = p["seg_w"], p["seg_h"], 1 if p["tiled"] else 0
-            s.compression, s.predictor, s.flags = p["compression"], p.get("predictor", 1), p.get("flags", 0)
-            s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
+            keep += _fill_tiff_segments(sgs[k], p)
+            _fill_plane_desc(descs[k], p)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
         _check(lib().pbx_planes_register_tiff(self._h, n, descs, sgs, ids, ms))
@@ -1966,24 +1965,14 @@ class PixelsService:
                                % (k, planes.index(layers[l])))
             if not (0 <= sample < 2 ** 32):
                 raise PbxError(400, "plane %d: bad sample %r" % (k, sample))
-            d = descs[k]
-            d.image_id, d.z, d.c, d.t = p["image_id"], p["z"], p["c"], p["t"]
-            d.resolution = p.get("level", 0)
-            d.pixel_type, d.size_x, d.size_y = p["pixel_type"], p["size_x"], p["size_y"]
-            d.byte_order = BIG_ENDIAN if p.get("big_endian", True) else LITTLE_ENDIAN
+            _fill_plane_desc(descs[k], p)
             rf[k].layer, rf[k].slice = l, sample
         nl = len(layers)
         sgs = (PbxTiffSegments * nl)()
         spps = (ctypes.c_int32 * nl)()
         keep = []
         for l, p in enumerate(layers):
-            seg = p["segments"]
-            data, offsets = seg if isinstance(seg, tuple) else pack_chunks(seg)
-            keep += [offsets, data]
-            s = sgs[l]
-            s.seg_w, s.seg_h, s.tiled = p["seg_w"], p["seg_h"], 1 if p["tiled"] else 0
-            s.compression, s.predictor, s.flags = p["compression"], p.get("predictor", 1), p.get("flags", 0)
-            s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
+            keep += _fill_tiff_segments(sgs[l], p)
             spps[l] = p.get("samples_per_pixel", 1)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
@@ -2145,19 +2134,16 @@ class PixelsService:
         offsets) pair).  codec and crc32c as register_zarr_plane.  With timing=True returns the decode /
         placement kernels' device ms.  chunk_planes > 1: the chunks hold that many planes and
         the rows are those of slice `slice` of each (pbx_band_write_zarr_deep)."""
-        if codec not in ZARR_CODECS:
-            raise PbxError(400, "unsupported Zarr compressor %r" % (codec,))
-        data, offsets = chunks if isinstance(chunks, tuple) else pack_chunks(chunks)
         zc = PbxZarrChunks()
-        zc.chunk_x, zc.chunk_y, zc.codec = chunk_x, chunk_y, ZARR_CODECS[codec]
-        zc.flags = ZARR_F_CRC32C if crc32c else 0
-        zc.data, zc.offsets, zc.fill_bits = data.ctypes.data, offsets.ctypes.data, fill_bits
+        kept = _fill_zarr_chunks(zc, dict(chunk_x=chunk_x, chunk_y=chunk_y, codec=codec, chunks=chunks,
+                                          fill_bits=fill_bits, crc32c=crc32c))
         ms = (ctypes.c_double * 2)()
         if chunk_planes == 1 and slice == 0:
             _check(lib().pbx_band_write_zarr(self._h, plane_id, y0, rows, ctypes.byref(zc), ms))
         else:
             _check(lib().pbx_band_write_zarr_deep(self._h, plane_id, y0, rows, ctypes.byref(zc),
                                                   chunk_planes, slice, ms))
+        del kept
         return (ms[0], ms[1]) if timing else None
 
     def band_write_tiff(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
@@ -2173,11 +2159,9 @@ class PixelsService:
         per pixel, of which only `sample` is written (pbx_band_write_tiff_sample).
         flags: a spec's `flags` (TIFF_F_J2K_PACKETS on JPEG 2000 segments).
         With timing=True returns the decoders' and the placement's device ms."""
-        data, offsets = segments if isinstance(segments, tuple) else pack_chunks(segments)
         s = PbxTiffSegments()
-        s.seg_w, s.seg_h, s.tiled = seg_w, seg_h, 1 if tiled else 0
-        s.compression, s.predictor, s.flags = compression, predictor, flags
-        s.data, s.offsets = data.ctypes.data, offsets.ctypes.data
+        kept = _fill_tiff_segments(s, dict(seg_w=seg_w, seg_h=seg_h, tiled=tiled, compression=compression,
+                                           predictor=predictor, flags=flags, segments=segments))
         ms = (ctypes.c_double * 2)()
         if j2k:  # JPEG 2000 segments (compression TIFF_J2K): a spec's `j2k`
             _check(lib().pbx_band_write_tiff_j2k(self._h, plane_id, y0, rows, ctypes.byref(s), samples_per_pixel,
@@ -2193,6 +2177,7 @@ class PixelsService:
         else:
             _check(lib().pbx_band_write_tiff_sample(self._h, plane_id, y0, rows, ctypes.byref(s),
                                                     samples_per_pixel, sample, ms))
+        del kept
         return [ms[0], ms[1]] if timing else None
 
     def band_abort(self, plane_id: int, y0: int) -> None:
