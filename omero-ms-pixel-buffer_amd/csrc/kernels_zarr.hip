@@ -178,6 +178,9 @@ __global__ __launch_bounds__(256) void k_zarr_lz4(const ZStream* __restrict__ st
             }
         }
         if (!flush_batch()) { bad = 6; break; }
+        // (the test above saw op without the pending batch; from here on op <= olen holds, which
+        // OutRing::match's own bound relies on)
+        if (lln > o.olen - o.op) { bad = 3; break; }
         for (uint32_t c = 0; c < lln; c += 64) {
             const uint32_t nb = lln - c < 64 ? lln - c : 64;
             const uint32_t v = win.lane_byte(ls + c);

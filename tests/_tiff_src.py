@@ -81,12 +81,27 @@ def lzw_encode(data, clear_every=None, clear_at=(), eoi=True, leading_clear=True
     return bits.done()
 
 
+def lzw_pack(codes, leading_clear=True):
+    """The stream of the raw code values `codes`, written as they are (after a Clear, unless
+    leading_clear is False), each at the width of its place in its run (the early change); a
+    Clear among them starts a new run.  No EOI is added."""
+    bits, j = _Bits(), 0
+    for v in ([CLEAR] if leading_clear else []) + list(codes):
+        bits.put(v, code_width(j))
+        j = 0 if v == CLEAR else j + 1
+    return bits.done()
+
+
+RUN_MAX = 3838  # codes of a run: the last one defines entry 4095
+
+
 def lzw_decode(stream, expect=None, widths=None):
     """Table-based decoder (the textbook form, not the library's).  Stops at EOI, at the end of
     the input or once `expect` bytes are out.  widths (a list) receives every code's width.
-    Raises ValueError for a code beyond the next free one."""
+    Raises ValueError for a code beyond the next free one, and for a code other than Clear or EOI
+    after the RUN_MAX codes that fill the table."""
     stream = bytes(stream)
-    out, table, nxt, nbits, old = bytearray(), {}, FIRST, 9, None
+    out, table, nxt, nbits, old, run = bytearray(), {}, FIRST, 9, None, 0
     pos, total = 0, len(stream) * 8
     while pos + nbits <= total and (expect is None or len(out) < expect):
         q, r = pos >> 3, pos & 7
@@ -96,10 +111,13 @@ def lzw_decode(stream, expect=None, widths=None):
         if widths is not None:
             widths.append(nbits)
         if code == CLEAR:
-            table, nxt, nbits, old = {}, FIRST, 9, None
+            table, nxt, nbits, old, run = {}, FIRST, 9, None, 0
             continue
         if code == EOI:
             break
+        if run >= RUN_MAX:
+            raise ValueError("LZW: no Clear after the %d codes that fill the table" % RUN_MAX)
+        run += 1
         if old is None:
             if code > 255:
                 raise ValueError("LZW: code %d right after a Clear" % code)

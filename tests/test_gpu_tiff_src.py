@@ -276,6 +276,46 @@ def test_corrupt_streams_register_nothing(service, case):
         service.release_plane(keep)
 
 
+# k_tiff_lzw's refusal codes (kernels_tiff_src.hip): 1 fewer bytes than dlen, 2 a code beyond the
+# next free one, 3 a string past dlen, 4 no Clear before the table is full.  Raw code values
+# after a Clear; the plane is one strip of `n` bytes.
+def _lzw_refusals():
+    lit = [int(v) for v in smooth(4000, 9)]
+    return {
+        "EOI before dlen": (T.lzw_pack([65, 66, 67, T.EOI]), 300, 1),
+        # code 2 of a round names entry 10, which code 11 of the same round would define
+        "code above the next free one, in the round that would define it":
+            (T.lzw_pack(lit[:2] + [T.FIRST + 10] + lit[3:100] + [T.EOI]), 300, 2),
+        # code 70, in the second round of 64, names entry 100
+        "code above the next free one, in a later round":
+            (T.lzw_pack(lit[:70] + [T.FIRST + 100] + lit[71:200] + [T.EOI]), 300, 2),
+        # entry 258 = "AB": the fifth code's two bytes end one past the five of the strip
+        "string past dlen mid-round": (T.lzw_pack([65, 66, 67, 68, T.FIRST, T.EOI]), 5, 3),
+        "3838 codes without a Clear and then no Clear": (T.lzw_pack(lit[:T.RUN_MAX + 2] + [T.EOI]), 4000, 4),
+    }
+
+
+@pytest.mark.parametrize("case", list(_lzw_refusals()))
+def test_lzw_refusal_names_its_decoder_code(service, case):
+    stream, n, code = _lzw_refusals()[case]
+    # the table-based decoder refuses the same streams: an error, or fewer bytes than the strip;
+    # code 3 is the exception: it decodes the whole string and merely cuts it at `expect`
+    try:
+        short = len(T.lzw_decode(stream, n)) < n
+    except ValueError:
+        short = True
+    assert short == (code != 3)
+    if code == 3:
+        assert len(T.lzw_decode(stream)) > n
+    image = next(_ids)
+    with pytest.raises(pbx.PbxError) as e:
+        service.register_tiff_planes([u8_plane(image, n, 1, [stream])])
+    assert e.value.status == 400 and "(lzw, decoder code %d)" % code in str(e.value), str(e.value)
+    assert service.lookup_plane(image, 0, 0, 0) is None
+    a = smooth(n, 10).reshape(1, n)
+    check_u8(service, a, [T.lzw_encode(a.tobytes())])
+
+
 # ------------------------------------------------------- TiffSource behind the handler
 def test_tiff_source_behind_the_handler():
     entry = next(e for e in FILES if e["file"].startswith("pyramid"))

@@ -117,6 +117,21 @@ def test_width_rule():
     assert [w for _, w in codes] == widths[:len(codes)]
 
 
+def test_raw_code_packer_and_the_full_table():
+    """lzw_pack writes the encoder's own codes to the encoder's own bytes (two runs, all four
+    widths); the decoder takes the RUN_MAX codes that fill the table and refuses a further one."""
+    data = np.random.default_rng(1).integers(0, 256, 5000, dtype=np.uint8).tobytes()
+    codes = []
+    s = T.lzw_encode(data, codes_out=codes)
+    assert T.lzw_pack([c for c, _ in codes[1:]]) == s
+    assert T.lzw_pack([c for c, _ in codes], leading_clear=False) == s
+    lit = list(data[:T.RUN_MAX + 1])
+    assert T.lzw_decode(T.lzw_pack(lit[:T.RUN_MAX] + [T.EOI])) == data[:T.RUN_MAX]
+    assert T.lzw_decode(T.lzw_pack(lit[:T.RUN_MAX] + [T.CLEAR] + lit[:3] + [T.EOI])) == data[:T.RUN_MAX] + data[:3]
+    with pytest.raises(ValueError, match="no Clear"):
+        T.lzw_decode(T.lzw_pack(lit + [T.EOI]))
+
+
 def test_predict2_wraps():
     a = np.array([[0, 65535, 1, 0]], ">u2")
     d = T.predict2(a)
