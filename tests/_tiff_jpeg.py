@@ -244,25 +244,29 @@ def _idct1(i):
             tmp10 - tmp3]
 
 
-def idct_islow(coefs):
+def idct_islow(coefs, exempt=None):
     """jidctint.c on an int64 array (..., 64) of dequantised coefficients: uint8 samples (..., 8,
     8).  Asserts the condition under which libjpeg's builds agree: every sample lies in [-512, 511]
-    before the level shift and the clamp."""
+    before the level shift and the clamp.  exempt: None, or a bool array coefs.shape[:-1] of blocks
+    the assertion leaves out (blocks no sample of which is ever placed: _tiff_jpeg_frames.py)."""
     b = coefs.reshape(coefs.shape[:-1] + (8, 8))
     cols = _idct1([b[..., r, :] for r in range(8)])
     ws = np.stack([(x + (1 << 10)) >> 11 for x in cols], axis=-2)
     rows = _idct1([ws[..., :, c] for c in range(8)])
     out = np.stack([(x + (1 << 17)) >> 18 for x in rows], axis=-1)
-    assert out.min() >= -512 and out.max() <= 511, "IDCT output %d .. %d leaves [-512, 511]" % (out.min(), out.max())
+    held = out if exempt is None else out[~np.asarray(exempt, bool)]
+    assert held.size == 0 or (held.min() >= -512 and held.max() <= 511), \
+        "IDCT output %d .. %d leaves [-512, 511]" % (held.min(), held.max())
     return np.clip(out + 128, 0, 255).astype(np.uint8)
 
 
-def component_planes(data, tables=None):
-    """(header, [uint8 plane per component at its own resolution, padded to whole MCUs])."""
+def component_planes(data, tables=None, exempt=None):
+    """(header, [uint8 plane per component at its own resolution, padded to whole MCUs]).  exempt:
+    None, or per component a bool array (block rows, block cols) for idct_islow."""
     H, coefs = decode_coefficients(data, tables)
     planes = []
-    for c in coefs:
-        px = idct_islow(c)  # (by, bx, 8, 8)
+    for k, c in enumerate(coefs):
+        px = idct_islow(c, None if exempt is None else exempt[k])  # (by, bx, 8, 8)
         planes.append(px.transpose(0, 2, 1, 3).reshape(c.shape[0] * 8, c.shape[1] * 8))
     return H, planes
 
@@ -306,10 +310,10 @@ def ycc_to_rgb(y, cb, cr):
     return np.clip(np.stack([r, g, b], axis=-1), 0, 255).astype(np.uint8)
 
 
-def decode(data, tables=None, ycbcr=True):
+def decode(data, tables=None, ycbcr=True, exempt=None):
     """A segment as the GPU stores it: (h, w) for one component, else (h, w, 3): converted to RGB
     with `ycbcr` (PhotometricInterpretation 6), else the components as they are."""
-    H, planes = component_planes(data, tables)
+    H, planes = component_planes(data, tables, exempt)
     w, h = H["width"], H["height"]
     if len(planes) == 1:
         return planes[0][:h, :w]
