@@ -393,10 +393,15 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * (PlanarConfiguration 1) through pbx_planes_register_tiff_samples / pbx_band_write_tiff_sample,
  * which split them on the GPU (k_tiff_split_place); planar ones (PlanarConfiguration 2) are
  * single-sample segments already and go through the calls below.
+ * Bit-packed samples (BitsPerSample 1 .. 7 and 9 .. 15: masks, 4-bit gray, 10- / 12- / 14-bit
+ * camera data), PackBits segments (Compression 32773) and FillOrder 2 go through the
+ * pbx_*_tiff_packed calls further down and through no other: the calls here keep answering 400 for
+ * compression 32773, and take whole-byte samples only.
  * Not supported (400 by the caller or here): SamplesPerPixel > 4, Predictor 3 on integer or
- * chunky multi-sample (RGB float) data, half-precision samples, FillOrder 2, pre-6.0 (LSB-first)
- * LZW streams, PackBits / LZMA / LERC / WebP / JPEG XR and other compressions, CMYK /
- * palette colour, sub-byte or 12-bit samples.  JPEG 2000, lossless (the reversible 5/3 path) and
+ * chunky multi-sample (RGB float) data, half-precision samples, pre-6.0 (LSB-first)
+ * LZW streams, CCITT / Group 4 / LZMA / LERC / WebP / JPEG XR and other compressions, CMYK /
+ * palette colour, WhiteIsZero inversion, Predictor 2 on bit-packed samples, samples that differ
+ * in width.  JPEG 2000, lossless (the reversible 5/3 path) and
  * lossy (the irreversible 9/7 path, "JPEG-2000 Lossy", Aperio's 33003 / 33005), goes through the
  * pbx_*_tiff_j2k calls further down and through no other; Aperio's habit of YCbCr components
  * outside the codestream is undone only where the caller says so (PBX_TIFF_F_J2K_YCBCR; without it
@@ -409,6 +414,7 @@ int pbx_band_write_zarr_deep(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_
  * The JNI shim does not wrap these calls (as the deep Zarr calls). */
 enum pbx_tiff_compression { PBX_TIFF_JPEG = 7 /* through the pbx_*_tiff_jpeg calls only */,
                             PBX_TIFF_J2K = 34712 /* through the pbx_*_tiff_j2k calls only */,
+                            PBX_TIFF_PACKBITS = 32773 /* through the pbx_*_tiff_packed calls only */,
                             PBX_TIFF_NONE = 1, PBX_TIFF_LZW = 5, PBX_TIFF_DEFLATE = 8, PBX_TIFF_ZSTD = 50000 };
 /* pbx_tiff_segments.flags.  J2K_PACKETS: the full packet structure of a JPEG 2000 codestream --
  * 1 .. 64 quality layers, any precinct sizes, SOP and EPH markers (see the JPEG 2000 calls below).
@@ -622,6 +628,49 @@ int pbx_planes_register_tiff_j2k(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc*
 int pbx_band_write_tiff_j2k(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                             const pbx_tiff_segments* segs, int32_t samples_per_pixel, int32_t sample,
                             double* kernel_ms);
+/* Bit-packed samples, PackBits and FillOrder 2 (DESIGN.md §10b "packed samples and PackBits").
+ * A segment row is a bit stream of seg_w * S samples of `bits` bits each (1 .. 16), most
+ * significant bit first in II and MM files alike, padded to a whole byte: ceil(seg_w * S * bits
+ * / 8) bytes a row, and an uncompressed segment is its rows times that.  With fill_order 2 the
+ * bits of every byte are reversed first (TIFF 6.0 FillOrder).  Values are stored unscaled, as
+ * Bio-Formats hands them to the reference: bits 1 .. 8 on an 8-bit integer plane, 9 .. 16 on a
+ * 16-bit one, in the plane's byte order (descs[k].byte_order; 16-bit samples are whole bytes in
+ * the file's order and keep it, so give the file's as in the other TIFF calls).  Sample i of a
+ * row is component i % S of pixel i / S and goes to that component's plane
+ * (k_tiff_unpack_place: one pass from the segment into up to four planes, tile padding and rows
+ * outside the band clipped).  Compression is 1, 5, 8, 50000 as in pbx_planes_register_tiff, or
+ * PBX_TIFF_PACKBITS (TIFF 6.0 section 9; k_tiff_packbits, one wave a segment: runs may cross
+ * rows, bytes after the segment's last row are not read).  With bits 8 or 16 the placement is a
+ * plain one: that is how PackBits files of ordinary samples are loaded. */
+typedef struct pbx_tiff_packed {
+    int32_t bits;               /* BitsPerSample, 1 .. 16 */
+    int32_t fill_order;         /* 1 (MSB first), 2 (the bits of every byte reversed) */
+    int32_t samples_per_pixel;  /* S, 1 .. 4: chunky samples of a segment row */
+    int32_t sample;             /* pbx_band_write_tiff_packed: the sample the plane is, 0 .. S - 1;
+                                   a registration takes it from refs[k].slice instead */
+} pbx_tiff_packed;              /* 16 bytes */
+/* pbx_planes_register_tiff_samples for such layers, packed[l] going with layers[l]: plane k is
+ * sample refs[k].slice of layer refs[k].layer.  Keys, all-or-none registration, statuses, staging
+ * and kernel_ms ([0] decoders, [1] placement) are that call's, stored segments are read where
+ * they were uploaded.  400 on the host names: bits outside 1 .. 16, bits that do not fit the
+ * plane's pixel type, fill_order outside {1, 2}, fill_order 2 with bits 16, a predictor other than
+ * 1 (libtiff defines the predictor on whole-byte samples only), flags != 0, samples_per_pixel
+ * outside 1 .. 4, a sample >= S, a compression outside {1, 5, 8, 50000, 32773}, and every other
+ * refusal of pbx_planes_register_tiff (segment shape, tile size, strip width, offsets, empty
+ * segments, an uncompressed segment that is not its rows' padded bytes, old-style LZW, zstd
+ * framing).  400 from the device, nothing registered: "corrupt chunk stream N (packbits, decoder
+ * code C)", C = 1 the stream ends before the segment's bytes are out, 3 a run that would write
+ * past them; the other decoders' as before. */
+int pbx_planes_register_tiff_packed(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* descs,
+                                    const pbx_zarr_slice* refs, uint64_t n_layers,
+                                    const pbx_tiff_segments* layers, const pbx_tiff_packed* packed,
+                                    uint64_t* plane_ids, double* kernel_ms);
+/* pbx_band_write_tiff_sample for such segments: the covering segment rows are decoded for this
+ * call and sample packed->sample alone is stored.  Band states, statuses and failure handling are
+ * pbx_band_write's, and pieces written by any band call may be mixed in one band. */
+int pbx_band_write_tiff_packed(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                               const pbx_tiff_segments* segs, const pbx_tiff_packed* packed,
+                               double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -933,6 +982,15 @@ int pbx_test_tiff_j2k_plan(const pbx_tiff_segments* segs, int32_t size_x, int32_
  * pitch; out_bytes must be exactly that. */
 int pbx_test_tiff_j2k_decode(const pbx_tiff_segments* segs, int32_t size_x, int32_t size_y, int32_t pixel_type,
                              int32_t samples_per_pixel, void* out, uint64_t out_bytes);
+
+/* Test hook: the host planner of pbx_planes_register_tiff_packed (rows == 0: the whole plane) or
+ * pbx_band_write_tiff_packed (rows >= 1: rows [y0, y0 + rows), segs holding the covering segment
+ * rows only) alone, no context and no device call.  400 as the real call.  out: streams handed to
+ * a decoder (stored segments are read where they lie: none), the decoded bytes of every segment
+ * (rows times padded row bytes), scratch bytes, segments handed to k_tiff_unpack_place, the padded
+ * row bytes of a segment, and the rows the segments hold in all. */
+int pbx_test_tiff_packed_plan(const pbx_tiff_segments* segs, const pbx_tiff_packed* packed, int32_t size_x,
+                              int32_t size_y, int32_t pixel_type, int32_t y0, int32_t rows, uint64_t out[6]);
 
 #ifdef __cplusplus
 }

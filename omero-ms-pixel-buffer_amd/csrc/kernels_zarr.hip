@@ -1495,7 +1495,7 @@ hipError_t launch_zarr_crc(hipStream_t st, const ZCheck* d_checks, uint32_t n_wa
 
 hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const uint32_t* counts,
                               const uint8_t* src, uint8_t* scratch, uint8_t* zstd_lit, uint32_t* err) {
-    // streams are ordered by kind: lz4, inflate, copy, blosclz, zstd, gzip, lzw
+    // streams are ordered by kind: lz4, inflate, copy, blosclz, zstd, gzip, lzw, packbits
     uint32_t first = 0;
     for (uint32_t k = 0; k < ZS_NKINDS; k++) {
         const uint32_t n = counts[k];
@@ -1525,6 +1525,11 @@ hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const ui
         case ZS_BLOSCLZ: hipLaunchKernelGGL(k_zarr_blosclz, g, b, ZWAVES * ZL_BYTES, st, s, n, src, scratch, e); break;
         case ZS_LZW: {
             hipError_t r = launch_tiff_lzw(st, s, n, src, scratch, e);
+            if (r != hipSuccess) return r;
+            break;
+        }
+        case ZS_PACKBITS: {
+            hipError_t r = launch_tiff_packbits(st, s, n, src, scratch, e);
             if (r != hipSuccess) return r;
             break;
         }

@@ -1,6 +1,6 @@
 // pbx_decode_types.h — the tables of the source decoders: plain structs the host planners fill
 // (source_plan.cpp), the runtime uploads as they are and the kernels read (kernels_zarr.hip,
-// kernels_zstd.hip, kernels_tiff_src.hip, kernels_tiff_jpeg.hip, kernels_tiff_j2k.hip), with the
+// kernels_zstd.hip, kernels_tiff_src.hip, kernels_tiff_packed.hip, kernels_tiff_jpeg.hip, kernels_tiff_j2k.hip), with the
 // decoders' stream kinds and error codes.  Plain C++ (no HIP headers): the launchers that take
 // these tables are declared in pbx_kernels.h.
 #pragma once
@@ -15,7 +15,9 @@ namespace pbx {
 // has parsed the header); k_zarr_inflate2 takes no zlib header and no Adler-32 for it and
 // requires the deflate data to end exactly 8 bytes before the stream's end.
 // ZS_LZW: a TIFF 6.0 LZW strip or tile (kernels_tiff_src.hip).
-enum : uint32_t { ZS_LZ4 = 0, ZS_ZLIB = 1, ZS_COPY = 2, ZS_BLOSCLZ = 3, ZS_ZSTD = 4, ZS_GZIP = 5, ZS_LZW = 6, ZS_NKINDS = 7 };
+// ZS_PACKBITS: a TIFF 6.0 PackBits strip or tile (kernels_tiff_packed.hip).
+enum : uint32_t { ZS_LZ4 = 0, ZS_ZLIB = 1, ZS_COPY = 2, ZS_BLOSCLZ = 3, ZS_ZSTD = 4, ZS_GZIP = 5, ZS_LZW = 6,
+                  ZS_PACKBITS = 7, ZS_NKINDS = 8 };
 struct ZStream {
     uint64_t src_off;  // compressed bytes in the uploaded chunk buffer
     uint64_t dst_off;  // decoded bytes in the scratch buffer
@@ -105,6 +107,28 @@ struct TSplitDst {
     uint32_t predictor;  // 1 or 2
 };
 static_assert(sizeof(TSplitDst) == 72, "TSplitDst is uploaded as is");
+
+// k_tiff_unpack_place (kernels_tiff_packed.hip; pbx_planes_register_tiff_packed and
+// pbx_band_write_tiff_packed): a segment whose rows are bit streams of `bits`-wide samples, MSB
+// first, every row padded to a whole byte: row_bytes = ceil(seg_w * spp * bits / 8).  Sample i of
+// a row is component i % spp of pixel i / spp and goes, unscaled, as uint8 (bits <= 8) or uint16
+// into plane dev[i % spp] of entry `dst` of the launch's TSplitDst table (bpp 1 or 2 to match;
+// spp 1 .. 4; predictor unused), clipped as k_tiff_split_place clips.  Also k_tiff_packbits: one
+// wave per ZS_PACKBITS stream, err[] 0, or 1 the stream ends before dlen bytes are out, 3 a run
+// past dlen.
+struct TUnpack {
+    uint64_t src;        // the segment's decoded bytes: scratch offset (input offset with from_input)
+    uint32_t row_bytes;  // the segment's own pitch
+    uint32_t rows;       // rows it holds (a short last strip: the rows left)
+    int32_t x0, y0;      // its origin in the plane
+    uint32_t from_input;
+    uint32_t dst;        // its entry in the launch's TSplitDst table
+    uint32_t seg_w;      // pixels of a row (a tile's padded width)
+    uint32_t bits;       // 1 .. 16
+    uint32_t fill_order; // 1, or 2: the bits of every source byte are reversed first
+    uint32_t pad;
+};
+static_assert(sizeof(TUnpack) == 48, "TUnpack is uploaded as is");
 
 // JPEG-compressed TIFF segments (kernels_tiff_jpeg.hip; Compression = 7, baseline streams of
 // 8-bit samples).  The host parses the marker segments; the tables reach the device resolved per

@@ -115,7 +115,7 @@ hipError_t launch_huffman(hipStream_t st, uint32_t nblk, BlkInfo* blk, SegInfo* 
                           const uint32_t* hist, uint32_t* codes);
 
 // NGFF/Zarr chunk decode (kernels_zarr.hip, kernels_zstd.hip; tables: pbx_decode_types.h).
-// Streams ordered by kind (ZS_LZ4| ZS_ZLIB | ZS_COPY | ZS_BLOSCLZ | ZS_ZSTD | ZS_GZIP | ZS_LZW), counts[k] of
+// Streams ordered by kind (ZS_LZ4| ZS_ZLIB | ZS_COPY | ZS_BLOSCLZ | ZS_ZSTD | ZS_GZIP | ZS_LZW | ZS_PACKBITS), counts[k] of
 // kind k; err[i] = 0 or a decoder error code per stream.
 // zstd_lit: zstd_scratch_bytes(counts[ZS_ZSTD]) bytes (a block's literals per zstd frame).
 hipError_t launch_zarr_decode(hipStream_t st, const ZStream* d_streams, const uint32_t* counts,
@@ -151,6 +151,14 @@ hipError_t launch_tiff_fpunpred_place(hipStream_t st, const TPlace* d_segs, uint
                                       const TPlaceDst* d_dst, const uint8_t* scratch, const uint8_t* input);
 hipError_t launch_tiff_split_place(hipStream_t st, const TPlace* d_segs, uint32_t n, uint32_t max_rows,
                                    const TSplitDst* d_dst, const uint8_t* scratch, const uint8_t* input);
+
+// Bit-packed samples and PackBits streams (kernels_tiff_packed.hip; TUnpack).  k_tiff_packbits:
+// one wave per ZS_PACKBITS stream, launched by launch_zarr_decode.  k_tiff_unpack_place: d_dst is
+// the launch's TSplitDst table, TUnpack::dst a segment's entry in it.
+hipError_t launch_tiff_packbits(hipStream_t st, const ZStream* d_streams, uint32_t n, const uint8_t* src,
+                                uint8_t* scratch, uint32_t* err);
+hipError_t launch_tiff_unpack_place(hipStream_t st, const TUnpack* d_segs, uint32_t n, uint32_t max_rows,
+                                    const TSplitDst* d_dst, const uint8_t* scratch, const uint8_t* input);
 
 // JPEG-compressed TIFF segments (kernels_tiff_jpeg.hip; JStream, JTabSet, TJpegSeg).
 // err[]: 0, or 1 entropy data ends before the last MCU, 2 a code that is in no table, 3 a run that

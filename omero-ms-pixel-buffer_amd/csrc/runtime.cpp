@@ -2380,7 +2380,8 @@ struct ZarrInput {
 //   bytes), k_tiff_unpred (P.unpred), the JPEG decoder (P.jstreams), the JPEG 2000 chain
 //   (P.j2streams)                                                       -- kernel_ms[0]
 //   k_zarr_place (P.chunks), k_tiff_unpred_place into zp[0] (P.uplace), k_tiff_split_place
-//   (P.split), k_tiff_fpunpred_place into the planes P.fdst_plane names (P.fplace),
+//   (P.split), k_tiff_unpack_place (P.unpack), k_tiff_fpunpred_place into the planes
+//   P.fdst_plane names (P.fplace),
 //   k_tiff_jpeg_place (P.jsegs), k_tiff_j2k_place and _place_chroma (P.j2segs)  -- kernel_ms[1]
 // 400 (launch_errors) for a stream a decoder or a check rejects; rows already placed are then the
 // caller's to discard.
@@ -2389,7 +2390,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
                       const std::vector<TSplitDst>* sd = nullptr) {
     const bool unpred = !P.unpred.empty(), uplace = !P.uplace.empty(), split = !P.split.empty();
     const bool fplace = !P.fplace.empty(), jpeg = !P.jstreams.empty(), j2k = !P.j2streams.empty();
-    if ((split || !P.jsegs.empty() || !P.j2segs.empty()) && (!sd || sd->empty()))
+    const bool unpack = !P.unpack.empty();
+    if ((split || unpack || !P.jsegs.empty() || !P.j2segs.empty()) && (!sd || sd->empty()))
         return fail(PBX_E_INTERNAL, "zarr decode: split segments without destinations");
     const LaunchLayout L(P, zarr_crc_split());
     std::vector<TPlaceDst> fd = P.fdst;  // Predictor = 3: the destinations of this launch
@@ -2420,7 +2422,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     TUnpred* d_up = S.table_if(unpred, P.unpred);
     TPlace* d_tp = S.table_if(uplace, P.uplace);
     TPlace* d_sp = S.table_if(split, P.split);
-    TSplitDst* d_sd = split || jpeg || j2k ? S.table(*sd) : nullptr;
+    TSplitDst* d_sd = split || unpack || jpeg || j2k ? S.table(*sd) : nullptr;
+    TUnpack* d_un = S.table_if(unpack, P.unpack);
     TPlace* d_fp = S.table_if(fplace, P.fplace);
     TPlaceDst* d_fd = S.table_if(fplace, fd);
     JStream* d_js = S.table_if(jpeg, P.jstreams);
@@ -2463,6 +2466,8 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     }
     if (e == hipSuccess && split)
         e = launch_tiff_split_place(st, d_sp, (uint32_t)P.split.size(), P.split_rows, d_sd, d_scr, d_in);
+    if (e == hipSuccess && unpack)
+        e = launch_tiff_unpack_place(st, d_un, (uint32_t)P.unpack.size(), P.unpack_rows, d_sd, d_scr, d_in);
     if (e == hipSuccess && fplace)
         e = launch_tiff_fpunpred_place(st, d_fp, (uint32_t)P.fplace.size(), P.fplace_rows, d_fd, d_scr, d_in);
     if (e == hipSuccess && jpeg)
@@ -2536,7 +2541,7 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const Tiff
         const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
                                             q->size_y, s->seg_w, s->seg_h, (uint32_t)bpp, 0, 0, y0, y0 + rows}};
         std::vector<TSplitDst> sd;
-        if (spp > 1 || c.jpeg || c.j2k) {
+        if (spp > 1 || c.jpeg || c.j2k || c.packed) {
             sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, q->pitch, q->size_x, q->size_y, y0, y0 + rows,
                                    (uint32_t)bpp, q->little_endian ? 0u : 1u, (uint32_t)spp, (uint32_t)s->predictor});
             sd[0].dev[sample] = zp[0].dev;
@@ -2553,7 +2558,10 @@ struct TiffLayers {
     const pbx_tiff_jpeg* jpeg = nullptr;  // the layers are JPEG streams: their tables
     bool j2k = false;                     // they are JPEG 2000 codestreams
     explicit operator bool() const { return s != nullptr; }
-    TiffCodec operator[](uint64_t l) const { return TiffCodec{&s[l], jpeg ? &jpeg[l] : nullptr, j2k}; }
+    const pbx_tiff_packed* packed = nullptr;  // their rows are bit-packed samples: how
+    TiffCodec operator[](uint64_t l) const {
+        return TiffCodec{&s[l], jpeg ? &jpeg[l] : nullptr, j2k, packed ? &packed[l] : nullptr};
+    }
 };
 
 int64_t plane_pitch(int32_t size_x, int bpp) { return ((int64_t)size_x * bpp + 255) & ~(int64_t)255; }
@@ -2659,7 +2667,7 @@ int register_zarr_layers(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, con
             if (int rc = tiff_codec_plan(c, d->size_x, d->size_y, bpp, big, in_base[l], want[l][0].plane, P, false, 0, -1,
                                          depths[l], (uint32_t)sd.size()))
                 return rc;
-            if (depths[l] > 1 || c.jpeg || c.j2k) {
+            if (depths[l] > 1 || c.jpeg || c.j2k || c.packed) {
                 sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, plane_pitch(d->size_x, bpp),
                                        d->size_x, d->size_y, 0, d->size_y, (uint32_t)bpp, big && bpp > 1 ? 1u : 0u,
                                        (uint32_t)depths[l], (uint32_t)c.s->predictor});
@@ -2783,6 +2791,27 @@ int pbx_band_write_tiff_j2k(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows,
     if (!ctx || !s) return fail(PBX_E_BADARG, "null argument");
     return with_sparse_plane(ctx, id, [&](Plane* q) {
         return band_write_tiff(ctx, q, y0, rows, TiffCodec{s, nullptr, true}, samples_per_pixel, sample, kernel_ms);
+    });
+}
+
+int pbx_planes_register_tiff_packed(pbx_ctx* ctx, uint64_t n, const pbx_plane_desc* ds, const pbx_zarr_slice* refs,
+                                    uint64_t n_layers, const pbx_tiff_segments* layers, const pbx_tiff_packed* packed,
+                                    uint64_t* plane_ids, double* kernel_ms) {
+    if (!ctx || !ds || !refs || !layers || !packed || !plane_ids || n == 0 || n_layers == 0)
+        return fail(PBX_E_BADARG, "null argument");
+    if (n > 0xffffffffull || n_layers > n) return fail(PBX_E_BADARG, "more layers than planes");
+    std::vector<int32_t> spp(n_layers);
+    for (uint64_t l = 0; l < n_layers; l++) spp[l] = packed[l].samples_per_pixel;
+    return register_zarr_layers(ctx, n, ds, refs, n_layers, nullptr, spp.data(), plane_ids, kernel_ms,
+                                TiffLayers{layers, nullptr, false, packed});
+}
+
+int pbx_band_write_tiff_packed(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
+                               const pbx_tiff_packed* packed, double* kernel_ms) {
+    if (!ctx || !s || !packed) return fail(PBX_E_BADARG, "null argument");
+    return with_sparse_plane(ctx, id, [&](Plane* q) {
+        return band_write_tiff(ctx, q, y0, rows, TiffCodec{s, nullptr, false, packed}, packed->samples_per_pixel,
+                               packed->sample, kernel_ms);
     });
 }
 

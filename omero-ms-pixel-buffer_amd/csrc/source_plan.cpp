@@ -279,20 +279,27 @@ int zarr_slice_check(int32_t depth, int64_t slice) {
 // ------------------------------------------------------------------ TIFF / OME-TIFF planes
 static_assert(sizeof(pbx_tiff_segments) == 40, "pbx_tiff_segments is part of the C-ABI (ctypes mirror PbxTiffSegments)");
 // pbx_tiff_segments fields that can be checked without the plane.
-int tiff_segments_check(const pbx_tiff_segments* s) {
+// (packed: the pbx_*_tiff_packed calls, which take PackBits too and predictor 1 alone)
+static int tiff_segments_check_as(const pbx_tiff_segments* s, bool packed) {
     if (!s->data || !s->offsets) return fail(PBX_E_BADARG, "null argument");
     if (s->seg_w < 1 || s->seg_h < 1) return fail(PBX_E_BADARG, "bad segment shape %d x %d", s->seg_w, s->seg_h);
     if (s->tiled && ((s->seg_w | s->seg_h) & 15))
         return fail(PBX_E_BADARG, "tile %d x %d: TileWidth and TileLength must be multiples of 16 (TIFF 6.0 section 15)",
                     s->seg_w, s->seg_h);
     if (s->compression != PBX_TIFF_NONE && s->compression != PBX_TIFF_LZW && s->compression != PBX_TIFF_DEFLATE &&
-        s->compression != PBX_TIFF_ZSTD)
-        return fail(PBX_E_BADARG, "bad compression %d (1 none, 5 LZW, 8 deflate, 50000 zstd)", s->compression);
+        s->compression != PBX_TIFF_ZSTD && !(packed && s->compression == PBX_TIFF_PACKBITS))
+        return fail(PBX_E_BADARG, packed ? "bad compression %d (1 none, 5 LZW, 8 deflate, 50000 zstd, 32773 PackBits)"
+                                         : "bad compression %d (1 none, 5 LZW, 8 deflate, 50000 zstd)", s->compression);
+    if (packed && s->predictor != 1)
+        return fail(PBX_E_BADARG, "bad predictor %d (bit-packed samples take 1 only: the predictor is defined on "
+                                  "whole-byte samples)", s->predictor);
     if (s->predictor < 1 || s->predictor > 3)
         return fail(PBX_E_BADARG, "bad predictor %d (1, 2, or 3 on float and double planes)", s->predictor);
     if (s->flags) return fail(PBX_E_BADARG, "bad flags 0x%x", (unsigned)s->flags);
     return PBX_OK;
 }
+
+int tiff_segments_check(const pbx_tiff_segments* s) { return tiff_segments_check_as(s, false); }
 
 // A sample of chunky segments that hold spp samples per pixel, on a plane of bpp bytes a sample.
 int tiff_samples_check(int32_t spp, int64_t sample, int bpp) {
@@ -413,6 +420,81 @@ int tiff_plan(int32_t size_x, int32_t size_y, int bpp, bool big_endian, const pb
                                        big_endian ? 1u : 0u});
             P.unpred_rows = std::max(P.unpred_rows, (uint32_t)rows);
         }
+    }
+    return PBX_OK;
+}
+
+// ------------------------------------------------------- bit-packed samples and PackBits
+static_assert(sizeof(pbx_tiff_packed) == 16, "pbx_tiff_packed is part of the C-ABI (ctypes mirror PbxTiffPacked)");
+int tiff_packed_check(const pbx_tiff_segments* s, const pbx_tiff_packed* k, int32_t pixel_type) {
+    if (int rc = tiff_segments_check_as(s, true)) return rc;
+    if (k->bits < 1 || k->bits > 16) return fail(PBX_E_BADARG, "bad bits %d (1 .. 16)", k->bits);
+    const bool integer = pixel_type >= PBX_INT8 && pixel_type <= PBX_UINT16;
+    if (!integer || bpp_of(pixel_type) != (k->bits > 8 ? 2 : 1))
+        return fail(PBX_E_BADARG, "%d-bit samples on a plane of pixel type %d (1 .. 8 bits take an 8-bit integer "
+                                  "plane, 9 .. 16 a 16-bit one)", k->bits, pixel_type);
+    if (k->fill_order != 1 && k->fill_order != 2) return fail(PBX_E_BADARG, "bad fill_order %d (1 or 2)", k->fill_order);
+    if (k->fill_order == 2 && k->bits == 16)
+        return fail(PBX_E_BADARG, "fill_order 2 on 16-bit samples (their bytes are in the file's order, not a bit "
+                                  "stream's)");
+    return PBX_OK;
+}
+
+// Host plan of the segment rows [sr0, sr1) (sr1 < 0: all) of bit-packed samples: tiff_plan's
+// geometry with rows of ceil(seg_w * spp * bits / 8) bytes, so a decoder's dlen is rows times
+// that.  Registration and band writes are planned alike, as chunky segments are: a stored segment
+// is read where it was uploaded (its length must be its rows' padded bytes), a compressed one gets
+// a stream (ZS_LZW, ZS_ZLIB, ZS_ZSTD or ZS_PACKBITS) into scratch, and every segment a TUnpack for
+// k_tiff_unpack_place with `dst` as its entry in the launch's TSplitDst table.
+int tiff_packed_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, const pbx_tiff_packed* k,
+                     uint64_t in_base, ZarrPlan& P, int64_t sr0, int64_t sr1, int spp, uint32_t dst,
+                     uint64_t* dlen_sum) {
+    if (!s->tiled && s->seg_w != size_x)
+        return fail(PBX_E_BADARG, "strip width %d != plane width %d", s->seg_w, size_x);
+    const int64_t gx = s->tiled ? ((int64_t)size_x + s->seg_w - 1) / s->seg_w : 1;
+    const int64_t gy = ((int64_t)size_y + s->seg_h - 1) / s->seg_h;
+    if (sr1 < 0) sr1 = gy;
+    const int64_t n = gx * (sr1 - sr0);
+    const uint64_t total = s->offsets[n];
+    const uint64_t rb = tiff_packed_row_bytes(s->seg_w, spp, k->bits);
+    for (int64_t i = 0; i < n; i++) {
+        const uint64_t o = s->offsets[i], len = s->offsets[i + 1] - o;
+        if (s->offsets[i + 1] < o || s->offsets[i + 1] > total)
+            return fail(PBX_E_BADARG, "segment %lld: bad offsets", (long long)i);
+        if (len == 0) return fail(PBX_E_BADARG, "segment %lld is empty", (long long)i);
+        const int32_t x0 = (int32_t)((i % gx) * s->seg_w), y0 = (int32_t)((sr0 + i / gx) * s->seg_h);
+        const int32_t rows = s->tiled ? s->seg_h : std::min(s->seg_h, size_y - y0);
+        const uint64_t dlen = rb * (uint64_t)rows;
+        if (rb > 0x7fffffffull || dlen > 0x7fffffffull || len > 0x7fffffffull || rows > (65535 << 4))
+            return fail(PBX_E_BADARG, "segment %lld too large", (long long)i);
+        const uint64_t ob = o + in_base;
+        const bool in_place = s->compression == PBX_TIFF_NONE;  // read from the upload buffer
+        if (in_place) {
+            if (len != dlen)
+                return fail(PBX_E_BADARG, "uncompressed segment %lld: %llu bytes, not %llu (%d rows of %llu bytes: "
+                                          "%d samples of %d bits, padded to a byte)", (long long)i,
+                            (unsigned long long)len, (unsigned long long)dlen, rows, (unsigned long long)rb,
+                            s->seg_w * spp, k->bits);
+        } else {
+            uint32_t kind = ZS_ZLIB;
+            if (s->compression == PBX_TIFF_LZW) {
+                // libtiff's test for the pre-6.0 bit order (LSB first, which begins 00 01 for Clear)
+                if (len >= 2 && s->data[o] == 0 && (s->data[o + 1] & 1))
+                    return fail(PBX_E_BADARG, "segment %lld: old-style (pre-6.0, LSB-first) LZW", (long long)i);
+                kind = ZS_LZW;
+            } else if (s->compression == PBX_TIFF_ZSTD) {
+                if (int rc = zstd_frame_check(s->data + o, len, dlen, (long long)i, "segment")) return rc;
+                kind = ZS_ZSTD;
+            } else if (s->compression == PBX_TIFF_PACKBITS) {
+                kind = ZS_PACKBITS;
+            }
+            P.kind[kind].push_back(ZStream{ob, P.scratch, (uint32_t)len, (uint32_t)dlen, kind, 0});
+        }
+        P.unpack.push_back(TUnpack{in_place ? ob : P.scratch, (uint32_t)rb, (uint32_t)rows, x0, y0, in_place ? 1u : 0u, dst,
+                                   (uint32_t)s->seg_w, (uint32_t)k->bits, (uint32_t)k->fill_order, 0});
+        P.unpack_rows = std::max(P.unpack_rows, (uint32_t)rows);
+        if (!in_place) P.scratch += (dlen + 255) & ~255ull;
+        if (dlen_sum) *dlen_sum += dlen;
     }
     return PBX_OK;
 }
@@ -1166,6 +1248,10 @@ int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segmen
 
 // ------------------------------------------------------------------ one codec, one launch
 int tiff_codec_check(const TiffCodec& c, int32_t pixel_type, int32_t spp, int64_t sample, uint64_t plane_label) {
+    if (c.packed) {
+        if (int rc = tiff_packed_check(c.s, c.packed, pixel_type)) return rc;
+        return tiff_samples_check(spp, sample, bpp_of(pixel_type));
+    }
     if (int rc = c.j2k    ? tiff_j2k_check(c.s, pixel_type, spp)
                  : c.jpeg ? tiff_jpeg_check(c.s, c.jpeg, pixel_type, spp)
                           : tiff_segments_check(c.s))
@@ -1178,6 +1264,7 @@ int tiff_codec_check(const TiffCodec& c, int32_t pixel_type, int32_t spp, int64_
 
 int tiff_codec_plan(const TiffCodec& c, int32_t size_x, int32_t size_y, int bpp, bool big_endian, uint64_t in_base,
                     uint32_t plane, ZarrPlan& P, bool band, int64_t sr0, int64_t sr1, int spp, uint32_t dst) {
+    if (c.packed) return tiff_packed_plan(size_x, size_y, c.s, c.packed, in_base, P, sr0, sr1, spp, dst);
     if (c.j2k) return tiff_j2k_plan(size_x, size_y, bpp, c.s, in_base, P, sr0, sr1, spp, dst);
     if (c.jpeg) return tiff_jpeg_plan(size_x, size_y, c.s, c.jpeg, in_base, P, sr0, sr1, spp, dst);
     return tiff_plan(size_x, size_y, bpp, big_endian, c.s, in_base, plane, P, nullptr, band, sr0, sr1, spp, dst);
@@ -1225,7 +1312,7 @@ LaunchLayout::LaunchLayout(const ZarrPlan& P, uint32_t crc_split) : j2segs(P.j2s
 int launch_errors(const LaunchLayout& L, const uint32_t* err) {
     for (uint32_t s = 0; s < L.nstreams; s++)
         if (const uint32_t code = err[L.err_streams + s]) {
-            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd", "gzip", "lzw"};
+            static const char* names[ZS_NKINDS] = {"lz4", "zlib", "stored", "blosclz", "zstd", "gzip", "lzw", "packbits"};
             uint32_t k = 0, first = 0;
             while (s >= first + L.counts[k]) first += L.counts[k++];
             return fail(PBX_E_BADARG, "corrupt chunk stream %u (%s, decoder code %u)", s, names[k], code);
@@ -1477,6 +1564,32 @@ int pbx_test_tiff_jpeg_plan(const pbx_tiff_segments* s, const pbx_tiff_jpeg* jpe
     out[4] = P.jsegs.empty() ? 0 : P.jsegs[0].mode;
     out[5] = 0;
     for (const JStream& t : P.jstreams) out[5] += t.csize;
+    return PBX_OK;
+}
+
+int pbx_test_tiff_packed_plan(const pbx_tiff_segments* s, const pbx_tiff_packed* k, int32_t size_x, int32_t size_y,
+                              int32_t pixel_type, int32_t y0, int32_t rows, uint64_t out[6]) {
+    if (!s || !k || !out) return fail(PBX_E_BADARG, "null argument");
+    if (int rc = tiff_codec_check(TiffCodec{s, nullptr, false, k}, pixel_type, k->samples_per_pixel, k->sample, 0))
+        return rc;
+    if (size_x <= 0 || size_y <= 0) return fail(PBX_E_BADARG, "bad plane size");
+    if (rows < 0 || y0 < 0 || (int64_t)y0 + rows > size_y)
+        return fail(PBX_E_BADARG, "rows %d+%d outside the plane (%d rows)", y0, rows, size_y);
+    ZarrPlan P;
+    uint64_t sum = 0;
+    const bool band = rows > 0;
+    if (int rc = tiff_packed_plan(size_x, size_y, s, k, 0, P, band ? y0 / s->seg_h : 0,
+                                  band ? ((int64_t)y0 + rows + s->seg_h - 1) / s->seg_h : -1, k->samples_per_pixel, 0,
+                                  &sum))
+        return rc;
+    out[0] = 0;
+    for (const auto& kd : P.kind) out[0] += kd.size();
+    out[1] = sum;
+    out[2] = P.scratch;
+    out[3] = P.unpack.size();
+    out[4] = P.unpack.empty() ? 0 : P.unpack[0].row_bytes;
+    out[5] = 0;
+    for (const TUnpack& u : P.unpack) out[5] += u.rows;
     return PBX_OK;
 }
 

@@ -51,6 +51,11 @@ struct ZarrPlan {
     uint32_t fplace_rows = 0;     // the tallest of them
     std::vector<TPlaceDst> fdst;
     std::vector<uint32_t> fdst_plane;
+    // TIFF segments of bit-packed samples (tiff_packed_plan): every segment, registration and band
+    // writes alike, for k_tiff_unpack_place (then no `unpred`, no `uplace`, no `chunks`);
+    // TUnpack::dst names the segment's entry in the launch's TSplitDst table
+    std::vector<TUnpack> unpack;
+    uint32_t unpack_rows = 0;     // the tallest of them
     // JPEG-compressed TIFF segments (tiff_jpeg_plan): one JStream and one TJpegSeg per segment
     // (then no `kind`, no `chunks`), the distinct table sets of the launch, and the tallest
     // segment; TJpegSeg::dst names the segment's entry in the launch's TSplitDst table
@@ -100,16 +105,29 @@ int tiff_j2k_check(const pbx_tiff_segments* s, int32_t pixel_type, int32_t spp);
 int tiff_j2k_plan(int32_t size_x, int32_t size_y, int bpp, const pbx_tiff_segments* s, uint64_t in_base, ZarrPlan& P,
                   int64_t sr0, int64_t sr1, int spp, uint32_t dst, uint64_t* packets = nullptr);
 
+// Bit-packed samples (pbx_*_tiff_packed): the fields of `k` that can be checked with the plane's
+// pixel type alone, and tiff_segments_check's with PackBits among the compressions.
+int tiff_packed_check(const pbx_tiff_segments* s, const pbx_tiff_packed* k, int32_t pixel_type);
+// Padded bytes of a segment row: ceil(seg_w * spp * bits / 8).
+inline uint64_t tiff_packed_row_bytes(int32_t seg_w, int32_t spp, int32_t bits) {
+    return ((uint64_t)seg_w * (uint64_t)spp * (uint64_t)bits + 7) >> 3;
+}
+int tiff_packed_plan(int32_t size_x, int32_t size_y, const pbx_tiff_segments* s, const pbx_tiff_packed* k,
+                     uint64_t in_base, ZarrPlan& P, int64_t sr0, int64_t sr1, int spp, uint32_t dst,
+                     uint64_t* dlen_sum = nullptr);
+
 // How a pbx_tiff_segments is compressed, as the entry point that took it says: its streams are
-// JPEG 2000 codestreams (j2k), JPEG streams with the tables of `jpeg`, or else what
+// JPEG 2000 codestreams (j2k), JPEG streams with the tables of `jpeg`, rows of bit-packed samples
+// as `packed` describes them (under s->compression, PackBits included), or else what
 // s->compression names.
 struct TiffCodec {
     const pbx_tiff_segments* s;
     const pbx_tiff_jpeg* jpeg;
     bool j2k;
+    const pbx_tiff_packed* packed = nullptr;
 };
-// The codec's own check (tiff_j2k_check, tiff_jpeg_check or tiff_segments_check), then what holds
-// for all three: no Predictor = 2 on float / double, tiff_fp_predictor_check, tiff_samples_check.
+// The codec's own check (tiff_j2k_check, tiff_jpeg_check, tiff_packed_check or tiff_segments_check), then what holds
+// for all: no Predictor = 2 on float / double, tiff_fp_predictor_check, tiff_samples_check.
 // `plane_label` is the number messages call the plane by.
 int tiff_codec_check(const TiffCodec& c, int32_t pixel_type, int32_t spp, int64_t sample, uint64_t plane_label);
 // tiff_j2k_plan, tiff_jpeg_plan or tiff_plan of segment rows [sr0, sr1) (sr1 < 0: all) with the

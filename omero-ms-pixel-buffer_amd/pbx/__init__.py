@@ -104,6 +104,17 @@ class PbxTiffJpeg(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class PbxTiffPacked(ctypes.Structure):
+    _fields_ = [("bits", ctypes.c_int32), ("fill_order", ctypes.c_int32),
+                ("samples_per_pixel", ctypes.c_int32), ("sample", ctypes.c_int32)]
+
+
+def _fill_tiff_packed(k: "PbxTiffPacked", packed: Mapping, samples_per_pixel: int = 1, sample: int = 0) -> None:
+    """pbx_tiff_packed from a spec's `packed` dict (bits[, fill_order]) and its samples_per_pixel / sample."""
+    k.bits, k.fill_order = packed["bits"], packed.get("fill_order", 1)
+    k.samples_per_pixel, k.sample = samples_per_pixel, sample
+
+
 def _fill_tiff_jpeg(j: "PbxTiffJpeg", jpeg: Mapping) -> object:
     """pbx_tiff_jpeg from a spec's `jpeg` dict (tables = tag 347's bytes or None, ycbcr); returns
     the buffer the struct points into, to be kept alive over the call."""
@@ -216,6 +227,7 @@ EXPORTS = [
     "pbx_band_write_tiff_sample", "pbx_test_tiff_plan_samples", "pbx_planes_register_tiff_jpeg",
     "pbx_band_write_tiff_jpeg", "pbx_test_tiff_jpeg_plan", "pbx_planes_register_tiff_j2k",
     "pbx_band_write_tiff_j2k", "pbx_test_tiff_j2k_plan", "pbx_test_tiff_j2k_decode",
+    "pbx_planes_register_tiff_packed", "pbx_band_write_tiff_packed", "pbx_test_tiff_packed_plan",
 ]
 
 _lib = None
@@ -341,6 +353,14 @@ def lib() -> ctypes.CDLL:
     L.pbx_test_tiff_j2k_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, i32, i32,
                                          ctypes.POINTER(u64)]
     L.pbx_test_tiff_j2k_decode.argtypes = [ctypes.POINTER(PbxTiffSegments), i32, i32, i32, i32, vp, u64]
+    L.pbx_planes_register_tiff_packed.argtypes = [vp, u64, ctypes.POINTER(PbxPlaneDesc),
+                                                  ctypes.POINTER(PbxZarrSlice), u64,
+                                                  ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(PbxTiffPacked),
+                                                  ctypes.POINTER(u64), ctypes.POINTER(ctypes.c_double)]
+    L.pbx_band_write_tiff_packed.argtypes = [vp, u64, i32, i32, ctypes.POINTER(PbxTiffSegments),
+                                             ctypes.POINTER(PbxTiffPacked), ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_tiff_packed_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(PbxTiffPacked), i32, i32,
+                                            i32, i32, i32, ctypes.POINTER(u64)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -831,6 +851,7 @@ def pack_chunks(chunks: Sequence[Optional[bytes]]):
 TIFF_NONE, TIFF_LZW, TIFF_DEFLATE = 1, 5, 8  # enum pbx_tiff_compression
 TIFF_ZSTD = 50000
 TIFF_JPEG = 7  # through the pbx_*_tiff_jpeg calls only
+TIFF_PACKBITS = 32773  # through the pbx_*_tiff_packed calls only
 TIFF_F_J2K_PACKETS = 1  # pbx_tiff_segments.flags: JPEG 2000 layers, precincts, SOP / EPH (the pbx_*_tiff_j2k calls only)
 TIFF_F_J2K_SUBSAMPLED = 4  # components 1 and 2 at half width and / or half height (the same calls only)
 TIFF_F_J2K_YCBCR = 8  # YCbCr components outside the codestream: converted to RGB (the same calls only)
@@ -1317,15 +1338,64 @@ def _tiff_j2k_first_segment(path: str, ifd: dict, spp: int, bits: int, packets: 
     return sub
 
 
+def _tiff_needs_packed(ifd: dict) -> bool:
+    """Whether an IFD is what the pbx_*_tiff_packed calls exist for: samples that are not whole
+    bytes, PackBits segments, or FillOrder 2."""
+    return ifd["bits"] not in (8, 16, 32, 64) or ifd["compression"] == TIFF_PACKBITS or ifd["fillorder"] == 2
+
+
+def _tiff_packed_pixel_type(path: str, ifd: dict) -> int:
+    """_tiff_pixel_type for an IFD that goes through the pbx_*_tiff_packed calls (SamplesPerPixel
+    and PlanarConfiguration are checked already): bits 1 .. 7 give UINT8 and 9 .. 15 UINT16,
+    unscaled, as Bio-Formats unpacks them; 8 and 16 their usual types."""
+    bits, sf, spp = ifd["bits"], ifd["sampleformat"], ifd["spp"]
+    if ifd["compression"] not in (1, 5, 8, 32946, TIFF_ZSTD, TIFF_PACKBITS):
+        raise PbxError(400, "%s: Compression %d with %d-bit samples or FillOrder %d (1 none, 5 LZW, 8 / 32946 deflate, "
+                       "50000 zstd, 32773 PackBits)" % (path, ifd["compression"], bits, ifd["fillorder"]))
+    if not 1 <= bits <= 16:
+        raise PbxError(400, "%s: BitsPerSample %d with Compression %d / FillOrder %d (PackBits and FillOrder 2 are "
+                       "supported on samples of 1 to 16 bits)" % (path, bits, ifd["compression"], ifd["fillorder"]))
+    if bits in (8, 16):
+        pt = _TIFF_PIXEL_TYPES.get((sf, bits))
+        if pt is None:
+            raise PbxError(400, "%s: SampleFormat %d with %d bits is none of the pixel types" % (path, sf, bits))
+    else:
+        if sf != 1:
+            raise PbxError(400, "%s: SampleFormat %d with BitsPerSample %d (packed samples are unsigned integers: "
+                           "SampleFormat 1 or none)" % (path, sf, bits))
+        pt = UINT8 if bits < 8 else UINT16
+        if ifd.get("photometric") == 0:
+            raise PbxError(400, "%s: PhotometricInterpretation 0 (WhiteIsZero) on %d-bit packed samples is not "
+                           "supported (the samples would have to be inverted)" % (path, bits))
+    if ifd.get("photometric") == 3:
+        raise PbxError(400, "%s: PhotometricInterpretation 3 (palette colour) is not supported" % path)
+    if spp == 1 and ifd.get("photometric") not in (None, 0, 1):
+        raise PbxError(400, "%s: PhotometricInterpretation %d with one %d-bit sample per pixel (0 or 1)"
+                       % (path, ifd["photometric"], bits))
+    if ifd["predictor"] != 1:
+        raise PbxError(400, "%s: Predictor %d with %s (the predictor is defined on whole-byte samples, and the packed "
+                       "path takes 1 only)" % (path, ifd["predictor"], "BitsPerSample %d" % bits if bits not in (8, 16)
+                                               else "Compression 32773" if ifd["compression"] == TIFF_PACKBITS
+                                               else "FillOrder 2"))
+    if ifd["fillorder"] not in (1, 2):
+        raise PbxError(400, "%s: FillOrder %d (1 or 2)" % (path, ifd["fillorder"]))
+    if ifd["fillorder"] == 2 and bits == 16:
+        raise PbxError(400, "%s: FillOrder 2 with 16-bit samples" % path)
+    if ifd["orientation"] != 1:
+        raise PbxError(400, "%s: Orientation %d (only 1, top left, is supported)" % (path, ifd["orientation"]))
+    return pt
+
+
 def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False, j2k_chroma: bool = False,
-                     aperio_ycbcr: bool = False, j2k_flags: Optional[list] = None) -> int:
+                     aperio_ycbcr: bool = False, j2k_flags: Optional[list] = None, packed: bool = False) -> int:
     """The pixel type of an IFD this library can load, else PbxError 400 with the reason.
     SamplesPerPixel 1 to 4: every sample is a channel of that type, ExtraSamples included.
     For a Compression-7 IFD, and for a JPEG 2000 one (Compression 33003 / 33004 / 33005 / 34712),
     the first segment is read and its header checked too, by every caller (a band spec of no
     rows included: its refusals are tiff_plane_spec's).  j2k_packets, j2k_chroma, aperio_ycbcr: as
     tiff_plane_spec's; j2k_flags, a list, receives the TIFF_F_J2K_* flags a JPEG 2000 IFD's
-    segments are to be handed over with."""
+    segments are to be handed over with.  packed: as tiff_plane_spec's; an IFD of 1- to 7-bit
+    samples is then UINT8 and one of 9- to 15-bit samples UINT16."""
     spp = ifd["spp"]
     # a three-sample chunky JPEG 2000 IFD: YCbCr components outside the codestream
     j2k_rgb = ifd["compression"] in _TIFF_J2K_COMPRESSIONS and spp == 3 and ifd.get("planar", 1) == 1
@@ -1343,6 +1413,8 @@ def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False, j2k_chroma
                        % (path, ifd["photometric"], spp))
     if ifd.get("planar", 1) not in (1, 2):
         raise PbxError(400, "%s: PlanarConfiguration %d (1 chunky or 2 planar)" % (path, ifd["planar"]))
+    if packed and _tiff_needs_packed(ifd):  # (every other IFD is checked as it always was)
+        return _tiff_packed_pixel_type(path, ifd)
     if ifd["bits"] not in (8, 16, 32, 64):
         raise PbxError(400, "%s: BitsPerSample %d (8, 16, 32 or 64)" % (path, ifd["bits"]))
     if spp > 1 and ifd["bits"] == 64:
@@ -1408,7 +1480,7 @@ def _tiff_pixel_type(path: str, ifd: dict, j2k_packets: bool = False, j2k_chroma
 
 def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int, level: int = 0,
                     sample: int = 0, j2k_packets: bool = False, j2k_chroma: bool = False,
-                    aperio_ycbcr: bool = False) -> dict:
+                    aperio_ycbcr: bool = False, packed: bool = False) -> dict:
     """register_tiff_planes() arguments for the plane that is sample `sample` of one IFD (a
     tiff_ifds() dict, main or SubIFD): its segments are read from the file as they are, nothing
     is decoded here.  A chunky IFD (PlanarConfiguration 1) of S samples per pixel gives
@@ -1424,13 +1496,21 @@ def tiff_plane_spec(path: str, ifd: dict, image_id: int, z: int, c: int, t: int,
     The spec's flags carry TIFF_F_J2K_SUBSAMPLED and / or TIFF_F_J2K_YCBCR where the IFD needs them
     and only then.  Without it both are refused by name, as they always were.
     aperio_ycbcr: treat Compression 33003 with three chunky samples as YCbCr whatever the
-    photometric tag says (OpenSlide's rule; off by default because the IFD does not say so)."""
-    return dict(_tiff_segment_rows(path, ifd, 0, None, sample, j2k_packets, j2k_chroma, aperio_ycbcr), image_id=image_id,
-                z=z, c=c, t=t, level=level)
+    photometric tag says (OpenSlide's rule; off by default because the IFD does not say so).
+    packed: take BitsPerSample 1 to 7 (a UINT8 plane) and 9 to 15 (UINT16; SampleFormat 1 or
+    none), Compression 32773 (PackBits) and FillOrder 2: samples are unpacked MSB-first on the
+    GPU, unscaled, as Bio-Formats hands them to the reference.  The spec of such an IFD then
+    carries packed = dict(bits, fill_order) and goes through the pbx_*_tiff_packed calls; every
+    other IFD's is what it always was.  Still refused by name: palette colour, WhiteIsZero on
+    packed samples, Predictor 2 on this path, samples of different widths, signed samples below 8
+    bits.  Without the keyword all of these IFDs are refused with the texts they always were."""
+    return dict(_tiff_segment_rows(path, ifd, 0, None, sample, j2k_packets, j2k_chroma, aperio_ycbcr, packed),
+                image_id=image_id, z=z, c=c, t=t, level=level)
 
 
 def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sample: int = 0,
-                       j2k_packets: bool = False, j2k_chroma: bool = False, aperio_ycbcr: bool = False) -> dict:
+                       j2k_packets: bool = False, j2k_chroma: bool = False, aperio_ycbcr: bool = False,
+                       packed: bool = False) -> dict:
     """What tiff_plane_spec and tiff_band_spec share: the IFD's pixel type, geometry and byte
     order, and segments = (data, offsets) of its segment rows [sr0, sr1) (sr1 None: to the last;
     sr1 == sr0: none, segments is None and the file is not opened), each full width, read from
@@ -1438,7 +1518,7 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
     the rows are those of group `sample`."""
     import numpy as np
     j2k_flags: list = []
-    pt = _tiff_pixel_type(path, ifd, j2k_packets, j2k_chroma, aperio_ycbcr, j2k_flags)
+    pt = _tiff_pixel_type(path, ifd, j2k_packets, j2k_chroma, aperio_ycbcr, j2k_flags, packed)
     spp = ifd["spp"]
     if not 0 <= sample < spp:
         raise PbxError(400, "%s: sample %d outside SamplesPerPixel %d" % (path, sample, spp))
@@ -1472,6 +1552,8 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
         extra["j2k"] = True
         if j2k_flags and j2k_flags[0]:
             extra["flags"] = j2k_flags[0]
+    if packed and _tiff_needs_packed(ifd):  # -> the pbx_*_tiff_packed calls
+        extra["packed"] = dict(bits=ifd["bits"], fill_order=ifd["fillorder"])
     return dict(extra, samples_per_pixel=1 if planar else spp, sample=0 if planar else sample, pixel_type=pt, size_x=ifd["width"], size_y=ifd["length"],
                 big_endian=ifd["byteorder"] == ">", seg_w=ifd["seg_w"], seg_h=ifd["seg_h"],
                 tiled=ifd["tiled"],
@@ -1481,7 +1563,7 @@ def _tiff_segment_rows(path: str, ifd: dict, sr0: int, sr1: Optional[int], sampl
 
 
 def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0, j2k_packets: bool = False,
-                   j2k_chroma: bool = False, aperio_ycbcr: bool = False) -> dict:
+                   j2k_chroma: bool = False, aperio_ycbcr: bool = False, packed: bool = False) -> dict:
     """band_write_tiff() arguments for rows [y0, y0 + rows) of the plane that is sample `sample`
     of one IFD (a tiff_ifds() dict, main or SubIFD; samples_per_pixel and sample as
     tiff_plane_spec, and of a planar IFD only that sample's segments are read): pixel_type, size_x, size_y, big_endian (the file's byte order),
@@ -1490,12 +1572,14 @@ def tiff_band_spec(path: str, ifd: dict, y0: int, rows: int, sample: int = 0, j2
     ranges of the file are read.  rows == 0 reads nothing (segments is None): the geometry and
     byte order alone (of a Compression-7 IFD also segment 0, whose header decides whether the file
     can be loaded at all).  PbxError 400 as tiff_plane_spec, and for rows outside the plane.
-    j2k_packets, j2k_chroma, aperio_ycbcr: as tiff_plane_spec's."""
+    j2k_packets, j2k_chroma, aperio_ycbcr, packed: as tiff_plane_spec's (a packed IFD's spec
+    carries `packed`, band_write_tiff's keyword of that name)."""
     if rows < 0 or y0 < 0 or y0 + rows > ifd["length"]:
         raise PbxError(400, "%s: rows %d+%d outside the image (%d rows)" % (path, y0, rows, ifd["length"]))
     sr0 = y0 // ifd["seg_h"]
     sr1 = -(-(y0 + rows) // ifd["seg_h"]) if rows else sr0
-    return dict(_tiff_segment_rows(path, ifd, sr0, sr1, sample, j2k_packets, j2k_chroma, aperio_ycbcr), y0=y0, rows=rows)
+    return dict(_tiff_segment_rows(path, ifd, sr0, sr1, sample, j2k_packets, j2k_chroma, aperio_ycbcr, packed),
+                y0=y0, rows=rows)
 
 
 def _ome_layout(path: str, xml: str, samples: int = 1) -> Optional[dict]:
@@ -1570,7 +1654,8 @@ def _ome_layout(path: str, xml: str, samples: int = 1) -> Optional[dict]:
     return dict(size_z=sz, size_c=sc, size_t=st, planes=planes, pixel_type=PIXEL_TYPES.index(typ), size_xy=sxy)
 
 
-def tiff_image_layout(path: str, j2k_packets: bool = False, j2k_chroma: bool = False, aperio_ycbcr: bool = False) -> dict:
+def tiff_image_layout(path: str, j2k_packets: bool = False, j2k_chroma: bool = False, aperio_ycbcr: bool = False,
+                      packed: bool = False) -> dict:
     """What register_tiff_image and TiffSource make of a file: ifds (tiff_ifds), planes = the
     (z, c, t) of main IFD k's first sample, samples = S (SamplesPerPixel, the same in every IFD),
     size_z / size_c / size_t, pixel_type, levels (1 + SubIFDs per main IFD).  Every sample is a
@@ -1578,9 +1663,10 @@ def tiff_image_layout(path: str, j2k_packets: bool = False, j2k_chroma: bool = F
     c % S.  OME-TIFF: the first Image's SizeZ/C/T and DimensionOrder, IFD k = channel group k in
     that order.  Any other multi-page TIFF: page k is t = k and size_c = S (Bio-Formats'
     BaseTiffReader puts the pages of a plain TIFF on the time axis).  j2k_packets, j2k_chroma,
-    aperio_ycbcr: as tiff_plane_spec's, for the header checks of JPEG 2000 IFDs."""
+    aperio_ycbcr: as tiff_plane_spec's, for the header checks of JPEG 2000 IFDs; packed: as
+    tiff_plane_spec's."""
     ifds = tiff_ifds(path)
-    pt = _tiff_pixel_type(path, ifds[0], j2k_packets, j2k_chroma, aperio_ycbcr)
+    pt = _tiff_pixel_type(path, ifds[0], j2k_packets, j2k_chroma, aperio_ycbcr, packed=packed)
     S = ifds[0]["spp"]
     ome = _ome_layout(path, ifds[0]["description"], S) if ifds[0]["description"] else None
     if ome is not None:
@@ -1596,7 +1682,7 @@ def tiff_image_layout(path: str, j2k_packets: bool = False, j2k_chroma: bool = F
     out["samples"] = S
     first = out["ifds"][0]
     for k, d in enumerate(out["ifds"]):
-        if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d, j2k_packets, j2k_chroma, aperio_ycbcr) != pt:
+        if (d["width"], d["length"]) != (first["width"], first["length"]) or _tiff_pixel_type(path, d, j2k_packets, j2k_chroma, aperio_ycbcr, packed=packed) != pt:
             raise PbxError(400, "%s: IFD %d differs from the first in size or pixel type" % (path, k))
         for sd in [d] + d["subifds"]:
             if sd["spp"] != S:
@@ -1910,9 +1996,13 @@ class PixelsService:
         registrations, the others first, undone if the JPEG one fails.  Specs that carry j2k = True
         are JPEG 2000 segments (compression TIFF_J2K, UINT8 or UINT16 planes, samples_per_pixel 1
         or 3) and go through pbx_planes_register_tiff_j2k, a registration of their own after
-        those, in the same way.  All are
+        those, in the same way.  Specs that carry packed = dict(bits[, fill_order]) hold rows of
+        bit-packed samples (bits 1 .. 16, padded to a byte per row; compression may also be
+        TIFF_PACKBITS) and go through pbx_planes_register_tiff_packed, a registration of their
+        own after those, in the same way.  All are
         registered or none.  Returns the plane ids (and the kernels' device ms with timing=True)."""
-        jp = [2 if p.get("j2k") else 1 if p.get("jpeg") is not None else 0 for p in planes]
+        jp = [3 if p.get("packed") is not None else 2 if p.get("j2k") else 1 if p.get("jpeg") is not None else 0
+              for p in planes]
         if len(set(jp)) > 1:
             ids = [0] * len(planes)
             done: List[int] = []
@@ -1945,6 +2035,16 @@ class PixelsService:
         del keep
         return (list(ids), (ms[0], ms[1])) if timing else list(ids)
 
+    def register_tiff_planes_packed(self, planes: Sequence[dict], timing: bool = False):
+        """pbx_planes_register_tiff_packed: register_tiff_planes for specs that all carry packed =
+        dict(bits[, fill_order]) (tiff_plane_spec with packed=True on an IFD of 1- to 15-bit
+        samples, PackBits segments or FillOrder 2).  predictor must be 1; pixel_type UINT8 / INT8
+        for bits <= 8, UINT16 / INT16 above."""
+        for k, p in enumerate(planes):
+            if p.get("packed") is None:
+                raise PbxError(400, "plane %d: no `packed` in its spec" % k)
+        return self._register_tiff_samples(planes, timing)
+
     def _register_tiff_samples(self, planes: Sequence[dict], timing: bool):
         n = len(planes)
         descs = (PbxPlaneDesc * n)()
@@ -1960,7 +2060,8 @@ class PixelsService:
                 if spp > 1:
                     layer_of[id(p["segments"])] = l
             elif any(layers[l].get(f) != p.get(f) for f in ("samples_per_pixel", "seg_w", "seg_h", "tiled",
-                                                             "compression", "predictor", "jpeg", "j2k", "flags")):
+                                                             "compression", "predictor", "jpeg", "j2k", "flags",
+                                                             "packed")):
                 raise PbxError(400, "plane %d: shares its segments with plane %d but not their layout"
                                % (k, planes.index(layers[l])))
             if not (0 <= sample < 2 ** 32):
@@ -1976,7 +2077,12 @@ class PixelsService:
             spps[l] = p.get("samples_per_pixel", 1)
         ids = (ctypes.c_uint64 * n)()
         ms = (ctypes.c_double * 2)()
-        if layers[0].get("j2k"):  # (all of them: register_tiff_planes)
+        if layers[0].get("packed") is not None:  # (all of them: register_tiff_planes)
+            pks = (PbxTiffPacked * nl)()
+            for l, p in enumerate(layers):
+                _fill_tiff_packed(pks[l], p["packed"], spps[l])
+            _check(lib().pbx_planes_register_tiff_packed(self._h, n, descs, rf, nl, sgs, pks, ids, ms))
+        elif layers[0].get("j2k"):  # (all of them)
             _check(lib().pbx_planes_register_tiff_j2k(self._h, n, descs, rf, nl, sgs, spps, ids, ms))
         elif layers[0].get("jpeg") is not None:  # (all of them)
             jps = (PbxTiffJpeg * nl)()
@@ -1989,7 +2095,8 @@ class PixelsService:
         return (list(ids), (ms[0], ms[1])) if timing else list(ids)
 
     def register_tiff_image(self, path: str, image_id: int, j2k_packets: bool = True, j2k_chroma: bool = True,
-                            aperio_ycbcr: bool = False) -> Dict[int, Dict[Tuple[int, int, int], int]]:
+                            aperio_ycbcr: bool = False,
+                            packed: bool = True) -> Dict[int, Dict[Tuple[int, int, int], int]]:
         """A whole TIFF / OME-TIFF file -- what the ordinary PixelsService opens through
         Bio-Formats for an image without an NGFF fileset (config.yaml:18) -- in ONE set of GPU
         launches: every plane of every level (tiff_image_layout: OME-XML axes, or page k = t;
@@ -1999,13 +2106,17 @@ class PixelsService:
         planes.  All are registered, or none.  Returns {level: {(z, c, t): plane id}}, as
         register_ngff_image.  j2k_packets (default on here, where whole files are served): JPEG
         2000 IFDs are read with tiff_plane_spec's keyword of that name.  j2k_chroma (default on
-        here too) and aperio_ycbcr (off: the IFD does not say so): likewise."""
-        lay = tiff_image_layout(path, j2k_packets, j2k_chroma, aperio_ycbcr)
+        here too) and aperio_ycbcr (off: the IFD does not say so): likewise.  packed (default on
+        here too): bit-packed samples, PackBits and FillOrder 2 are read with tiff_plane_spec's
+        keyword of that name."""
+        lay = tiff_image_layout(path, j2k_packets, j2k_chroma, aperio_ycbcr, **({"packed": True} if packed else {}))
 
         def plane_spec(d, *a, **kw):  # (the keywords only where they mean something)
             if d["compression"] in _TIFF_J2K_COMPRESSIONS:
                 kw.update({k: True for k, v in (("j2k_packets", j2k_packets), ("j2k_chroma", j2k_chroma),
                                                 ("aperio_ycbcr", aperio_ycbcr)) if v})
+            if packed and _tiff_needs_packed(d):
+                kw["packed"] = True
             return tiff_plane_spec(path, d, *a, **kw)
         specs, keys = [], []
         for (z, c, t), ifd in zip(lay["planes"], lay["ifds"]):
@@ -2149,7 +2260,7 @@ class PixelsService:
     def band_write_tiff(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
                         compression: int, predictor: int, segments, timing: bool = False,
                         samples_per_pixel: int = 1, sample: int = 0, jpeg: Optional[Mapping] = None,
-                        j2k: bool = False, flags: int = 0):
+                        j2k: bool = False, flags: int = 0, packed: Optional[Mapping] = None):
         """pbx_band_write_tiff: rows [y0, y0 + rows) of one band, decoded on the GPU from the TIFF
         segment rows y0 // seg_h .. ceil((y0 + rows) / seg_h) - 1 that cover them (strips, or
         rows of tiles at full width, C order: a sequence of bytes, or pack_chunks()' (data,
@@ -2158,7 +2269,12 @@ class PixelsService:
         With samples_per_pixel > 1 the segments are chunky and hold that many interleaved samples
         per pixel, of which only `sample` is written (pbx_band_write_tiff_sample).
         flags: a spec's `flags` (TIFF_F_J2K_PACKETS on JPEG 2000 segments).
+        packed: a spec's `packed` dict (bits[, fill_order]): band_write_tiff_packed.
         With timing=True returns the decoders' and the placement's device ms."""
+        if packed is not None:
+            return self.band_write_tiff_packed(plane_id, y0, rows, seg_w, seg_h, tiled, compression, segments,
+                                               packed["bits"], packed.get("fill_order", 1), samples_per_pixel,
+                                               sample, predictor=predictor, flags=flags, timing=timing)
         s = PbxTiffSegments()
         kept = _fill_tiff_segments(s, dict(seg_w=seg_w, seg_h=seg_h, tiled=tiled, compression=compression,
                                            predictor=predictor, flags=flags, segments=segments))
@@ -2177,6 +2293,25 @@ class PixelsService:
         else:
             _check(lib().pbx_band_write_tiff_sample(self._h, plane_id, y0, rows, ctypes.byref(s),
                                                     samples_per_pixel, sample, ms))
+        del kept
+        return [ms[0], ms[1]] if timing else None
+
+    def band_write_tiff_packed(self, plane_id: int, y0: int, rows: int, seg_w: int, seg_h: int, tiled: bool,
+                               compression: int, segments, bits: int, fill_order: int = 1,
+                               samples_per_pixel: int = 1, sample: int = 0, predictor: int = 1, flags: int = 0,
+                               timing: bool = False):
+        """pbx_band_write_tiff_packed: band_write_tiff for segment rows of bit-packed samples
+        (bits 1 .. 16, MSB first, every row padded to a byte; fill_order 2: the bits of every
+        byte reversed) under compression 1, 5, 8, 50000 or TIFF_PACKBITS.  Of samples_per_pixel
+        chunky samples only `sample` is written.  With timing=True returns the decoders' and the
+        placement's device ms."""
+        s = PbxTiffSegments()
+        kept = _fill_tiff_segments(s, dict(seg_w=seg_w, seg_h=seg_h, tiled=tiled, compression=compression,
+                                           predictor=predictor, flags=flags, segments=segments))
+        k = PbxTiffPacked()
+        _fill_tiff_packed(k, dict(bits=bits, fill_order=fill_order), samples_per_pixel, sample)
+        ms = (ctypes.c_double * 2)()
+        _check(lib().pbx_band_write_tiff_packed(self._h, plane_id, y0, rows, ctypes.byref(s), ctypes.byref(k), ms))
         del kept
         return [ms[0], ms[1]] if timing else None
 
@@ -2339,7 +2474,9 @@ class PixelsService:
                                                      sample=tsp.get("sample", 0),
                                                      **({"jpeg": tsp["jpeg"]} if tsp.get("jpeg") is not None else {}),
                                                      **({"j2k": True} if tsp.get("j2k") else {}),
-                                                     **({"flags": tsp["flags"]} if tsp.get("flags") else {}))
+                                                     **({"flags": tsp["flags"]} if tsp.get("flags") else {}),
+                                                     **({"packed": tsp["packed"]} if tsp.get("packed") is not None
+                                                        else {}))
                             elif sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
@@ -2765,9 +2902,10 @@ class TiffSource(PixelSource):
     band_write_tiff).  Either way every byte of pixel data is decoded on the GPU."""
 
     def __init__(self, images: Mapping[int, str], j2k_packets: bool = True, j2k_chroma: bool = True,
-                 aperio_ycbcr: bool = False):
+                 aperio_ycbcr: bool = False, packed: bool = True):
         import threading
         self.images = dict(images)
+        self.packed = packed  # bit-packed samples, PackBits, FillOrder 2: tiff_plane_spec's keyword of this name
         self.j2k_packets = j2k_packets  # JPEG 2000 IFDs: tiff_plane_spec's keywords of these names
         self.j2k_chroma = j2k_chroma
         self.aperio_ycbcr = aperio_ycbcr
@@ -2779,7 +2917,8 @@ class TiffSource(PixelSource):
             lay = self._opened.get(image_id)
             if lay is None:
                 lay = self._opened[image_id] = tiff_image_layout(self.images[image_id], self.j2k_packets, self.j2k_chroma,
-                                                                  self.aperio_ycbcr)
+                                                                  self.aperio_ycbcr,
+                                                                  **({"packed": True} if self.packed else {}))
             return lay
 
     def get_pixels(self, image_id: int) -> Optional[Pixels]:
@@ -2802,9 +2941,10 @@ class TiffSource(PixelSource):
         return d["width"], d["length"]
 
     def _j2k_kw(self, ifd: dict) -> dict:
-        """(the keywords only for a JPEG 2000 IFD: every other file is the call it always was)"""
+        """(the keywords only for a JPEG 2000 IFD, `packed` only for an IFD that needs it: every
+        other file is the call it always was)"""
         if ifd["compression"] not in _TIFF_J2K_COMPRESSIONS:
-            return {}
+            return {"packed": True} if self.packed and _tiff_needs_packed(ifd) else {}
         return {k: True for k in ("j2k_packets", "j2k_chroma", "aperio_ycbcr") if getattr(self, k)}
 
     def plane_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Optional[dict]:

@@ -64,7 +64,7 @@ int main() {
     P.j2cons = 7;
     P.j2nodes = 11;
     const LaunchLayout L(P, 1000);
-    check("counts by kind", same(L.counts, {0, 2, 0, 0, 1, 3, 0}));
+    check("counts by kind", same(L.counts, {0, 2, 0, 0, 1, 3, 0, 0}));
     bool order = L.streams.size() == 6;
     for (size_t k = 0; order && k < 6; k++) order = L.streams[k].dst_off == 100 + k;
     check("streams: zlib, zstd, gzip, each kind in the plan's order", order);
