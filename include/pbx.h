@@ -502,9 +502,9 @@ int pbx_planes_register_tiff_samples(pbx_ctx* ctx, uint64_t n, const pbx_plane_d
 /* pbx_band_write_tiff for chunky segments of samples_per_pixel samples per pixel: the covering
  * segment rows are decoded for this call and only sample `sample` is written, into the band of
  * `plane_id` (one plane per call, as pbx_band_write_zarr_deep: a cold region of all S channels
- * decodes its segments S times).  Stored segments are read where they were uploaded.  With
- * samples_per_pixel == 1 (sample 0) this is pbx_band_write_tiff.  400 as that call and as
- * pbx_planes_register_tiff_samples. */
+ * decodes its segments S times through this call, once through pbx_band_write_tiff_group).
+ * Stored segments are read where they were uploaded.  With samples_per_pixel == 1 (sample 0) this
+ * is pbx_band_write_tiff.  400 as that call and as pbx_planes_register_tiff_samples. */
 int pbx_band_write_tiff_sample(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                                const pbx_tiff_segments* segs, int32_t samples_per_pixel, int32_t sample,
                                double* kernel_ms);
@@ -671,6 +671,44 @@ int pbx_planes_register_tiff_packed(pbx_ctx* ctx, uint64_t n, const pbx_plane_de
 int pbx_band_write_tiff_packed(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
                                const pbx_tiff_segments* segs, const pbx_tiff_packed* packed,
                                double* kernel_ms);
+/* Band writes that span planes: ONE upload, decode and placement fills the bands of up to four
+ * sparse planes that share the segments (the samples of chunky TIFF segments) or the chunks (the
+ * slices of Zarr chunks that hold several planes), so that a cold RGB region costs one decode and
+ * not three (DESIGN.md §10b "A band load that spans planes").
+ * pbx_band_write_tiff_group: n is the segments' samples per pixel, 1 .. 4 (packed segments:
+ * packed->samples_per_pixel, packed->sample is ignored); plane_ids[s] is the plane of sample s, 0 =
+ * nobody wants that sample.  jpeg: NULL unless Compression 7; j2k non-zero: JPEG 2000 segments;
+ * packed: NULL unless the rows are bit-packed / PackBits / FillOrder 2 -- the codec is chosen as the
+ * four single calls choose it.
+ * pbx_band_write_zarr_group: plane_ids[i] receives slice slices[i] of the covering chunk rows, n is
+ * 1 .. 4, the slices are distinct and lie in [0, chunk_planes).
+ * Both: plane_ids[primary] (a wanted id) is the plane the caller needs; the others are siblings,
+ * filled if they can be.  All members are admitted in one critical section by pbx_band_write's
+ * rule.  If the primary is kept out, no sibling is joined, nothing is uploaded or decoded and its
+ * status is returned; a sibling that is kept out (resident: 409, being allocated or reset by
+ * another caller: 409, reset as stale and the piece not at the band's first row: 500), or whose
+ * band does not fit the residency budget (507, allocated after the primary's), is dropped and the
+ * rest is written.  A failure of the one fill (an upload error, a stream a decoder rejects: 400)
+ * fails the load of every band the call joined; each is reset by its last writer.  The return
+ * value is what the corresponding single call on plane_ids[primary] would have returned, so a
+ * binding's handling of 400 / 404 / 409 / 500 / 507 does not change.  statuses[i] (may be NULL):
+ * PBX_OK (written), the status that kept member i out (409, 500, 507), the failure's status for
+ * a member the failed call had joined, -1 for an id of 0 or a sibling never attempted.  kernel_ms
+ * as in the single calls.  With n == 1 the calls are the single calls.
+ * 400 before anything is joined: null arguments, n outside 1 .. 4 or (packed) not the segments'
+ * samples per pixel, primary out of range or naming an id of 0, the same id (or slice) twice, a
+ * plane that is not sparse, members that disagree on size, pixel type, byte order or band_rows or
+ * whose rows do not lie in one band, and every refusal of the single calls.  404: an unknown id.
+ * Pieces written by any band call may be mixed in one band; a loader that wants a sibling's band
+ * completed uses the group call for every piece of it, and a sibling left partly written goes
+ * stale like any abandoned load. */
+int pbx_band_write_tiff_group(pbx_ctx* ctx, const uint64_t* plane_ids, int32_t n, int32_t primary,
+                              int32_t y0, int32_t rows, const pbx_tiff_segments* segs,
+                              const pbx_tiff_jpeg* jpeg, int32_t j2k, const pbx_tiff_packed* packed,
+                              int32_t* statuses, double* kernel_ms);
+int pbx_band_write_zarr_group(pbx_ctx* ctx, const uint64_t* plane_ids, const int32_t* slices, int32_t n,
+                              int32_t primary, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
+                              int32_t chunk_planes, int32_t* statuses, double* kernel_ms);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -896,8 +934,19 @@ int pbx_test_fail_batch(pbx_ctx* ctx, uint64_t ahead);
 int pbx_test_stall_batch(pbx_ctx* ctx, uint64_t ahead);
 /* Upload failure injection (test hook): the `ahead`-th pbx_band_write, pbx_band_write_zarr or
  * pbx_band_write_tiff from now on fails after joining its band's load, as a failed
- * host-to-device copy would.  0 disables. */
+ * host-to-device copy would.  A group call (pbx_band_write_tiff_group / _zarr_group) counts as
+ * one write and fails every band it joined.  0 disables. */
 int pbx_test_fail_band_write(pbx_ctx* ctx, uint64_t ahead);
+/* Test hook, no context and no device: the admission decision of a band write that spans planes
+ * (pbx_band_write_tiff_group / _zarr_group; csrc/band_state.h) on band descriptions given as plain
+ * integers.  bands: n x 6 values, per member {state (0 absent, 1 loading, 2 resident), the band's
+ * HBM is there, writers in flight, failed, stale_reset, idle past the stale limit}; first_row: the
+ * piece starts at the band's first row.  out[i]: 1 = join and allocate, 2 = join as one more
+ * writer, 409, 500, or -1 for a sibling that is never attempted because the primary is kept out.
+ * 400: null arguments, n outside 1 .. 4, primary outside the group, a state outside 0 .. 2 or
+ * negative writers. */
+int pbx_test_band_group_admit(const int32_t* bands, int32_t n, int32_t primary, int32_t first_row,
+                              int32_t* out);
 
 /* Request sharding across GPUs (one process per GPU, no collectives): the rank that
  * owns a request, by hash of (image, z, c, t, tile column, tile row) for tile_w x tile_h

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/pbx.h"
+#include "band_state.h"
 #include "pbx_common.h"
 #include "pbx_config.h"
 #include "pbx_kernels.h"
@@ -58,13 +59,6 @@ enum PlaneState : int {
     PS_EVICTED = 2   // key still registered, HBM returned (NOT_RESIDENT until re-registered)
 };
 
-// One row band of a sparse plane (pbx_plane_create_sparse): rows [k*B, (k+1)*B) of the plane
-// (clipped to the plane and to the context's owned rows), loaded on demand, pinned by the
-// batches that read it and evicted on its own (region-proportional residency: a request
-// loads only the bands its rows cover, as getTileDirect reads only the requested region,
-// TileRequestHandler.java:102-109).
-enum BandState : int { BS_ABSENT = 0, BS_LOADING = 1, BS_READY = 2 };
-
 // A plane or band that has just been loaded is not evicted until a batch has read it, or
 // FRESH_NS has passed (a loader that went away): otherwise, under a budget smaller than the
 // working set, concurrent loaders evict each other's planes between the load and the retry
@@ -79,24 +73,6 @@ inline int64_t mono_ns() {
     return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch())
         .count();
 }
-
-struct Band {
-    uint8_t* dev = nullptr;      // the band's rows at the plane's pitch + 256 B slack
-    size_t bytes = 0;
-    int state = BS_ABSENT;
-    int64_t pins = 0;            // planned batches that read it
-    uint64_t last_use = 0;
-    int64_t fresh_until = 0;     // loaded, not served yet: not evicted before this (fresh_now)
-    uint32_t rows_left = 0;      // BS_LOADING: rows not written yet
-    int32_t writers = 0;         // pbx_band_write calls in flight
-    bool failed = false;         // BS_LOADING: a write failed; the last writer out resets the band
-    int64_t touched = 0;         // BS_LOADING: mono_ns of the last write activity
-    // the last load went idle past stale_ns and was reset: the next load must start at the
-    // band's first row, so a late piece of the reset load fails instead of starting a load
-    // that could never complete
-    bool stale_reset = false;
-    std::vector<uint8_t> rows_done;
-};
 
 struct Plane {
     uint64_t id = 0;
@@ -1910,14 +1886,7 @@ int pbx_plane_create_sparse(pbx_ctx* ctx, const pbx_plane_desc* d, int32_t band_
 namespace {
 
 // A loading band back to absent (under reg_mu); its HBM goes to `to_free`.
-void band_reset_locked(Band& b, std::vector<std::pair<void*, size_t>>& to_free) {
-    if (b.dev) to_free.emplace_back(b.dev, b.bytes);
-    b.dev = nullptr;
-    b.state = BS_ABSENT;
-    b.rows_done.clear();
-    b.rows_left = 0;
-    b.failed = false;
-}
+void band_reset_locked(Band& b, std::vector<std::pair<void*, size_t>>& to_free) { band_reset(b, to_free); }
 
 // free_planes under reg_mu (the memory goes to the reaper, the bytes stop counting)
 void free_planes_locked(pbx_ctx* ctx, const std::vector<std::pair<void*, size_t>>& to_free) {
@@ -1942,107 +1911,148 @@ int band_of_rows(const Plane* q, int32_t y0, int32_t rows, int32_t* band) {
     return PBX_OK;
 }
 
-// One write of rows [y0, y0 + rows) of band k (band_of_rows) of a sparse plane, whatever fills
-// them: the first write of an absent band allocates it (within the budget, evicting idle planes /
-// bands), the last one publishes it.  `fill(band_dev)` puts the rows into the band (rows
-// [band_lo, band_hi) at the plane's pitch) on ctx->upload_stream and returns once they are
-// there; it runs under ctx->upload_mu.  The caller has checked its own arguments: from here on a
-// failure fails the band's whole load.
+// A member of a band write that spans planes: band k of plane `q` (null: nobody wants the
+// member).  `status` is what the pbx_band_write_*_group calls report for it.
+struct BandMember {
+    Plane* q = nullptr;
+    int status = -1;
+    bool joined = false, alloc = false;
+};
+
+// One write of rows [y0, y0 + rows) of band k (band_of_rows) of up to four sparse planes of one
+// geometry, whatever fills them: the first write of an absent band allocates it (within the
+// budget, evicting idle planes / bands), the last one publishes it.  The caller needs member
+// `primary`; the others are siblings, filled if they can be.  The decisions are band_state.h's:
+//   admission   all members in one critical section; a primary that is kept out ends the call
+//               with its status and nothing is joined, a sibling that is kept out is dropped
+//   allocation  primary first; its 507 fails every joined member, a sibling's 507 fails and drops
+//               that sibling alone
+//   fill        `fill(band_dev)` puts the rows into the bands band_dev[i] (rows [band_lo, band_hi)
+//               at the planes' pitch; null: member i is not written) on ctx->upload_stream and
+//               returns once they are there; it runs once, under ctx->upload_mu.  The caller has
+//               checked its own arguments: from here on a failure fails every joined band's load
+//   completion  member by member in one critical section; a member whose load another writer
+//               failed meanwhile gets 500 and is not published
+// Returns what a write of the primary alone would have.
 template <class Fill>
-int band_load_rows(pbx_ctx* ctx, Plane* q, int32_t k, int32_t y0, int32_t rows, Fill&& fill) {
-    const int32_t lo = q->band_lo(k), hi = q->band_hi(k);
+int band_group_load_rows(pbx_ctx* ctx, BandMember* m, int n, int primary, int32_t k, int32_t y0, int32_t rows,
+                         Fill&& fill) {
+    const Plane* q0 = m[primary].q;
+    const int32_t lo = q0->band_lo(k), hi = q0->band_hi(k);
     if (ensure_device(ctx)) return PBX_E_INTERNAL;
-    Band& b = q->bands[(size_t)k];
-    bool alloc = false;
-    const size_t nbytes = (size_t)q->pitch * (size_t)(hi - lo) + 256;
-    std::vector<std::pair<void*, size_t>> stale;
+    const size_t nbytes = (size_t)q0->pitch * (size_t)(hi - lo) + 256;
+    auto band = [&](int i) -> Band& { return m[i].q->bands[(size_t)k]; };
     {
         std::lock_guard<std::mutex> g(ctx->reg_mu);
-        if (b.state == BS_READY) return fail(PBX_E_EXISTS, "band %d is resident", k);
-        // a load that failed part-way, or whose loader went away, starts over
-        if (b.state == BS_LOADING && b.writers == 0 && (b.failed || mono_ns() - b.touched > ctx->stale_ns)) {
-            if (!b.failed) b.stale_reset = true;
-            band_reset_locked(b, stale);
-        }
-        if (b.state == BS_ABSENT && b.stale_reset && y0 != lo) {
+        BandBlocks stale;
+        const int64_t now = mono_ns();
+        BandView v[4];
+        int who[4], a[4], nw = 0, pw = 0;
+        for (int i = 0; i < n; i++)
+            if (m[i].q) {
+                if (i == primary) pw = nw;
+                who[nw] = i;
+                v[nw++] = band_view(band(i), now, ctx->stale_ns);
+            }
+        band_group_admit(v, nw, pw, y0 == lo, a);
+        if (!band_admitted(a[pw])) {
+            band_reap(band(primary), v[pw], stale);  // a load that failed part-way, or whose loader went away
             free_planes_locked(ctx, stale);
-            return fail(PBX_E_INTERNAL, "band %d: its load was idle for more than %lld ms and was reset; "
-                        "write it again from row %d", k, (long long)(ctx->stale_ns / 1000000), lo);
-        }
-        if (b.state == BS_ABSENT) {
-            b.stale_reset = false;
-            b.state = BS_LOADING;
-            b.failed = false;
-            b.rows_done.assign((size_t)(hi - lo), 0);
-            b.rows_left = (uint32_t)(hi - lo);
-            alloc = true;
-        } else if (!b.dev || b.failed) {
-            free_planes_locked(ctx, stale);
+            m[primary].status = band_admit_status(a[pw]);
+            if (a[pw] == BA_RESIDENT) return fail(PBX_E_EXISTS, "band %d is resident", k);
+            if (a[pw] == BA_STALE)
+                return fail(PBX_E_INTERNAL, "band %d: its load was idle for more than %lld ms and was reset; "
+                            "write it again from row %d", k, (long long)(ctx->stale_ns / 1000000), lo);
             return fail(PBX_E_EXISTS, "band %d is being allocated (or reset) by another caller", k);
         }
-        b.writers++;
-        b.touched = mono_ns();
+        for (int j = 0; j < nw; j++) {
+            BandMember& x = m[who[j]];
+            x.status = band_admit_status(a[j]);
+            if (!band_admitted(a[j])) continue;
+            band_join(band(who[j]), v[j], a[j], hi - lo, now, stale);
+            x.joined = true;
+            x.alloc = a[j] == BA_ALLOC;
+        }
         free_planes_locked(ctx, stale);
     }
-    // A failed write fails the whole load: the band is reset (its HBM returned) by the last
-    // writer to leave, never under another writer's upload.
-    auto leave_failed = [&](int rc) {
+    // A failed write fails the whole load of every band it joined (`only` < 0), or of the one
+    // sibling that is dropped: the band is reset by the last writer to leave.
+    auto leave_failed = [&](int rc, int only) {
         const std::string msg = last_error();
-        std::vector<std::pair<void*, size_t>> to_free;
+        BandBlocks to_free;
         {
             std::lock_guard<std::mutex> g(ctx->reg_mu);
-            b.writers--;
-            b.failed = true;
-            b.touched = mono_ns();
-            if (b.writers == 0) band_reset_locked(b, to_free);
+            const int64_t now = mono_ns();
+            for (int i = 0; i < n; i++)
+                if (m[i].joined && (only < 0 || i == only)) {
+                    band_leave_failed(band(i), now, to_free);
+                    m[i].joined = false;
+                    m[i].status = rc;
+                }
             free_planes_locked(ctx, to_free);
         }
         last_error() = msg;
         return rc;
     };
-    if (alloc) {
+    for (int j = 0; j < n; j++) {
+        const int i = j == 0 ? primary : j <= primary ? j - 1 : j;  // the primary first
+        if (!m[i].joined || !m[i].alloc) continue;
         uint8_t* dev = nullptr;
-        if (int rc = plane_alloc(ctx, nbytes, &dev)) return leave_failed(rc);
+        const std::string before = last_error();
+        if (int rc = plane_alloc(ctx, nbytes, &dev)) {
+            if (i == primary) return leave_failed(rc, -1);
+            leave_failed(rc, i);
+            last_error() = before;  // a dropped sibling is no error of the call's
+            continue;
+        }
         std::lock_guard<std::mutex> g(ctx->reg_mu);
-        b.dev = dev;
-        b.bytes = nbytes;
+        band(i).dev = dev;
+        band(i).bytes = nbytes;
     }
     hipError_t e = hipSuccess;
     int rc = PBX_OK;
     if (++ctx->band_writes == ctx->fail_band_write_at.load())  // test hook: this write's upload fails
         return leave_failed(fail(PBX_E_INTERNAL, "injected upload failure in band write %llu",
-                                 (unsigned long long)ctx->band_writes.load()));
+                                 (unsigned long long)ctx->band_writes.load()), -1);
     {
         std::lock_guard<std::mutex> u(ctx->upload_mu);
-        if (alloc) e = hipMemsetAsync(b.dev + (size_t)q->pitch * (size_t)(hi - lo), 0, 256, ctx->upload_stream);
-        if (e == hipSuccess) rc = fill(b.dev);
+        uint8_t* devs[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int i = 0; i < n; i++) {
+            if (!m[i].joined) continue;
+            devs[i] = band(i).dev;
+            if (m[i].alloc && e == hipSuccess)
+                e = hipMemsetAsync(devs[i] + (size_t)q0->pitch * (size_t)(hi - lo), 0, 256, ctx->upload_stream);
+        }
+        if (e == hipSuccess) rc = fill(devs);
     }
     if (e != hipSuccess) rc = fail(PBX_E_INTERNAL, "band write: %s", hipGetErrorString(e));
-    if (rc) return leave_failed(rc);
+    if (rc) return leave_failed(rc, -1);
     std::lock_guard<std::mutex> g(ctx->reg_mu);
-    if (b.failed || b.state != BS_LOADING || b.rows_done.size() != (size_t)(hi - lo)) {
-        // another writer failed meanwhile: this load is void; the last writer out resets it
-        std::vector<std::pair<void*, size_t>> to_free;
-        b.writers--;
-        if (b.writers == 0) band_reset_locked(b, to_free);
-        free_planes_locked(ctx, to_free);
-        return fail(PBX_E_INTERNAL, "band %d: another write of this load failed; load it again", k);
-    }
-    b.writers--;
-    b.touched = mono_ns();
-    for (int32_t r = y0 - lo; r < y0 - lo + rows; r++)
-        if (!b.rows_done[(size_t)r]) {
-            b.rows_done[(size_t)r] = 1;
-            b.rows_left--;
+    BandBlocks to_free;
+    const int64_t now = mono_ns();
+    for (int i = 0; i < n; i++) {
+        if (!m[i].joined) continue;
+        Band& b = band(i);
+        const int done = band_complete(b, hi - lo, y0 - lo, rows, now, to_free);
+        m[i].status = done == BD_VOID ? (int)PBX_E_INTERNAL : (int)PBX_OK;
+        if (done == BD_PUBLISHED) {  // the last write publishes it
+            b.last_use = ++ctx->use_tick;
+            b.fresh_until = now + FRESH_NS;
         }
-    if (b.rows_left == 0 && b.writers == 0) {  // the last write publishes it
-        b.rows_done.clear();
-        b.rows_done.shrink_to_fit();
-        b.state = BS_READY;
-        b.last_use = ++ctx->use_tick;
-        b.fresh_until = mono_ns() + FRESH_NS;
     }
+    free_planes_locked(ctx, to_free);
+    // another writer failed meanwhile: this load is void; the last writer out resets it
+    if (m[primary].status != PBX_OK)
+        return fail(PBX_E_INTERNAL, "band %d: another write of this load failed; load it again", k);
     return PBX_OK;
+}
+
+// The write of one plane's band: a group of one.  `fill(band_dev)` as above, for the one band.
+template <class Fill>
+int band_load_rows(pbx_ctx* ctx, Plane* q, int32_t k, int32_t y0, int32_t rows, Fill&& fill) {
+    BandMember m;
+    m.q = q;
+    return band_group_load_rows(ctx, &m, 1, 0, k, y0, rows, [&](uint8_t* const* band_dev) { return fill(band_dev[0]); });
 }
 
 // pbx_band_write: packed host rows, or (data == NULL on a generator plane) rows generated on
@@ -2117,6 +2127,52 @@ int with_sparse_plane(pbx_ctx* ctx, uint64_t id, Write&& write) {
     rc = write(q);
     const std::string msg = last_error();
     unpin_one(ctx, q);
+    last_error() = msg;
+    return rc;
+}
+
+// The planes of a group call, pinned: checks n, primary and the ids (0: nobody wants the member),
+// pins every wanted plane as with_sparse_plane does, checks that band_of_rows puts the rows in one
+// band of each and that the members agree on what the one fill depends on, runs
+// write(members, band) and unpins; the members' statuses go to `statuses` (may be null), the
+// thread's last error stays the write's.
+template <class Write>
+int with_sparse_group(pbx_ctx* ctx, const uint64_t* ids, int32_t n, int32_t primary, int32_t y0, int32_t rows,
+                      int32_t* statuses, Write&& write) {
+    if (n < 1 || n > 4) return fail(PBX_E_BADARG, "group of %d planes outside 1 .. 4", n);
+    if (statuses)
+        for (int32_t i = 0; i < n; i++) statuses[i] = -1;
+    if (primary < 0 || primary >= n) return fail(PBX_E_BADARG, "primary %d outside the group of %d", primary, n);
+    if (!ids[primary]) return fail(PBX_E_BADARG, "primary %d names plane id 0 (nobody wants that member)", primary);
+    for (int32_t i = 0; i < n; i++)
+        for (int32_t j = 0; j < i; j++)
+            if (ids[i] && ids[i] == ids[j])
+                return fail(PBX_E_BADARG, "plane %llu is members %d and %d of the group", (unsigned long long)ids[i], j, i);
+    BandMember m[4];
+    int rc = PBX_OK;
+    for (int32_t i = 0; i < n && !rc; i++) {
+        if (!ids[i]) continue;
+        m[i].q = pin_id(ctx, ids[i], 1u << PS_READY, &rc);  // (a plane without bands: band_of_rows below)
+    }
+    int32_t k = 0;
+    const Plane* p = m[primary].q;
+    for (int32_t i = 0; i < n && !rc; i++) {
+        const Plane* q = m[i].q;
+        if (!q) continue;
+        int32_t kq = 0;
+        if (q->sparse_rows && p->sparse_rows &&
+            (q->size_x != p->size_x || q->size_y != p->size_y || q->pixel_type != p->pixel_type ||
+             q->little_endian != p->little_endian || q->sparse_rows != p->sparse_rows))
+            rc = fail(PBX_E_BADARG, "planes %llu and %llu differ in size, pixel type, byte order or band rows",
+                      (unsigned long long)q->id, (unsigned long long)p->id);
+        if (!rc) rc = band_of_rows(q, y0, rows, i == primary ? &k : &kq);
+    }
+    if (!rc) rc = write(m, k);
+    const std::string msg = last_error();
+    for (int32_t i = 0; i < n; i++) {
+        if (statuses && m[i].q) statuses[i] = m[i].status;
+        if (m[i].q) unpin_one(ctx, m[i].q);
+    }
     last_error() = msg;
     return rc;
 }
@@ -2490,44 +2546,73 @@ int zarr_decode_place(pbx_ctx* ctx, hipStream_t st, const ZarrPlan& P, const std
     return PBX_OK;
 }
 
-// pbx_band_write_zarr: the piece's covering chunk rows are planned on the host first (a
-// malformed piece never joins the band's load), then uploaded, decoded and placed under the
-// band state machine of band_load_rows, with the piece's rows as the placement window.
+// pbx_band_write_zarr, its _deep form (a group of one) and pbx_band_write_zarr_group: member i
+// (m[i].q, null: not wanted) receives slice slices[i] of the chunks; the caller has checked the
+// members (band k holds the rows in each), z and the slices.  The piece's covering chunk rows are
+// planned on the host first (a malformed piece never joins a band's load), then uploaded, decoded
+// and placed once under the band state machine of band_group_load_rows, with the piece's rows as
+// the placement window of every member that joined.
+int band_write_zarr_members(pbx_ctx* ctx, BandMember* m, const int32_t* slices, int n, int primary, int32_t k,
+                            int32_t y0, int32_t rows, const pbx_zarr_chunks* z, int32_t depth, double* kernel_ms) {
+    const Plane* q = m[primary].q;
+    const int bpp = bpp_of(q->pixel_type);
+    const SourceGrid g = source_grid(z, q->size_x, q->size_y, y0, rows);
+    // one ZChunk per chunk and member in `use`, on plane number = the member's place among them
+    auto plan = [&](const bool* use, ZarrPlan& P) {
+        std::vector<ZarrWant> want;
+        for (int i = 0; i < n; i++)
+            if (use[i]) want.push_back(ZarrWant{(uint32_t)slices[i], (uint32_t)want.size()});
+        return zarr_plan(q->size_x, z, bpp, 0, g.r0, g.r1, depth, want, y0, (int64_t)y0 + rows, P);
+    };
+    bool wanted[4] = {false, false, false, false};
+    for (int i = 0; i < n; i++) wanted[i] = m[i].q != nullptr;
+    ZarrPlan P;
+    if (int rc = plan(wanted, P)) return rc;
+    const uint64_t len = (g.used + 15) & ~15ull;
+    const std::vector<ZarrInput> in{ZarrInput{z->data, g.used, 0, len}};
+    return band_group_load_rows(ctx, m, n, primary, k, y0, rows, [&](uint8_t* const* band_dev) {
+        // rows keep their plane index: the destination is the band's virtual base, as in the
+        // tile kernels (pitch and the allocation are 256-byte aligned, so is the base)
+        std::vector<ZPlane> zp;
+        bool joined[4] = {false, false, false, false}, all = true;
+        for (int i = 0; i < n; i++) {
+            joined[i] = band_dev[i] != nullptr;
+            all = all && joined[i] == wanted[i];
+            if (joined[i])
+                zp.push_back(ZPlane{band_dev[i] - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x, q->size_y,
+                                    z->chunk_x, z->chunk_y, (uint32_t)bpp, 0,
+                                    zarr_fill(z->fill_bits, bpp, q->little_endian), y0, y0 + rows});
+        }
+        if (all) return zarr_decode_place(ctx, ctx->upload_stream, P, zp, in, len, z->chunk_y, kernel_ms);
+        ZarrPlan J;  // a sibling was kept out: the plan of those that joined
+        if (int rc = plan(joined, J)) return rc;
+        return zarr_decode_place(ctx, ctx->upload_stream, J, zp, in, len, z->chunk_y, kernel_ms);
+    });
+}
+
 int band_write_zarr(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
                     int32_t depth, int32_t slice, double* kernel_ms) {
     int32_t k = 0;
     if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
     if (int rc = zarr_chunks_check(z)) return rc;
     if (int rc = zarr_slice_check(depth, slice)) return rc;
-    const int bpp = bpp_of(q->pixel_type);
-    const SourceGrid g = source_grid(z, q->size_x, q->size_y, y0, rows);
-    ZarrPlan P;
-    if (int rc = zarr_plan(q->size_x, z, bpp, 0, g.r0, g.r1, depth, {ZarrWant{(uint32_t)slice, 0}}, y0,
-                           (int64_t)y0 + rows, P))
-        return rc;
-    const uint64_t len = (g.used + 15) & ~15ull;
-    const std::vector<ZarrInput> in{ZarrInput{z->data, g.used, 0, len}};
-    return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
-        // rows keep their plane index: the destination is the band's virtual base, as in the
-        // tile kernels (pitch and the allocation are 256-byte aligned, so is the base)
-        const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
-                                            q->size_y, z->chunk_x, z->chunk_y, (uint32_t)bpp, 0,
-                                            zarr_fill(z->fill_bits, bpp, q->little_endian), y0, y0 + rows}};
-        return zarr_decode_place(ctx, ctx->upload_stream, P, zp, in, len, z->chunk_y, kernel_ms);
-    });
+    BandMember m;
+    m.q = q;
+    return band_write_zarr_members(ctx, &m, &slice, 1, 0, k, y0, rows, z, depth, kernel_ms);
 }
 
-// pbx_band_write_tiff and its _sample, _jpeg and _j2k forms: pbx_band_write_zarr for segment
-// rows.  The piece's covering segment rows are checked and planned on the host first by the
-// codec `c` names (a malformed piece never joins the band's load), then uploaded, decoded and
-// placed under the band state machine of band_load_rows.  With spp > 1 the segments are chunky
-// and only component `sample` is written (the others' destinations are null); those, and JPEG and
-// JPEG 2000 segments of any spp, reach the band through the launch's one TSplitDst entry.
-int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const TiffCodec& c, int32_t spp,
-                    int32_t sample, double* kernel_ms) {
-    int32_t k = 0;
-    if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
-    if (int rc = tiff_codec_check(c, q->pixel_type, spp, sample, q->id)) return rc;
+// pbx_band_write_tiff, its _sample, _jpeg, _j2k and _packed forms (a group of one) and
+// pbx_band_write_tiff_group: pbx_band_write_zarr for segment rows.  Member s (m[s].q, null: not
+// wanted) is sample s of the segments' spp; the caller has checked the members (band k holds the
+// rows in each) and the codec `c` names (tiff_codec_check).  The piece's covering segment rows are
+// planned on the host first by that codec (a malformed piece never joins a band's load), then
+// uploaded, decoded and placed once under the band state machine of band_group_load_rows.  With
+// spp > 1 the segments are chunky and the components of the members that joined are written (the
+// others' destinations are null); those, and JPEG, JPEG 2000 and bit-packed segments of any spp,
+// reach the bands through the launch's one TSplitDst entry.
+int band_write_tiff_members(pbx_ctx* ctx, BandMember* m, int32_t spp, int primary, int32_t k, int32_t y0,
+                            int32_t rows, const TiffCodec& c, double* kernel_ms) {
+    const Plane* q = m[primary].q;
     const pbx_tiff_segments* s = c.s;
     const int bpp = bpp_of(q->pixel_type);
     const SourceGrid g = source_grid(s, q->size_x, q->size_y, y0, rows);
@@ -2536,19 +2621,31 @@ int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const Tiff
         return rc;
     const uint64_t len = (g.used + 15) & ~15ull;
     const std::vector<ZarrInput> in{ZarrInput{s->data, g.used, 0, len}};
-    return band_load_rows(ctx, q, k, y0, rows, [&](uint8_t* band_dev) {
+    return band_group_load_rows(ctx, m, spp, primary, k, y0, rows, [&](uint8_t* const* band_dev) {
         // rows keep their plane index: the destination is the band's virtual base
-        const std::vector<ZPlane> zp{ZPlane{band_dev - (int64_t)q->band_lo(k) * q->pitch, q->pitch, q->size_x,
-                                            q->size_y, s->seg_w, s->seg_h, (uint32_t)bpp, 0, 0, y0, y0 + rows}};
+        const int64_t back = (int64_t)q->band_lo(k) * q->pitch;
+        const std::vector<ZPlane> zp{ZPlane{band_dev[primary] - back, q->pitch, q->size_x, q->size_y, s->seg_w, s->seg_h,
+                                            (uint32_t)bpp, 0, 0, y0, y0 + rows}};
         std::vector<TSplitDst> sd;
         if (spp > 1 || c.jpeg || c.j2k || c.packed) {
             sd.push_back(TSplitDst{{nullptr, nullptr, nullptr, nullptr}, q->pitch, q->size_x, q->size_y, y0, y0 + rows,
                                    (uint32_t)bpp, q->little_endian ? 0u : 1u, (uint32_t)spp, (uint32_t)s->predictor});
-            sd[0].dev[sample] = zp[0].dev;
+            for (int i = 0; i < spp; i++)
+                if (band_dev[i]) sd[0].dev[i] = band_dev[i] - back;
         }
         return zarr_decode_place(ctx, ctx->upload_stream, P, zp, in, len, std::min(s->seg_h, q->size_y), kernel_ms,
                                  &sd);
     });
+}
+
+int band_write_tiff(pbx_ctx* ctx, Plane* q, int32_t y0, int32_t rows, const TiffCodec& c, int32_t spp,
+                    int32_t sample, double* kernel_ms) {
+    int32_t k = 0;
+    if (int rc = band_of_rows(q, y0, rows, &k)) return rc;
+    if (int rc = tiff_codec_check(c, q->pixel_type, spp, sample, q->id)) return rc;
+    BandMember m[4];
+    m[sample].q = q;
+    return band_write_tiff_members(ctx, m, spp, sample, k, y0, rows, c, kernel_ms);
 }
 
 // The TIFF layers of a registration as its entry point took them: layer l's segments and codec
@@ -2842,6 +2939,36 @@ int pbx_band_write_tiff_sample(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t ro
 int pbx_band_write_tiff(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const pbx_tiff_segments* s,
                         double* kernel_ms) {
     return pbx_band_write_tiff_sample(ctx, id, y0, rows, s, 1, 0, kernel_ms);
+}
+
+int pbx_band_write_tiff_group(pbx_ctx* ctx, const uint64_t* plane_ids, int32_t n, int32_t primary, int32_t y0,
+                              int32_t rows, const pbx_tiff_segments* s, const pbx_tiff_jpeg* jpeg, int32_t j2k,
+                              const pbx_tiff_packed* packed, int32_t* statuses, double* kernel_ms) {
+    if (!ctx || !plane_ids || !s) return fail(PBX_E_BADARG, "null argument");
+    const TiffCodec c{s, jpeg, j2k != 0, packed};
+    return with_sparse_group(ctx, plane_ids, n, primary, y0, rows, statuses, [&](BandMember* m, int32_t k) {
+        if (packed && packed->samples_per_pixel != n)
+            return fail(PBX_E_BADARG, "group of %d planes on segments of %d samples per pixel", n, packed->samples_per_pixel);
+        const Plane* q = m[primary].q;
+        if (int rc = tiff_codec_check(c, q->pixel_type, n, primary, q->id)) return rc;
+        return band_write_tiff_members(ctx, m, n, primary, k, y0, rows, c, kernel_ms);
+    });
+}
+
+int pbx_band_write_zarr_group(pbx_ctx* ctx, const uint64_t* plane_ids, const int32_t* slices, int32_t n,
+                              int32_t primary, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
+                              int32_t chunk_planes, int32_t* statuses, double* kernel_ms) {
+    if (!ctx || !plane_ids || !slices || !z) return fail(PBX_E_BADARG, "null argument");
+    return with_sparse_group(ctx, plane_ids, n, primary, y0, rows, statuses, [&](BandMember* m, int32_t k) {
+        if (int rc = zarr_chunks_check(z)) return rc;
+        for (int32_t i = 0; i < n; i++) {
+            if (int rc = zarr_slice_check(chunk_planes, slices[i])) return rc;
+            for (int32_t j = 0; j < i; j++)
+                if (slices[i] == slices[j])
+                    return fail(PBX_E_BADARG, "slice %d is members %d and %d of the group", slices[i], j, i);
+        }
+        return band_write_zarr_members(ctx, m, slices, n, primary, k, y0, rows, z, chunk_planes, kernel_ms);
+    });
 }
 
 int pbx_plane_release(pbx_ctx* ctx, uint64_t id) {
@@ -3886,6 +4013,22 @@ int pbx_get_tile(pbx_ctx* ctx, const pbx_tile_req* req, pbx_result* out) {
 int pbx_test_fail_band_write(pbx_ctx* ctx, uint64_t ahead) {
     if (!ctx) return fail(PBX_E_BADARG, "null ctx");
     ctx->fail_band_write_at = ahead ? ctx->band_writes.load() + ahead : 0;
+    return PBX_OK;
+}
+
+int pbx_test_band_group_admit(const int32_t* bands, int32_t n, int32_t primary, int32_t first_row, int32_t* out) {
+    if (!bands || !out) return fail(PBX_E_BADARG, "null argument");
+    if (n < 1 || n > 4) return fail(PBX_E_BADARG, "group of %d planes outside 1 .. 4", n);
+    if (primary < 0 || primary >= n) return fail(PBX_E_BADARG, "primary %d outside the group of %d", primary, n);
+    BandView v[4];
+    int a[4];
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t* d = bands + 6 * i;
+        if (d[0] < BS_ABSENT || d[0] > BS_READY || d[2] < 0) return fail(PBX_E_BADARG, "bad band description %d", i);
+        v[i] = BandView{d[0], d[1] != 0, d[2], d[3] != 0, d[4] != 0, d[5] != 0};
+    }
+    band_group_admit(v, n, primary, first_row != 0, a);
+    for (int32_t i = 0; i < n; i++) out[i] = band_admitted(a[i]) ? a[i] : band_admit_status(a[i]);
     return PBX_OK;
 }
 

@@ -228,6 +228,7 @@ EXPORTS = [
     "pbx_band_write_tiff_jpeg", "pbx_test_tiff_jpeg_plan", "pbx_planes_register_tiff_j2k",
     "pbx_band_write_tiff_j2k", "pbx_test_tiff_j2k_plan", "pbx_test_tiff_j2k_decode",
     "pbx_planes_register_tiff_packed", "pbx_band_write_tiff_packed", "pbx_test_tiff_packed_plan",
+    "pbx_band_write_tiff_group", "pbx_band_write_zarr_group", "pbx_test_band_group_admit",
 ]
 
 _lib = None
@@ -361,6 +362,14 @@ def lib() -> ctypes.CDLL:
                                              ctypes.POINTER(PbxTiffPacked), ctypes.POINTER(ctypes.c_double)]
     L.pbx_test_tiff_packed_plan.argtypes = [ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(PbxTiffPacked), i32, i32,
                                             i32, i32, i32, ctypes.POINTER(u64)]
+    L.pbx_band_write_tiff_group.argtypes = [vp, ctypes.POINTER(u64), i32, i32, i32, i32,
+                                            ctypes.POINTER(PbxTiffSegments), ctypes.POINTER(PbxTiffJpeg), i32,
+                                            ctypes.POINTER(PbxTiffPacked), ctypes.POINTER(i32),
+                                            ctypes.POINTER(ctypes.c_double)]
+    L.pbx_band_write_zarr_group.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(i32), i32, i32, i32, i32,
+                                            ctypes.POINTER(PbxZarrChunks), i32, ctypes.POINTER(i32),
+                                            ctypes.POINTER(ctypes.c_double)]
+    L.pbx_test_band_group_admit.argtypes = [ctypes.POINTER(i32), i32, i32, i32, ctypes.POINTER(i32)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -1758,16 +1767,21 @@ class PixelsService:
                  tiff_deflate: bool = False, coalesce: bool = True, stage_rows: bool = False,
                  tiff_tile: Optional[int] = None, sparse_band_rows: int = 0,
                  request_timeout_us: Optional[int] = None, deflate_strategy: Optional[int] = None,
-                 tiff_predictor: Optional[int] = None, _handle=None):
+                 tiff_predictor: Optional[int] = None, fill_siblings: bool = False, _handle=None):
         """deflate_strategy: DEFLATE_DEFAULT / DEFLATE_HUFFMAN_ONLY / DEFLATE_AUTO (None: the
         library's initial value, $PBX_DEFLATE_STRATEGY or DEFAULT).
         tiff_predictor: TIFF_PREDICTOR_NONE / TIFF_PREDICTOR_HORIZONTAL for deflated TIFF
         responses of integer pixel types (None: $PBX_TIFF_PREDICTOR or NONE).
         sparse_band_rows > 0: planes the handler opens on demand are sparse planes of bands
         of that many rows (region-proportional residency); 0: whole planes (or the handler's
-        row band)."""
+        row band).
+        fill_siblings: load_bands fills the bands of the planes that share the primary's segments
+        or chunks (the other channels of chunky TIFF samples, of Zarr chunks that hold several
+        channels) from the primary's one decode (band_write_*_group).  Off by default: a cold
+        request then creates and fills its own plane alone."""
         import threading
         self.sparse_band_rows = int(sparse_band_rows)
+        self.fill_siblings = bool(fill_siblings)
         self._load_lock = threading.Lock()  # one loader per plane key / band
         self._loading: Dict[tuple, list] = {}  # key -> [lock, users]; removed with its last user
         self._owned = _handle is None
@@ -2315,6 +2329,87 @@ class PixelsService:
         del kept
         return [ms[0], ms[1]] if timing else None
 
+    @staticmethod
+    def _group_args(plane_ids: Sequence[int], primary: int):
+        """What the group calls refuse before they reach the library (the library refuses the
+        same with the same status): returns the ids as a C array."""
+        ids = [int(p) for p in plane_ids]
+        n = len(ids)
+        if not 1 <= n <= 4:
+            raise PbxError(E_BADARG, "group of %d planes outside 1 .. 4" % n)
+        if not 0 <= primary < n:
+            raise PbxError(E_BADARG, "primary %d outside the group of %d" % (primary, n))
+        if not ids[primary]:
+            raise PbxError(E_BADARG, "primary %d names plane id 0 (nobody wants that member)" % primary)
+        for i in range(n):
+            if ids[i] and ids[i] in ids[:i]:
+                raise PbxError(E_BADARG, "plane %d is members %d and %d of the group" % (ids[i], ids.index(ids[i]), i))
+        return (ctypes.c_uint64 * n)(*ids)
+
+    def _group_result(self, status: int, st, ms):
+        """(statuses, kernel_ms) of a group call, or its PbxError carrying `statuses`."""
+        if status != OK:
+            e = PbxError(status, lib().pbx_last_error().decode(errors="replace"))
+            e.statuses = list(st)
+            raise e
+        return list(st), [ms[0], ms[1]]
+
+    def band_write_tiff_group(self, plane_ids: Sequence[int], primary: int, y0: int, rows: int, seg_w: int,
+                              seg_h: int, tiled: bool, compression: int, predictor: int, segments,
+                              jpeg: Optional[Mapping] = None, j2k: bool = False, flags: int = 0,
+                              packed: Optional[Mapping] = None):
+        """pbx_band_write_tiff_group: band_write_tiff of rows [y0, y0 + rows) into the bands of
+        all the planes of chunky segments at once, from ONE upload and decode.  plane_ids[s] is
+        the sparse plane of sample s (len(plane_ids) = the segments' samples per pixel, 0 = nobody
+        wants that sample); plane_ids[primary] is the plane the caller needs, the others are
+        filled if they can be.  The other arguments are band_write_tiff's.  Returns (statuses,
+        kernel_ms): per member OK (written), 409 / 500 / 507 (kept out), -1 (id 0); raises what
+        band_write_tiff of the primary alone would have raised (the PbxError's `statuses`
+        attribute then holds the members')."""
+        ids = self._group_args(plane_ids, primary)
+        n = len(ids)
+        s = PbxTiffSegments()
+        kept = _fill_tiff_segments(s, dict(seg_w=seg_w, seg_h=seg_h, tiled=tiled, compression=compression,
+                                           predictor=predictor, flags=flags, segments=segments))
+        j = k = None
+        if jpeg is not None:
+            j = PbxTiffJpeg()
+            kept.append(_fill_tiff_jpeg(j, jpeg))
+        if packed is not None:
+            k = PbxTiffPacked()
+            _fill_tiff_packed(k, packed, n, 0)
+        st, ms = (ctypes.c_int32 * n)(), (ctypes.c_double * 2)()
+        status = lib().pbx_band_write_tiff_group(self._h, ids, n, primary, y0, rows, ctypes.byref(s),
+                                                 ctypes.byref(j) if j is not None else None, 1 if j2k else 0,
+                                                 ctypes.byref(k) if k is not None else None, st, ms)
+        del kept
+        return self._group_result(status, st, ms)
+
+    def band_write_zarr_group(self, plane_ids: Sequence[int], slices: Sequence[int], primary: int, y0: int,
+                              rows: int, chunk_x: int, chunk_y: int, codec: Optional[str],
+                              chunks: Sequence[Optional[bytes]], fill_bits: int = 0, chunk_planes: int = 1,
+                              crc32c: bool = False):
+        """pbx_band_write_zarr_group: band_write_zarr of rows [y0, y0 + rows) into the bands of up
+        to four planes that the same chunks hold, from ONE upload and decode: plane_ids[i]
+        receives slice slices[i] (distinct, in [0, chunk_planes)).  primary, the result and the
+        error as band_write_tiff_group; the other arguments are band_write_zarr's."""
+        ids = self._group_args(plane_ids, primary)
+        n = len(ids)
+        sl = [int(v) for v in slices]
+        if len(sl) != n:
+            raise PbxError(E_BADARG, "%d slices for a group of %d planes" % (len(sl), n))
+        for i in range(n):
+            if sl[i] in sl[:i]:
+                raise PbxError(E_BADARG, "slice %d is members %d and %d of the group" % (sl[i], sl.index(sl[i]), i))
+        zc = PbxZarrChunks()
+        kept = _fill_zarr_chunks(zc, dict(chunk_x=chunk_x, chunk_y=chunk_y, codec=codec, chunks=chunks,
+                                          fill_bits=fill_bits, crc32c=crc32c))
+        st, ms = (ctypes.c_int32 * n)(), (ctypes.c_double * 2)()
+        status = lib().pbx_band_write_zarr_group(self._h, ids, (ctypes.c_int32 * n)(*sl), n, primary, y0, rows,
+                                                 ctypes.byref(zc), chunk_planes, st, ms)
+        del kept
+        return self._group_result(status, st, ms)
+
     def band_abort(self, plane_id: int, y0: int) -> None:
         """pbx_band_abort: give back the band holding row y0 when its load is abandoned."""
         _check(lib().pbx_band_abort(self._h, plane_id, y0))
@@ -2413,9 +2508,89 @@ class PixelsService:
                 raise
             return pid
 
+    def _sparse_plane(self, source: "PixelSource", pixels: "Pixels", z: int, c: int, t: int, level: int,
+                      sx: int, sy: int, own: Optional[Tuple[int, int]], big_endian: Optional[bool] = None) -> int:
+        """The sparse plane of the key, created if absent or evicted (bands of
+        self.sparse_band_rows rows, in the source's byte order: `big_endian`, or asked of the
+        source), under the key's lock."""
+        key = (pixels.image_id, z, c, t, level)
+        with self._exclusive(key):
+            found = self.lookup_plane(*key)
+            if found is not None and found[1] != PS_EVICTED:
+                return found[0]
+            if big_endian is None:
+                band_chunks = getattr(source, "band_chunks", None)
+                band_segments = getattr(source, "band_segments", None)
+                # chunks stay in the array's byte order (no rows: nothing is read for this)
+                sp = band_chunks(pixels, z, c, t, level, 0, 0) if band_chunks is not None else None
+                if sp is None and band_segments is not None:  # segments stay in the file's byte order
+                    sp = band_segments(pixels, z, c, t, level, 0, 0)
+                big_endian = sp["big_endian"] if sp is not None else True
+            try:
+                return self.create_sparse_plane(pixels.image_id, z, c, t, pixels.pixel_type, sx, sy,
+                                                self.sparse_band_rows, level, own=own, big_endian=big_endian)
+            except PbxError as e:
+                if e.status != E_EXISTS:
+                    raise
+                return self.lookup_plane(*key)[0]
+
+    def _sibling_group(self, source: "PixelSource", pixels: "Pixels", z: int, c: int, t: int, level: int,
+                       sx: int, sy: int, own: Optional[Tuple[int, int]], pid: int, B: int) -> Optional[dict]:
+        """fill_siblings: the planes that share the segments or chunks of plane `pid` = (z, c, t),
+        looked up or created like it, as the arguments of the group calls -- ids (and slices)
+        and primary -- or None when the source's spec has no shared siblings (single-sample and
+        planar TIFF, one plane per Zarr chunk, rows only).  Siblings that are not sparse planes
+        of the primary's bands and owned rows are left out.  Each key's lock is taken on its own,
+        never inside another."""
+        band_chunks = getattr(source, "band_chunks", None)
+        band_segments = getattr(source, "band_segments", None)
+        sp = band_chunks(pixels, z, c, t, level, 0, 0) if band_chunks is not None else None
+        tsp = band_segments(pixels, z, c, t, level, 0, 0) if sp is None and band_segments is not None else None
+        chans: Dict[int, int] = {}  # member (TIFF: sample, Zarr: slice) -> channel
+        if tsp is not None and tsp.get("samples_per_pixel", 1) > 1:
+            # chunky samples: channel c - sample + s is sample s
+            chans = {s: c - tsp.get("sample", 0) + s for s in range(tsp["samples_per_pixel"])}
+            mine, big = tsp.get("sample", 0), tsp["big_endian"]
+        elif sp is not None and sp.get("chunk_planes", 1) > 1 and sp.get("layer") is not None:
+            # the neighbours along the channel axis whose chunks are the primary's (at most 3)
+            for step in (-1, 1):
+                cc = c + step
+                while 0 <= cc < pixels.size_c and len(chans) < 3:
+                    try:
+                        o = band_chunks(pixels, z, cc, t, level, 0, 0)
+                    except PbxError:
+                        break
+                    if (o is None or o.get("chunk_planes") != sp["chunk_planes"] or
+                            (o.get("layer") or ())[:2] != sp["layer"][:2]):
+                        break
+                    chans[o["slice"]] = cc
+                    cc += step
+            mine, big = sp["slice"], sp["big_endian"]
+            chans[mine] = c
+        else:
+            return None
+        held = self.lookup_plane(pixels.image_id, z, c, t, level)
+        ids = {mine: pid}
+        for m, cc in chans.items():
+            if m == mine or not 0 <= cc < pixels.size_c:
+                continue
+            try:
+                q = self._sparse_plane(source, pixels, z, cc, t, level, sx, sy, own, big)
+                if self.band_info(q)[0] != B or self.lookup_plane(pixels.image_id, z, cc, t, level)[2:] != held[2:]:
+                    continue
+            except (PbxError, TypeError):  # not a sparse plane, or released meanwhile
+                continue
+            ids[m] = q
+        if len(ids) < 2:
+            return None
+        if tsp is not None:
+            return dict(ids=[ids.get(s, 0) for s in range(len(chans))], primary=mine)
+        order = [mine] + sorted(m for m in ids if m != mine)
+        return dict(ids=[ids[m] for m in order], slices=order, primary=0)
+
     def load_bands(self, source: "PixelSource", pixels: "Pixels", z: int, c: int, t: int, level: int,
                    y: int, h: int, own: Optional[Tuple[int, int]] = None,
-                   timeout_s: float = 60.0) -> int:
+                   timeout_s: float = 60.0, siblings: Optional[bool] = None) -> int:
         """Region-proportional loading (TileRequestHandler.java:102-109 reads only the region):
         the sparse plane of the key (created if absent, bands of self.sparse_band_rows rows) gets
         the bands that rows [y, y + h) cover, each read from `source` once; bands another
@@ -2423,36 +2598,27 @@ class PixelsService:
         (PixelSource.band_chunks) hands over the Zarr chunk rows covering each band, which are
         decoded on the GPU (band_write_zarr); one with segment-level access
         (PixelSource.band_segments) the TIFF strips or tile rows (band_write_tiff); any other
-        source is read with read_rows.  Returns the plane id."""
+        source is read with read_rows.  siblings (None: the service's fill_siblings): the planes
+        that share those segments or chunks -- the other samples of chunky TIFF segments, the
+        other channels of Zarr chunks that hold several -- are looked up or created too and
+        every absent band of this plane is loaded by one group call that fills theirs from the
+        same decode, if they can be (band_write_tiff_group / band_write_zarr_group).  Returns
+        the plane id."""
         self.declare_image(pixels)
         key = (pixels.image_id, z, c, t, level)
         sx, sy = source.level_size(pixels, level)
         band_chunks = getattr(source, "band_chunks", None)
         band_segments = getattr(source, "band_segments", None)
-        with self._exclusive(key):
-            found = self.lookup_plane(*key)
-            if found is None or found[1] == PS_EVICTED:
-                # chunks stay in the array's byte order (no rows: nothing is read for this)
-                sp = band_chunks(pixels, z, c, t, level, 0, 0) if band_chunks is not None else None
-                if sp is None and band_segments is not None:  # segments stay in the file's byte order
-                    sp = band_segments(pixels, z, c, t, level, 0, 0)
-                try:
-                    pid = self.create_sparse_plane(pixels.image_id, z, c, t, pixels.pixel_type, sx, sy,
-                                                   self.sparse_band_rows, level, own=own,
-                                                   big_endian=sp["big_endian"] if sp is not None else True)
-                except PbxError as e:
-                    if e.status != E_EXISTS:
-                        raise
-                    pid = self.lookup_plane(*key)[0]
-            else:
-                pid = found[0]
+        pid = self._sparse_plane(source, pixels, z, c, t, level, sx, sy, own)
         B, states = self.band_info(pid)
         # every band the rows cover: the owned ones, and the guest bands past the owned rows that
         # a region starting in them covers (the reference's getTileDirect serves any region)
         y0, y1 = max(y, 0), min(y + h, sy)
-        for k in range(y0 // B, (y1 + B - 1) // B) if y1 > y0 else ():
-            if states[k] == BS_READY:
-                continue
+        bands = [k for k in (range(y0 // B, (y1 + B - 1) // B) if y1 > y0 else ()) if states[k] != BS_READY]
+        group = None
+        if bands and (self.fill_siblings if siblings is None else siblings):
+            group = self._sibling_group(source, pixels, z, c, t, level, sx, sy, own, pid, B)
+        for k in bands:
             with self._exclusive(key + (k,)):
                 deadline = time.monotonic() + timeout_s
                 while True:
@@ -2466,7 +2632,13 @@ class PixelsService:
                                   if band_chunks is not None else None)
                             tsp = (band_segments(pixels, z, c, t, level, r0, r1 - r0)
                                    if sp is None and band_segments is not None else None)
-                            if tsp is not None:
+                            if tsp is not None and group is not None:
+                                self.band_write_tiff_group(group["ids"], group["primary"], r0, r1 - r0,
+                                                           tsp["seg_w"], tsp["seg_h"], tsp["tiled"],
+                                                           tsp["compression"], tsp["predictor"], tsp["segments"],
+                                                           jpeg=tsp.get("jpeg"), j2k=bool(tsp.get("j2k")),
+                                                           flags=tsp.get("flags", 0), packed=tsp.get("packed"))
+                            elif tsp is not None:
                                 self.band_write_tiff(pid, r0, r1 - r0, tsp["seg_w"], tsp["seg_h"],
                                                      tsp["tiled"], tsp["compression"], tsp["predictor"],
                                                      tsp["segments"],
@@ -2477,6 +2649,12 @@ class PixelsService:
                                                      **({"flags": tsp["flags"]} if tsp.get("flags") else {}),
                                                      **({"packed": tsp["packed"]} if tsp.get("packed") is not None
                                                         else {}))
+                            elif sp is not None and group is not None:
+                                self.band_write_zarr_group(group["ids"], group["slices"], group["primary"], r0,
+                                                           r1 - r0, sp["chunk_x"], sp["chunk_y"], sp["codec"],
+                                                           sp["chunks"], sp["fill_bits"],
+                                                           chunk_planes=sp["chunk_planes"],
+                                                           crc32c=sp.get("crc32c", False))
                             elif sp is not None:
                                 self.band_write_zarr(pid, r0, r1 - r0, sp["chunk_x"], sp["chunk_y"],
                                                      sp["codec"], sp["chunks"], sp["fill_bits"],
@@ -2487,6 +2665,13 @@ class PixelsService:
                                                 source.read_rows(pixels, z, c, t, level, r0, r1 - r0))
                             break
                         except PbxError as e:
+                            sts = getattr(e, "statuses", None)
+                            if group is not None and sts is not None and sts[group["primary"]] == -1:
+                                # refused before the primary was attempted (a sibling released,
+                                # evicted or replaced meanwhile, or the piece's own fault): siblings
+                                # are best effort, the single call decides
+                                group = None
+                                continue
                             if e.status != E_EXISTS:  # another binding loads it: wait
                                 raise
                     if time.monotonic() > deadline:
