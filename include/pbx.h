@@ -709,6 +709,32 @@ int pbx_band_write_tiff_group(pbx_ctx* ctx, const uint64_t* plane_ids, int32_t n
 int pbx_band_write_zarr_group(pbx_ctx* ctx, const uint64_t* plane_ids, const int32_t* slices, int32_t n,
                               int32_t primary, int32_t y0, int32_t rows, const pbx_zarr_chunks* z,
                               int32_t chunk_planes, int32_t* statuses, double* kernel_ms);
+/* A band of a derived resolution level (DESIGN.md §10b "Derived levels"): rows [y0, y0 + rows) of
+ * one band of the sparse plane plane_id, stored level r + k, are made on the GPU from the resident
+ * rows of src_plane_id, stored level r, bit for bit what pbx_plane_build_pyramid would have put
+ * there: k (1 .. 4) applications of its rule -- each level has size ((n + 1) / 2) per axis and a
+ * sample is the mean of (2x, 2y), (min(2x + 1, n_x - 1), 2y), (2x, min(2y + 1, n_y - 1)) and the
+ * diagonal of the level above, the clamp taken at every level -- in one kernel, no level in between
+ * written to memory.  So the piece reads source rows [y0 << k, min((y0 + rows) << k, size_y)) and
+ * no others.  The contract is pbx_band_write's: any piece inside one band, the first write
+ * allocates (residency budget, eviction), the last one publishes; pieces written by any band call
+ * may be mixed in one band.
+ * The source is another plane of the same image, z, c, t, pixel type and byte order, of stored
+ * level r = the destination's - k, whose size reduces to the destination's by the rule above: a
+ * sparse plane (its band_rows need not be the destination's) or a whole dense READY plane.  Every
+ * source band that holds a needed row must be resident; they are pinned from the check until the
+ * kernel has finished and stamped as a batch that read them stamps them (least recently used
+ * order; no longer "fresh").
+ * 400: k outside 1 .. 4, src_plane_id == plane_id, a source of another image / z / c / t / pixel
+ * type / byte order / level or of a size that does not reduce to the destination's, a dense source
+ * that is a row band or still loading, a destination that is not a sparse plane, rows outside the
+ * plane or leaving their band.  404: an unknown id.  PBX_E_NOT_RESIDENT: a needed source band (or
+ * an evicted dense source) is not resident -- the destination band stays as it was, nothing is
+ * allocated, and pbx_last_error names the first missing source rows; the binding loads them and
+ * calls again.  409 / 500 / 507: exactly as pbx_band_write (pbx_test_fail_band_write counts this
+ * call too). */
+int pbx_band_write_reduced(pbx_ctx* ctx, uint64_t plane_id, int32_t y0, int32_t rows,
+                           uint64_t src_plane_id, int32_t k);
 /* Copy a registered plane back to the host, samples in big-endian order (test hook). */
 int pbx_plane_read_be(pbx_ctx* ctx, uint64_t plane_id, void* out, uint64_t bytes);
 
@@ -932,8 +958,8 @@ int pbx_test_fail_batch(pbx_ctx* ctx, uint64_t ahead);
  * queue behind it on the device, as behind a wedged one.  Callers of pbx_get_tile get 500 at
  * their deadline (pbx_config.request_timeout_us).  0 releases the stall and disarms. */
 int pbx_test_stall_batch(pbx_ctx* ctx, uint64_t ahead);
-/* Upload failure injection (test hook): the `ahead`-th pbx_band_write, pbx_band_write_zarr or
- * pbx_band_write_tiff from now on fails after joining its band's load, as a failed
+/* Upload failure injection (test hook): the `ahead`-th pbx_band_write, pbx_band_write_zarr,
+ * pbx_band_write_tiff or pbx_band_write_reduced from now on fails after joining its band's load, as a failed
  * host-to-device copy would.  A group call (pbx_band_write_tiff_group / _zarr_group) counts as
  * one write and fails every band it joined.  0 disables. */
 int pbx_test_fail_band_write(pbx_ctx* ctx, uint64_t ahead);
@@ -947,6 +973,14 @@ int pbx_test_fail_band_write(pbx_ctx* ctx, uint64_t ahead);
  * negative writers. */
 int pbx_test_band_group_admit(const int32_t* bands, int32_t n, int32_t primary, int32_t first_row,
                               int32_t* out);
+/* Test hook, no context and no device: the source rows and bands of pbx_band_write_reduced
+ * (csrc/reduce_plan.h).  Rows [y0, y0 + rows) of a level k below a level of src_size_y rows, held
+ * in bands of dst_band_rows rows, from source bands of src_band_rows rows (a dense source:
+ * src_band_rows = src_size_y).  out[0 .. 5): the first source row, the row after the last, the
+ * first and the last source band, the destination level's rows.  400: k outside 1 .. 4, a size or
+ * band height that is not positive, rows outside the destination level or leaving their band. */
+int pbx_test_reduce_plan(int32_t k, int32_t src_size_y, int32_t src_band_rows, int32_t dst_band_rows,
+                         int32_t y0, int32_t rows, int32_t* out);
 
 /* Request sharding across GPUs (one process per GPU, no collectives): the rank that
  * owns a request, by hash of (image, z, c, t, tile column, tile row) for tile_w x tile_h

@@ -15,6 +15,7 @@
 #include "dev_util.h"
 #include "pbx_common.h"
 #include "pbx_kernels.h"
+#include "reduce_plan.h"
 
 namespace pbx {
 
@@ -72,7 +73,13 @@ __device__ __forceinline__ T ds_swap(T v, bool be) {
 template <class T>
 __device__ __forceinline__ T ds_mean4(T a, T b, T c, T d) {
     if constexpr (std::is_floating_point<T>::value) {
-        return ((a + b) + (c + d)) * (T)0.25;
+        // no contraction: nothing to contract in one level whose result is stored, but where levels
+        // follow each other in one kernel (k_reduce_band) a product by 0.25 fused into the next
+        // level's sum would round once where the stored level rounds twice (denormals)
+#pragma clang fp contract(off)
+        const T s0 = a + b, s1 = c + d;
+        const T s = s0 + s1;
+        return s * (T)0.25;
     } else {
         const int64_t s = (int64_t)a + (int64_t)b + (int64_t)c + (int64_t)d;
         return (T)((s + 2) >> 2);
@@ -90,58 +97,79 @@ __device__ __forceinline__ T ds_mean4(T a, T b, T c, T d) {
 #define PBX_DS_NT 1  // bit 0: nontemporal loads, bit 1: nontemporal stores (1: 0.697 -> 0.768 of HBM peak, profiles/r06zg/)
 #endif
 constexpr int DS_G = PBX_DS_G;
+// One item: the DS_G groups from group g0 of an output row (`out`: its first sample) from the two
+// input rows r0, r1 of sx samples; dx: the output row's samples.
 template <class T>
-__global__ __launch_bounds__(256) void k_downsample(const uint8_t* __restrict__ src, int64_t spitch,
-                                                    int32_t sx, int32_t sy, uint8_t* __restrict__ dst,
-                                                    int64_t dpitch, int32_t dx, int32_t dy, bool be) {
+__device__ __forceinline__ void ds_item(const uint8_t* r0, const uint8_t* r1, T* out, int32_t g0, int32_t sx,
+                                        int32_t dx, bool be) {
+    constexpr int N = 8 / sizeof(T);
+    if (2 * (g0 + DS_G) * N <= sx) {
+        uint4 va[DS_G], vb[DS_G];
+#pragma unroll
+        for (int k = 0; k < DS_G; k++) {
+            va[k] = (PBX_DS_NT & 1) ? gload16_nt(r0 + 16 * (g0 + k)) : gload16(r0 + 16 * (g0 + k));
+            vb[k] = (PBX_DS_NT & 1) ? gload16_nt(r1 + 16 * (g0 + k)) : gload16(r1 + 16 * (g0 + k));
+        }
+        T m[N * DS_G];
+#pragma unroll
+        for (int k = 0; k < DS_G; k++) {
+            T a[2 * N], b[2 * N];
+            __builtin_memcpy(a, &va[k], 16);
+            __builtin_memcpy(b, &vb[k], 16);
+#pragma unroll
+            for (int j = 0; j < N; j++)
+                m[k * N + j] = ds_swap(ds_mean4(ds_swap(a[2 * j], be), ds_swap(a[2 * j + 1], be),
+                                                ds_swap(b[2 * j], be), ds_swap(b[2 * j + 1], be)), be);
+        }
+        if constexpr (DS_G == 2) {
+            uint4 w;
+            __builtin_memcpy(&w, m, 16);
+            if (PBX_DS_NT & 2) gstore16_nt(out, w);
+            else gstore16(out, w);
+        } else {
+            uint2 w;
+            __builtin_memcpy(&w, m, 8);
+            *(uint2*)out = w;
+        }
+    } else {
+        for (int32_t j = 0; j < N * DS_G && g0 * N + j < dx; j++) {
+            const int32_t xa = 2 * (g0 * N + j), xb = xa + 1 < sx ? xa + 1 : sx - 1;
+            const T* p0 = (const T*)r0;
+            const T* p1 = (const T*)r1;
+            out[j] = ds_swap(ds_mean4(ds_swap(p0[xa], be), ds_swap(p0[xb], be), ds_swap(p1[xa], be),
+                                      ds_swap(p1[xb], be)), be);
+        }
+    }
+}
+
+// The loop of one level: dy output rows of dx samples at dst from input rows of sx samples;
+// rows(y, r0, r1) gives the two input rows of output row y (the second one clamped).
+template <class T, class Rows>
+__device__ __forceinline__ void ds_level(Rows rows, int32_t sx, uint8_t* __restrict__ dst, int64_t dpitch,
+                                         int32_t dx, int32_t dy, bool be) {
     constexpr int N = 8 / sizeof(T);
     const uint64_t ngx = ((uint64_t)dx + N * DS_G - 1) / (N * DS_G), total = ngx * (uint64_t)dy;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const int32_t y = (int32_t)(i / ngx), sg = (int32_t)(i - (uint64_t)y * ngx);
-        const int32_t y0 = 2 * y, y1 = 2 * y + 1 < sy ? 2 * y + 1 : sy - 1;
-        const uint8_t* r0 = src + (int64_t)y0 * spitch;
-        const uint8_t* r1 = src + (int64_t)y1 * spitch;
+        const uint8_t* r0;
+        const uint8_t* r1;
+        rows(y, r0, r1);
         const int32_t g0 = sg * DS_G;
         T* out = (T*)(dst + (int64_t)y * dpitch) + g0 * N;
-        if (2 * (g0 + DS_G) * N <= sx) {
-            uint4 va[DS_G], vb[DS_G];
-#pragma unroll
-            for (int k = 0; k < DS_G; k++) {
-                va[k] = (PBX_DS_NT & 1) ? gload16_nt(r0 + 16 * (g0 + k)) : gload16(r0 + 16 * (g0 + k));
-                vb[k] = (PBX_DS_NT & 1) ? gload16_nt(r1 + 16 * (g0 + k)) : gload16(r1 + 16 * (g0 + k));
-            }
-            T m[N * DS_G];
-#pragma unroll
-            for (int k = 0; k < DS_G; k++) {
-                T a[2 * N], b[2 * N];
-                __builtin_memcpy(a, &va[k], 16);
-                __builtin_memcpy(b, &vb[k], 16);
-#pragma unroll
-                for (int j = 0; j < N; j++)
-                    m[k * N + j] = ds_swap(ds_mean4(ds_swap(a[2 * j], be), ds_swap(a[2 * j + 1], be),
-                                                    ds_swap(b[2 * j], be), ds_swap(b[2 * j + 1], be)), be);
-            }
-            if constexpr (DS_G == 2) {
-                uint4 w;
-                __builtin_memcpy(&w, m, 16);
-                if (PBX_DS_NT & 2) gstore16_nt(out, w);
-                else gstore16(out, w);
-            } else {
-                uint2 w;
-                __builtin_memcpy(&w, m, 8);
-                *(uint2*)out = w;
-            }
-        } else {
-            for (int32_t j = 0; j < N * DS_G && g0 * N + j < dx; j++) {
-                const int32_t xa = 2 * (g0 * N + j), xb = xa + 1 < sx ? xa + 1 : sx - 1;
-                const T* p0 = (const T*)r0;
-                const T* p1 = (const T*)r1;
-                out[j] = ds_swap(ds_mean4(ds_swap(p0[xa], be), ds_swap(p0[xb], be), ds_swap(p1[xa], be),
-                                          ds_swap(p1[xb], be)), be);
-            }
-        }
+        ds_item<T>(r0, r1, out, g0, sx, dx, be);
     }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_downsample(const uint8_t* __restrict__ src, int64_t spitch,
+                                                    int32_t sx, int32_t sy, uint8_t* __restrict__ dst,
+                                                    int64_t dpitch, int32_t dx, int32_t dy, bool be) {
+    ds_level<T>([&](int32_t y, const uint8_t*& r0, const uint8_t*& r1) {
+        const int32_t y0 = 2 * y, y1 = 2 * y + 1 < sy ? 2 * y + 1 : sy - 1;
+        r0 = src + (int64_t)y0 * spitch;
+        r1 = src + (int64_t)y1 * spitch;
+    }, sx, dst, dpitch, dx, dy, be);
 }
 
 hipError_t launch_downsample(hipStream_t st, const uint8_t* src, int64_t spitch, int32_t sx, int32_t sy,
@@ -164,6 +192,250 @@ hipError_t launch_downsample(hipStream_t st, const uint8_t* src, int64_t spitch,
     case PT_FLOAT: hipLaunchKernelGGL(k_downsample<float>, g, b, 0, st, src, spitch, sx, sy, dst, dpitch, dx, dy, be); break;
     default: hipLaunchKernelGGL(k_downsample<double>, g, b, 0, st, src, spitch, sx, sy, dst, dpitch, dx, dy, be); break;
     }
+    return hipGetLastError();
+}
+
+// --------------------------------------------------- a band of a derived resolution level
+// Rows [y0, y0 + rows) of level r + k (k = 2 .. 4; k = 1 is k_reduce_band1's, below) from level r
+// in ONE pass: what k launches of k_downsample would leave there, bit for bit, with no intermediate level written to HBM
+// (pbx_band_write_reduced; the row and band arithmetic is reduce_plan.h's).  The source rows are
+// not one allocation: row Y lies in band Y / band_rows, whose first row is at
+// bands[Y / band_rows - band0] (a dense plane: one band of all its rows).
+//
+// A workgroup owns the output tile that a level-1 tile of RD_W1 bytes x RD_H1 rows reduces to:
+// (RD_W1 >> (k-1)) bytes x (RD_H1 >> (k-1)) rows.  Level 1 is made straight from global memory as
+// k_downsample makes it (two aligned 16-byte loads per 8 bytes of level 1; the base tile's rows
+// start at multiples of 2 RD_W1 bytes of 256-aligned rows) and kept in LDS; levels 2 .. k-1 go
+// LDS -> LDS between two buffers, level k LDS -> global.  Every level's tile has even origins, so
+// the per-level clamp (an odd level repeats ITS last column / row) is a clamp to the tile's valid
+// width / height at that level.  Samples are in the stored byte order in global memory and native
+// in LDS.  Rows of a level that the piece's rows do not need are neither read nor made: source
+// rows outside [y0 << k, min((y0 + rows) << k, sy)) are never touched (their bands need not be
+// there).
+// LDS: 32 KiB (level 1, later level 3) + 8 KiB (level 2) = 40 KiB for every type and k: four
+// workgroups a CU.
+constexpr int RD_NT = 256;
+constexpr int RD_W1 = 512;   // bytes of a level-1 tile row (the base tile's rows: one wave x 16 bytes)
+constexpr int RD_H1 = 64;    // rows of a level-1 tile
+constexpr int RD_U = 4;      // items a thread has in flight (2 x 16-byte loads each)
+
+// One level: the ow x oh tile behind drow from the vw x vh tile behind srow (ow = (vw + 1) / 2,
+// oh <= (vh + 1) / 2; srow(y) / drow(y): the tile's row y at its first column).  ld16: the
+// 16-byte load of the source's address space.
+template <class T, class SrcRow, class DstRow, class Ld16>
+__device__ __forceinline__ void rb_level(int tid, SrcRow srow, int vw, int vh, DstRow drow, int ow, int oh,
+                                         bool be_in, bool be_out, Ld16 ld16) {
+    constexpr int N = 8 / sizeof(T);
+    const int ng = (ow + N - 1) / N, items = ng * oh;
+    for (int base = 0; base < items; base += RD_NT * RD_U) {
+        uint4 va[RD_U], vb[RD_U];
+#pragma unroll
+        for (int u = 0; u < RD_U; u++) {
+            const int i = base + u * RD_NT + tid;
+            va[u] = vb[u] = make_uint4(0, 0, 0, 0);
+            if (i < items) {
+                const int y = i / ng, g = i - y * ng;
+                if (2 * (g + 1) * N <= vw) {
+                    va[u] = ld16(srow(2 * y) + 16 * g);
+                    vb[u] = ld16(srow(2 * y + 1 < vh ? 2 * y + 1 : vh - 1) + 16 * g);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RD_U; u++) {
+            const int i = base + u * RD_NT + tid;
+            if (i >= items) continue;
+            const int y = i / ng, g = i - y * ng;
+            T* out = (T*)drow(y) + g * N;
+            if (2 * (g + 1) * N <= vw) {
+                T a[2 * N], b[2 * N], m[N];
+                __builtin_memcpy(a, &va[u], 16);
+                __builtin_memcpy(b, &vb[u], 16);
+#pragma unroll
+                for (int j = 0; j < N; j++)
+                    m[j] = ds_swap(ds_mean4(ds_swap(a[2 * j], be_in), ds_swap(a[2 * j + 1], be_in),
+                                            ds_swap(b[2 * j], be_in), ds_swap(b[2 * j + 1], be_in)), be_out);
+                uint2 w;
+                __builtin_memcpy(&w, m, 8);
+                *(uint2*)out = w;
+            } else {  // the row's last, partial group (or one that needs the clamp)
+                const T* p0 = (const T*)srow(2 * y);
+                const T* p1 = (const T*)srow(2 * y + 1 < vh ? 2 * y + 1 : vh - 1);
+                for (int j = 0; j < N && g * N + j < ow; j++) {
+                    const int xa = 2 * (g * N + j), xb = xa + 1 < vw ? xa + 1 : vw - 1;
+                    out[j] = ds_swap(ds_mean4(ds_swap(p0[xa], be_in), ds_swap(p0[xb], be_in), ds_swap(p1[xa], be_in),
+                                              ds_swap(p1[xb], be_in)), be_out);
+                }
+            }
+        }
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(RD_NT) void k_reduce_band(const uint8_t* const* __restrict__ bands, int32_t band0,
+                                                       int32_t band_rows, int64_t spitch, int32_t sx, int32_t sy,
+                                                       uint8_t* __restrict__ dst, int64_t dpitch, int32_t y0,
+                                                       int32_t rows, int32_t k, bool be) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds_a[RD_W1 * RD_H1];
+    __shared__ __attribute__((aligned(16))) uint8_t lds_b[RD_W1 / 2 * RD_H1 / 2];
+    const int tid = (int)threadIdx.x;
+    const int tw = (RD_W1 / (int)sizeof(T)) >> (k - 1), th = RD_H1 >> (k - 1);  // the output tile
+    const int32_t X0 = (int32_t)blockIdx.x * tw, Y0 = y0 + (int32_t)blockIdx.y * th;
+    // sizes of the levels 0 .. k, and the tile's valid width / height at each
+    int32_t vw[REDUCE_MAX_K + 1], vh[REDUCE_MAX_K + 1];
+    {
+        int32_t lx = sx, ly = sy;
+        const int32_t oh = Y0 + th < y0 + rows ? th : y0 + rows - Y0;  // output rows of this tile
+        for (int j = 0; j <= REDUCE_MAX_K; j++) {
+            if (j <= k) {
+                const int32_t ox = X0 << (k - j), oy = Y0 << (k - j);
+                vw[j] = lx - ox < (tw << (k - j)) ? lx - ox : (tw << (k - j));
+                vh[j] = ly - oy < (oh << (k - j)) ? ly - oy : (oh << (k - j));
+            } else {
+                vw[j] = vh[j] = 0;
+            }
+            lx = (lx + 1) / 2;
+            ly = (ly + 1) / 2;
+        }
+    }
+    const int64_t xoff0 = ((int64_t)X0 << k) * (int64_t)sizeof(T);
+    const int32_t yb = Y0 << k;
+    auto src_row = [&](int y) -> const uint8_t* {
+        const int32_t Y = yb + y, b = Y / band_rows;
+        return bands[b - band0] + (int64_t)(Y - b * band_rows) * spitch + xoff0;
+    };
+    auto dst_row = [&](int y) -> uint8_t* {
+        return dst + (int64_t)(Y0 - y0 + y) * dpitch + (int64_t)X0 * (int64_t)sizeof(T);
+    };
+    auto ldg = [](const uint8_t* p) { return (PBX_DS_NT & 1) ? gload16_nt(p) : gload16(p); };
+    auto lds = [](const uint8_t* p) { return *(const uint4*)p; };
+    // level j >= 1 lives in lds_a (odd j) or lds_b (even j), rows of RD_W1 >> (j-1) bytes
+    rb_level<T>(tid, src_row, vw[0], vh[0], [&](int y) { return lds_a + y * RD_W1; }, vw[1], vh[1], be, false, ldg);
+    __syncthreads();
+    if (k == 2) {
+        rb_level<T>(tid, [&](int y) { return (const uint8_t*)lds_a + y * RD_W1; }, vw[1], vh[1], dst_row, vw[2], vh[2],
+                    false, be, lds);
+        return;
+    }
+    rb_level<T>(tid, [&](int y) { return (const uint8_t*)lds_a + y * RD_W1; }, vw[1], vh[1],
+                [&](int y) { return lds_b + y * (RD_W1 / 2); }, vw[2], vh[2], false, false, lds);
+    __syncthreads();
+    if (k == 3) {
+        rb_level<T>(tid, [&](int y) { return (const uint8_t*)lds_b + y * (RD_W1 / 2); }, vw[2], vh[2], dst_row, vw[3],
+                    vh[3], false, be, lds);
+        return;
+    }
+    rb_level<T>(tid, [&](int y) { return (const uint8_t*)lds_b + y * (RD_W1 / 2); }, vw[2], vh[2],
+                [&](int y) { return lds_a + y * (RD_W1 / 4); }, vw[3], vh[3], false, false, lds);
+    __syncthreads();
+    rb_level<T>(tid, [&](int y) { return (const uint8_t*)lds_a + y * (RD_W1 / 4); }, vw[3], vh[3], dst_row, vw[4], vh[4],
+                false, be, lds);
+}
+
+// One level from banded rows: k_downsample's loop and item (ds_level: grid-stride, no LDS) with the
+// two input rows looked up in the band table.  Rows [y0, y0 + rows) of level r + 1, row y0 at
+// `dst`.  It is what k = 1 runs, where there is nothing to fuse: the tiled kernel above read the
+// base at 3.3-3.9 TB/s there, 1.35-1.5 x the time of one k_downsample launch
+// (profiles/reduce_band/fused_vs_chain_tiled_every_k.log).  This kernel (fused_vs_chain.log): a tie
+// with k_downsample for one-byte samples, 1.2 x its time for 2- and 4-byte ones -- the band pointers
+// are vector loads that the two 16-byte loads wait for (supposed, not profiled; a wave-uniform
+// lookup written with readfirstlane was merged back into vector loads by the compiler).
+template <class T>
+__global__ __launch_bounds__(256) void k_reduce_band1(const uint8_t* const* __restrict__ bands, int32_t band0,
+                                                      int32_t band_rows, int64_t spitch, int32_t sx, int32_t sy,
+                                                      uint8_t* __restrict__ dst, int64_t dpitch, int32_t dx,
+                                                      int32_t y0, int32_t rows, bool be) {
+    ds_level<T>([&](int32_t y, const uint8_t*& r0, const uint8_t*& r1) {
+        const int32_t Ya = 2 * (y0 + y), Yb = Ya + 1 < sy ? Ya + 1 : sy - 1;
+        const int32_t ba = Ya / band_rows, bb = Yb / band_rows;
+        r0 = bands[ba - band0] + (int64_t)(Ya - ba * band_rows) * spitch;
+        r1 = bands[bb - band0] + (int64_t)(Yb - bb * band_rows) * spitch;
+    }, sx, dst, dpitch, dx, rows, be);
+}
+
+static hipError_t launch_reduce_band1(hipStream_t st, const uint8_t* const* d_bands, int32_t band0, int32_t band_rows,
+                                      int64_t spitch, int32_t sx, int32_t sy, uint8_t* dst, int64_t dpitch, int32_t y0,
+                                      int32_t rows, int32_t pixel_type, bool be) {
+    static const int bpps[PT_N] = {1, 1, 2, 2, 4, 4, 4, 8};
+    const int32_t dx = reduce_size(sx, 1);
+    const uint64_t n = 8 / bpps[pixel_type] * DS_G;
+    uint64_t blocks = (((uint64_t)dx + n - 1) / n * (uint64_t)rows + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    const dim3 g((uint32_t)blocks), b(256);
+#define PBX_RB1(T) hipLaunchKernelGGL(k_reduce_band1<T>, g, b, 0, st, d_bands, band0, band_rows, spitch, sx, sy, dst, dpitch, dx, y0, rows, be)
+    switch (pixel_type) {
+    case PT_INT8: PBX_RB1(int8_t); break;
+    case PT_UINT8: PBX_RB1(uint8_t); break;
+    case PT_INT16: PBX_RB1(int16_t); break;
+    case PT_UINT16: PBX_RB1(uint16_t); break;
+    case PT_INT32: PBX_RB1(int32_t); break;
+    case PT_UINT32: PBX_RB1(uint32_t); break;
+    case PT_FLOAT: PBX_RB1(float); break;
+    default: PBX_RB1(double); break;
+    }
+#undef PBX_RB1
+    return hipGetLastError();
+}
+
+// One-byte samples at k = 2 go level by level through scratch instead of through the tiled kernel,
+// which was measured 8-10 % slower there than two launches of k_downsample on the same rows
+// (profiles/reduce_band/fused_vs_chain_tiled_every_k.log): k_reduce_band1 puts the piece's level 1
+// into scratch, k_downsample makes level 2 from it into the band.
+static bool reduce_band_chained(int32_t pixel_type, int32_t k) {
+    return k == 2 && (pixel_type == PT_INT8 || pixel_type == PT_UINT8);
+}
+
+// The piece's level 1 in scratch (k = 2): rows [2 y0, min(2 (y0 + rows), its height)), their pitch.
+static void reduce_band_level1(int32_t sx, int32_t sy, int32_t y0, int32_t rows, int32_t* lx, int32_t* n,
+                               int64_t* pitch) {
+    const int32_t ly = reduce_size(sy, 1);
+    const int64_t a = (int64_t)y0 * 2, b = ((int64_t)y0 + rows) * 2;
+    *lx = reduce_size(sx, 1);
+    *n = (int32_t)((b < ly ? b : ly) - a);
+    *pitch = ((int64_t)*lx + 255) & ~(int64_t)255;  // one-byte samples
+}
+
+size_t reduce_band_scratch_bytes(int32_t sx, int32_t sy, int32_t y0, int32_t rows, int32_t k, int32_t pixel_type) {
+    if (!reduce_band_chained(pixel_type, k)) return 0;
+    int32_t lx, n;
+    int64_t pitch;
+    reduce_band_level1(sx, sy, y0, rows, &lx, &n, &pitch);
+    return (size_t)pitch * (size_t)n + 256;
+}
+
+hipError_t launch_reduce_band(hipStream_t st, const uint8_t* const* d_bands, int32_t band0, int32_t band_rows,
+                              int64_t spitch, int32_t sx, int32_t sy, uint8_t* dst, int64_t dpitch, int32_t y0,
+                              int32_t rows, int32_t k, int32_t pixel_type, bool be, uint8_t* scratch) {
+    static const int bpps[PT_N] = {1, 1, 2, 2, 4, 4, 4, 8};
+    if (k < 1 || k > REDUCE_MAX_K || rows <= 0 || pixel_type < 0 || pixel_type >= PT_N) return hipErrorInvalidValue;
+    if (k == 1)
+        return launch_reduce_band1(st, d_bands, band0, band_rows, spitch, sx, sy, dst, dpitch, y0, rows, pixel_type, be);
+    if (reduce_band_chained(pixel_type, k)) {
+        if (!scratch) return hipErrorInvalidValue;
+        int32_t lx, n;
+        int64_t pitch;
+        reduce_band_level1(sx, sy, y0, rows, &lx, &n, &pitch);
+        const hipError_t e = launch_reduce_band1(st, d_bands, band0, band_rows, spitch, sx, sy, scratch, pitch, 2 * y0, n,
+                                                 pixel_type, be);
+        if (e != hipSuccess) return e;
+        return launch_downsample(st, scratch, pitch, lx, n, dst, dpitch, reduce_size(sx, 2), rows, pixel_type, be);
+    }
+    const int32_t tw = (RD_W1 / bpps[pixel_type]) >> (k - 1), th = RD_H1 >> (k - 1);
+    const int32_t dx = reduce_size(sx, k);
+    const dim3 g((uint32_t)((dx + tw - 1) / tw), (uint32_t)((rows + th - 1) / th)), b(RD_NT);
+    if (g.y > 65535) return hipErrorInvalidValue;
+#define PBX_RB(T) hipLaunchKernelGGL(k_reduce_band<T>, g, b, 0, st, d_bands, band0, band_rows, spitch, sx, sy, dst, dpitch, y0, rows, k, be)
+    switch (pixel_type) {
+    case PT_INT8: PBX_RB(int8_t); break;
+    case PT_UINT8: PBX_RB(uint8_t); break;
+    case PT_INT16: PBX_RB(int16_t); break;
+    case PT_UINT16: PBX_RB(uint16_t); break;
+    case PT_INT32: PBX_RB(int32_t); break;
+    case PT_UINT32: PBX_RB(uint32_t); break;
+    case PT_FLOAT: PBX_RB(float); break;
+    default: PBX_RB(double); break;
+    }
+#undef PBX_RB
     return hipGetLastError();
 }
 

@@ -24,6 +24,17 @@ hipError_t launch_gen_plane(hipStream_t st, uint8_t* out, int64_t pitch, int32_t
 hipError_t launch_downsample(hipStream_t st, const uint8_t* src, int64_t spitch, int32_t sx, int32_t sy,
                              uint8_t* dst, int64_t dpitch, int32_t dx, int32_t dy, int32_t pixel_type,
                              bool be);
+// Rows [y0, y0 + rows) of level r + k (k = 1 .. 4; row y0 at `dst`) from level r (sx x sy) in one
+// pass, bit for bit what k launch_downsample calls leave there.  Source row Y is in band
+// Y / band_rows, whose first row is at d_bands[Y / band_rows - band0] (a device table); only rows
+// [y0 << k, min((y0 + rows) << k, sy)) are read.  k = 1: k_reduce_band1 (k_downsample's loop over banded
+// rows); k >= 2: the tiled k_reduce_band, except where it was measured slower than the chain of
+// single levels -- those (type, k) go level by level through `scratch`, reduce_band_scratch_bytes()
+// bytes of it (0: none needed, scratch may be null).
+size_t reduce_band_scratch_bytes(int32_t sx, int32_t sy, int32_t y0, int32_t rows, int32_t k, int32_t pixel_type);
+hipError_t launch_reduce_band(hipStream_t st, const uint8_t* const* d_bands, int32_t band0, int32_t band_rows,
+                              int64_t spitch, int32_t sx, int32_t sy, uint8_t* dst, int64_t dpitch, int32_t y0,
+                              int32_t rows, int32_t k, int32_t pixel_type, bool be, uint8_t* scratch);
 // test hook (pbx_test_stall_batch): one wave spinning until *flag == 0 or limit_ticks of the
 // 100 MHz constant clock
 hipError_t launch_stall(hipStream_t st, const uint32_t* flag, uint64_t limit_ticks);

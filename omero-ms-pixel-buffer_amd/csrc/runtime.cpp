@@ -34,6 +34,7 @@
 #include "pbx_common.h"
 #include "pbx_config.h"
 #include "pbx_kernels.h"
+#include "reduce_plan.h"
 #include "source_plan.h"
 
 using namespace pbx;
@@ -2177,12 +2178,118 @@ int with_sparse_group(pbx_ctx* ctx, const uint64_t* ids, int32_t n, int32_t prim
     return rc;
 }
 
+// pbx_band_write_reduced: rows [y0, y0 + rows) of one band of the sparse plane `id` (stored level
+// r + k) made from the resident rows of plane `src_id` (level r) by k_reduce_band.  One critical
+// section checks both planes, plans the source rows (reduce_plan.h), checks that every source band
+// holding one is resident and pins them, stamped as a batch read stamps them; nothing of the
+// destination is touched before that, so a source that is not resident leaves it as it was.  The
+// write itself is a band write like every other (band_load_rows); the pins go when the kernel is
+// done, or was never launched.
+int band_write_reduced(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, uint64_t src_id, int32_t k) {
+    if (k < 1 || k > REDUCE_MAX_K) return fail(PBX_E_BADARG, "reduction by %d levels outside 1 .. %d", k, REDUCE_MAX_K);
+    if (id == src_id) return fail(PBX_E_BADARG, "plane %llu is its own source", (unsigned long long)id);
+    Plane* q = nullptr;
+    Plane* sp = nullptr;
+    ReducePlan P{};
+    int32_t kb = 0;
+    std::vector<const uint8_t*> tab;  // first rows of the source bands P.band0 .. P.band1
+    int32_t src_band_rows = 0;
+    {
+        std::lock_guard<std::mutex> g(ctx->reg_mu);
+        auto find = [&](uint64_t pid) -> Plane* {
+            auto it = ctx->planes.find(pid);
+            return it == ctx->planes.end() || !it->second->indexed ? nullptr : it->second;
+        };
+        q = find(id);
+        if (!q) return fail(PBX_E_NOTFOUND, "no plane %llu", (unsigned long long)id);
+        sp = find(src_id);
+        if (!sp) return fail(PBX_E_NOTFOUND, "no plane %llu", (unsigned long long)src_id);
+        if (!q->sparse_rows || q->state == PS_FILLING)
+            return fail(PBX_E_BADARG, "plane %llu is not a sparse plane", (unsigned long long)id);
+        if (q->state != PS_READY) return fail(PBX_E_NOT_RESIDENT, "plane %llu is evicted", (unsigned long long)id);
+        if (int rc = band_of_rows(q, y0, rows, &kb)) return rc;
+        if (sp->image_id != q->image_id || sp->z != q->z || sp->c != q->c || sp->t != q->t)
+            return fail(PBX_E_BADARG, "planes %llu and %llu are not the same image, z, c and t", (unsigned long long)src_id,
+                        (unsigned long long)id);
+        if (sp->pixel_type != q->pixel_type || sp->little_endian != q->little_endian)
+            return fail(PBX_E_BADARG, "planes %llu and %llu differ in pixel type or byte order", (unsigned long long)src_id,
+                        (unsigned long long)id);
+        if (sp->res != q->res - k)
+            return fail(PBX_E_BADARG, "plane %llu is stored level %d, not level %d - %d", (unsigned long long)src_id, sp->res,
+                        q->res, k);
+        if (reduce_size(sp->size_x, k) != q->size_x || reduce_size(sp->size_y, k) != q->size_y)
+            return fail(PBX_E_BADARG, "%d x %d does not reduce to %d x %d in %d levels", sp->size_x, sp->size_y, q->size_x,
+                        q->size_y, k);
+        if (!sp->sparse_rows && !(sp->band_y0 == 0 && sp->band_rows == sp->size_y))
+            return fail(PBX_E_BADARG, "plane %llu is a row band: no source of a reduction", (unsigned long long)src_id);
+        if (sp->state == PS_FILLING) return fail(PBX_E_BADARG, "plane %llu is still loading", (unsigned long long)src_id);
+        src_band_rows = sp->sparse_rows ? sp->sparse_rows : sp->size_y;
+        if (reduce_plan(k, sp->size_y, src_band_rows, q->sparse_rows, y0, rows, &P) != RP_OK || P.dst_band != kb)
+            return fail(PBX_E_INTERNAL, "reduction plan of rows %d+%d", y0, rows);  // (band_of_rows said otherwise)
+        if (sp->state != PS_READY || (!sp->sparse_rows && !sp->dev))
+            return fail(PBX_E_NOT_RESIDENT, "source rows %d..%d: plane %llu is evicted", P.src_y0, P.src_y1,
+                        (unsigned long long)src_id);
+        if (sp->sparse_rows)
+            for (int32_t b = P.band0; b <= P.band1; b++)
+                if (sp->bands[(size_t)b].state != BS_READY || !sp->bands[(size_t)b].dev)
+                    return fail(PBX_E_NOT_RESIDENT, "source rows %d..%d: band %d (rows %d..%d) of plane %llu not resident",
+                                std::max(P.src_y0, sp->band_lo(b)), std::min(P.src_y1, sp->band_hi(b)), b, sp->band_lo(b),
+                                sp->band_hi(b), (unsigned long long)src_id);
+        const uint64_t tick = ++ctx->use_tick;
+        if (sp->sparse_rows) {
+            for (int32_t b = P.band0; b <= P.band1; b++) {
+                Band& sb = sp->bands[(size_t)b];
+                sb.pins++;
+                sb.last_use = tick;
+                sb.fresh_until = 0;  // read for a reduction: served
+                tab.push_back(sb.dev);
+            }
+        } else {
+            tab.push_back(sp->dev);
+        }
+        sp->pins++;
+        sp->last_use = tick;
+        sp->fresh_until = 0;
+        q->pins++;
+    }
+    const int bpp = bpp_of(q->pixel_type);
+    const int rc = band_load_rows(ctx, q, kb, y0, rows, [&](uint8_t* band_dev) {
+        LaunchScratch S(ctx, ctx->upload_stream);
+        const uint8_t* const* d_tab = S.table(tab);
+        const size_t need = reduce_band_scratch_bytes(sp->size_x, sp->size_y, y0, rows, k, q->pixel_type);
+        uint8_t* scratch = need ? S.raw(need) : nullptr;  // (type, k) served level by level
+        if (S.e == hipSuccess)
+            S.e = launch_reduce_band(ctx->upload_stream, d_tab, P.band0, src_band_rows, sp->pitch, sp->size_x, sp->size_y,
+                                     band_dev + (int64_t)(y0 - q->band_lo(kb)) * q->pitch, q->pitch, y0, rows, k,
+                                     q->pixel_type, !q->little_endian && bpp > 1, scratch);
+        if (S.e == hipSuccess) S.e = hipStreamSynchronize(ctx->upload_stream);
+        return S.e == hipSuccess ? (int)PBX_OK : fail(PBX_E_INTERNAL, "band write (reduced): %s", hipGetErrorString(S.e));
+    });
+    const std::string msg = last_error();
+    std::vector<std::pair<void*, size_t>> to_free;
+    {
+        std::lock_guard<std::mutex> g(ctx->reg_mu);
+        if (sp->sparse_rows)
+            for (int32_t b = P.band0; b <= P.band1; b++) sp->bands[(size_t)b].pins--;  // before the plane pins
+        unpin_locked(ctx, sp, 1, to_free);
+        unpin_locked(ctx, q, 1, to_free);
+    }
+    free_planes(ctx, to_free);
+    last_error() = msg;
+    return rc;
+}
+
 }  // namespace
 extern "C" {
 
 int pbx_band_write(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, const void* data, uint64_t bytes) {
     if (!ctx) return fail(PBX_E_BADARG, "null ctx");
     return with_sparse_plane(ctx, id, [&](Plane* q) { return band_write(ctx, q, y0, rows, data, bytes); });
+}
+
+int pbx_band_write_reduced(pbx_ctx* ctx, uint64_t id, int32_t y0, int32_t rows, uint64_t src_id, int32_t k) {
+    if (!ctx) return fail(PBX_E_BADARG, "null ctx");
+    return band_write_reduced(ctx, id, y0, rows, src_id, k);
 }
 
 int pbx_band_abort(pbx_ctx* ctx, uint64_t id, int32_t y0) {
@@ -4029,6 +4136,22 @@ int pbx_test_band_group_admit(const int32_t* bands, int32_t n, int32_t primary, 
     }
     band_group_admit(v, n, primary, first_row != 0, a);
     for (int32_t i = 0; i < n; i++) out[i] = band_admitted(a[i]) ? a[i] : band_admit_status(a[i]);
+    return PBX_OK;
+}
+
+int pbx_test_reduce_plan(int32_t k, int32_t src_size_y, int32_t src_band_rows, int32_t dst_band_rows, int32_t y0,
+                         int32_t rows, int32_t* out) {
+    if (!out) return fail(PBX_E_BADARG, "null argument");
+    ReducePlan P{};
+    switch (reduce_plan(k, src_size_y, src_band_rows, dst_band_rows, y0, rows, &P)) {
+    case RP_OK: break;
+    case RP_BAD_K: return fail(PBX_E_BADARG, "reduction by %d levels outside 1 .. %d", k, REDUCE_MAX_K);
+    case RP_BAD_BANDS: return fail(PBX_E_BADARG, "bad plane height or band rows");
+    case RP_BAD_ROWS:
+        return fail(PBX_E_BADARG, "rows %d+%d outside the plane (%d rows)", y0, rows, reduce_size(src_size_y, k));
+    default: return fail(PBX_E_BADARG, "rows %d+%d cross the end of band %d", y0, rows, y0 / dst_band_rows);
+    }
+    out[0] = P.src_y0; out[1] = P.src_y1; out[2] = P.band0; out[3] = P.band1; out[4] = P.dst_sy;
     return PBX_OK;
 }
 

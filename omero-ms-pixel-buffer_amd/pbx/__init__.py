@@ -229,6 +229,7 @@ EXPORTS = [
     "pbx_band_write_tiff_j2k", "pbx_test_tiff_j2k_plan", "pbx_test_tiff_j2k_decode",
     "pbx_planes_register_tiff_packed", "pbx_band_write_tiff_packed", "pbx_test_tiff_packed_plan",
     "pbx_band_write_tiff_group", "pbx_band_write_zarr_group", "pbx_test_band_group_admit",
+    "pbx_band_write_reduced", "pbx_test_reduce_plan",
 ]
 
 _lib = None
@@ -370,6 +371,8 @@ def lib() -> ctypes.CDLL:
                                             ctypes.POINTER(PbxZarrChunks), i32, ctypes.POINTER(i32),
                                             ctypes.POINTER(ctypes.c_double)]
     L.pbx_test_band_group_admit.argtypes = [ctypes.POINTER(i32), i32, i32, i32, ctypes.POINTER(i32)]
+    L.pbx_band_write_reduced.argtypes = [vp, u64, i32, i32, u64, i32]
+    L.pbx_test_reduce_plan.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.POINTER(i32)]
     L.pbx_band_abort.argtypes = [vp, u64, i32]
     L.pbx_plane_band_info.argtypes = [vp, u64, ctypes.POINTER(i32), ctypes.POINTER(i32), vp]
     L.pbx_node_init.argtypes = [ctypes.POINTER(PbxConfig), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(vp)]
@@ -1767,7 +1770,8 @@ class PixelsService:
                  tiff_deflate: bool = False, coalesce: bool = True, stage_rows: bool = False,
                  tiff_tile: Optional[int] = None, sparse_band_rows: int = 0,
                  request_timeout_us: Optional[int] = None, deflate_strategy: Optional[int] = None,
-                 tiff_predictor: Optional[int] = None, fill_siblings: bool = False, _handle=None):
+                 tiff_predictor: Optional[int] = None, fill_siblings: bool = False, reduce_step: int = 2,
+                 _handle=None):
         """deflate_strategy: DEFLATE_DEFAULT / DEFLATE_HUFFMAN_ONLY / DEFLATE_AUTO (None: the
         library's initial value, $PBX_DEFLATE_STRATEGY or DEFAULT).
         tiff_predictor: TIFF_PREDICTOR_NONE / TIFF_PREDICTOR_HORIZONTAL for deflated TIFF
@@ -1778,8 +1782,15 @@ class PixelsService:
         fill_siblings: load_bands fills the bands of the planes that share the primary's segments
         or chunks (the other channels of chunky TIFF samples, of Zarr chunks that hold several
         channels) from the primary's one decode (band_write_*_group).  Off by default: a cold
-        request then creates and fills its own plane alone."""
+        request then creates and fills its own plane alone.
+        reduce_step (1 .. 4): a band of a derived level (DerivedLevels) is made from the level that
+        many levels above it, or from the last stored level if that is nearer; the levels in
+        between are not made for it.  A larger step reads more base rows per band (2^step rows
+        per row) and caches fewer intermediate bands."""
         import threading
+        if not 1 <= int(reduce_step) <= 4:
+            raise ValueError("reduce_step %r outside 1 .. 4" % (reduce_step,))
+        self.reduce_step = int(reduce_step)
         self.sparse_band_rows = int(sparse_band_rows)
         self.fill_siblings = bool(fill_siblings)
         self._load_lock = threading.Lock()  # one loader per plane key / band
@@ -2250,6 +2261,15 @@ class PixelsService:
         else:
             _check(lib().pbx_band_write(self._h, plane_id, y0, rows, data, len(data)))
 
+    def band_write_reduced(self, plane_id: int, y0: int, rows: int, src_plane_id: int, k: int) -> None:
+        """pbx_band_write_reduced: rows [y0, y0 + rows) of one band of the sparse plane
+        `plane_id` (stored level r + k), made on the GPU from the resident rows
+        [y0 << k, min((y0 + rows) << k, size_y)) of plane `src_plane_id` (level r, the same image,
+        z, c, t, pixel type and byte order): k = 1 .. 4 levels of 2x2 means in one kernel, bit for
+        bit build_pyramid's.  E_NOT_RESIDENT: a source band that holds one of those rows is not
+        resident (nothing was written or allocated); load it and call again."""
+        _check(lib().pbx_band_write_reduced(self._h, plane_id, y0, rows, src_plane_id, k))
+
     def band_write_zarr(self, plane_id: int, y0: int, rows: int, chunk_x: int, chunk_y: int,
                         codec: Optional[str], chunks: Sequence[Optional[bytes]], fill_bits: int = 0,
                         timing: bool = False, chunk_planes: int = 1, slice: int = 0, crc32c: bool = False):
@@ -2468,6 +2488,30 @@ class PixelsService:
         `band_bytes`, commit.  If another caller is loading the same key, wait for it."""
         self.declare_image(pixels)
         key = (pixels.image_id, z, c, t, level)
+        if _derived_from(source, pixels, level, 1) is not None:
+            # a level the source does not store: the last stored level whole, then every derived
+            # level at once (build_pyramid), under the stored level's lock
+            if band is not None:
+                raise PbxError(E_BADARG, "derived levels are not sharded by rows")
+            found = self.lookup_plane(*key)
+            if found is not None and found[1] == PS_READY:
+                return found[0]
+            last = source.stored_levels(pixels) - 1
+            base = self.load_plane(source, pixels, z, c, t, last, None, band_bytes, timeout_s)
+            with self._exclusive(key[:4] + (last,)):
+                found = self.lookup_plane(*key)
+                if found is not None and found[1] == PS_READY:
+                    return found[0]
+                try:
+                    return self.build_pyramid(base, pixels.levels - 1 - last)[level - last - 1]
+                except PbxError as e:
+                    if e.status != E_EXISTS:
+                        raise
+                    found = self.lookup_plane(*key)  # another context user built them
+                    if found is None:  # levels partly built, or released in between
+                        raise PbxError(E_INTERNAL, "level %d of Image:%d z=%d c=%d t=%d: some derived level is "
+                                       "registered, this one is not" % (level, pixels.image_id, z, c, t))
+                    return found[0]
         with self._exclusive(key):
             found = self.lookup_plane(*key)
             if found is not None and found[1] == PS_READY:
@@ -2603,10 +2647,17 @@ class PixelsService:
         other channels of Zarr chunks that hold several -- are looked up or created too and
         every absent band of this plane is loaded by one group call that fills theirs from the
         same decode, if they can be (band_write_tiff_group / band_write_zarr_group).  Returns
-        the plane id."""
+        the plane id.
+        A level the source does not store (DerivedLevels) is made from the level reduce_step above
+        it (_load_derived_bands)."""
         self.declare_image(pixels)
         key = (pixels.image_id, z, c, t, level)
         sx, sy = source.level_size(pixels, level)
+        derived = _derived_from(source, pixels, level, self.reduce_step)
+        if derived is not None:
+            if own is not None:
+                raise PbxError(E_BADARG, "derived levels are not sharded by rows")
+            return self._load_derived_bands(source, pixels, z, c, t, level, y, h, timeout_s, *derived)
         band_chunks = getattr(source, "band_chunks", None)
         band_segments = getattr(source, "band_segments", None)
         pid = self._sparse_plane(source, pixels, z, c, t, level, sx, sy, own)
@@ -2676,6 +2727,64 @@ class PixelsService:
                                 raise
                     if time.monotonic() > deadline:
                         raise PbxError(E_INTERNAL, "band %d of plane %d: timed out loading" % (k, pid))
+                    time.sleep(0.001)
+        return pid
+
+    def _level_big_endian(self, source: "PixelSource", pixels: "Pixels", z: int, c: int, t: int, level: int) -> bool:
+        """The byte order load_bands keeps a level's sparse plane in: the chunks' or segments' of
+        a stored level, rows big-endian; a derived level has its last stored level's."""
+        if _derived_from(source, pixels, level, 1) is not None:
+            level = source.stored_levels(pixels) - 1
+        sp = None
+        for name in ("band_chunks", "band_segments"):
+            f = getattr(source, name, None)
+            sp = f(pixels, z, c, t, level, 0, 0) if sp is None and f is not None else sp
+        return sp["big_endian"] if sp is not None else True
+
+    def _load_derived_bands(self, source: "PixelSource", pixels: "Pixels", z: int, c: int, t: int, level: int,
+                            y: int, h: int, timeout_s: float, src_level: int, k: int) -> int:
+        """load_bands for a level the source does not store: every absent band [r0, r1) the rows
+        cover gets the rows [r0 << k, min(r1 << k, size_y)) of `src_level` = level - k loaded
+        (load_bands again: a derived source level becomes a sparse plane of its own, whose bands
+        the neighbours reuse) and is then made from them on the GPU (band_write_reduced).  A
+        source band evicted between the two is loaded again, LOAD_ATTEMPTS times at most.
+        fill_siblings is ignored here, for the stored source level's bands too: what a derived
+        request loads is its own channel's rows."""
+        key = (pixels.image_id, z, c, t, level)
+        sx, sy = source.level_size(pixels, level)
+        ssy = source.level_size(pixels, src_level)[1]
+        pid = self._sparse_plane(source, pixels, z, c, t, level, sx, sy, None,
+                                 self._level_big_endian(source, pixels, z, c, t, level))
+        B, states = self.band_info(pid)
+        y0, y1 = max(y, 0), min(y + h, sy)
+        for kb in (range(y0 // B, (y1 + B - 1) // B) if y1 > y0 else ()):
+            if states[kb] == BS_READY:
+                continue
+            with self._exclusive(key + (kb,)):
+                deadline, attempts = time.monotonic() + timeout_s, 0
+                while True:
+                    st = self.band_info(pid)[1][kb]
+                    if st == BS_READY:
+                        break
+                    if st == BS_ABSENT:
+                        r0, r1 = kb * B, min((kb + 1) * B, sy)
+                        if attempts >= TileRequestHandler.LOAD_ATTEMPTS:
+                            raise PbxError(E_INTERNAL, "band %d of plane %d: its source rows could not be held "
+                                           "resident (residency budget smaller than the working set)" % (kb, pid))
+                        attempts += 1
+                        s0, s1 = r0 << k, min(r1 << k, ssy)
+                        src = self.load_bands(source, pixels, z, c, t, src_level, s0, s1 - s0,
+                                              timeout_s=timeout_s, siblings=False)
+                        try:
+                            self.band_write_reduced(pid, r0, r1 - r0, src, k)
+                            break
+                        except PbxError as e:
+                            if e.status == E_NOT_RESIDENT:  # a source band was evicted in between
+                                continue
+                            if e.status != E_EXISTS:  # another binding makes it: wait
+                                raise
+                    if time.monotonic() > deadline:
+                        raise PbxError(E_INTERNAL, "band %d of plane %d: timed out loading" % (kb, pid))
                     time.sleep(0.001)
         return pid
 
@@ -3152,6 +3261,97 @@ class TiffSource(PixelSource):
                        "so serve it without a whole-row band")
 
 
+def _derived_from(source, pixels: "Pixels", level: int, step: int) -> Optional[Tuple[int, int]]:
+    """source.derived_from(pixels, level, step) of a source that has derived levels, or None: the
+    source stores every level it declares, or stores this one."""
+    f = getattr(source, "derived_from", None)
+    return f(pixels, level, step) if f is not None else None
+
+
+class DerivedLevels(PixelSource):
+    """Lower resolution levels for a source that stores none, or too few: `inner`'s L stored levels
+    are served as they are, and E more are declared after them, each the 2x2 mean of the one
+    before (size (n + 1) // 2 per axis, the last column / row repeated when n is odd) -- what
+    OMERO's pyramid generation gives an image too large to serve whole.  levels: E; None: halve
+    until both sides of the smallest level are <= max_side (3192 is believed to be the default of
+    omero.pixeldata.max_plane_width / _height; it has not been checked against a server).
+    Nothing of a derived level is stored or read: a PixelsService makes its bands on the GPU from
+    the resident bands of the level reduce_step above it (load_bands -> band_write_reduced), or,
+    without sparse_band_rows, builds all E levels from the whole last stored level (load_plane ->
+    build_pyramid).  Derived levels are not sharded by rows (a handler with band=: 400)."""
+
+    def __init__(self, inner: PixelSource, levels: Optional[int] = None, max_side: int = 3192):
+        if levels is not None and levels < 0:
+            raise ValueError("levels %r" % (levels,))
+        if max_side < 1:
+            raise ValueError("max_side %r" % (max_side,))
+        self.inner, self.levels, self.max_side = inner, levels, max_side
+        self._counts: Dict[int, Tuple[int, int]] = {}  # image -> (stored levels, all levels)
+
+    def get_pixels(self, image_id: int) -> Optional[Pixels]:
+        import copy
+        p = self.inner.get_pixels(image_id)
+        if p is None:
+            return None
+        extra = self.levels
+        if extra is None:
+            extra, (sx, sy) = 0, self.inner.level_size(p, p.levels - 1)
+            while max(sx, sy) > self.max_side:
+                sx, sy, extra = (sx + 1) // 2, (sy + 1) // 2, extra + 1
+        q = copy.copy(p)
+        q.stored_levels, q.levels = p.levels, p.levels + extra
+        self._counts[image_id] = (p.levels, q.levels)
+        return q
+
+    def resolution_is_derived(self, image_id: int, resolution: int) -> bool:
+        """Whether `resolution` (OMERO numbering, 0 = the smallest level) names a derived level of
+        the image; its level counts are looked up once (get_pixels) and remembered."""
+        if image_id not in self._counts and self.get_pixels(image_id) is None:
+            return False
+        stored, levels = self._counts[image_id]
+        return stored <= levels - 1 - resolution < levels
+
+    def stored_levels(self, pixels: Pixels) -> int:
+        """L: the levels `inner` stores (levels L .. pixels.levels - 1 are derived)."""
+        n = getattr(pixels, "stored_levels", None)
+        return n if n is not None else self.inner.get_pixels(pixels.image_id).levels
+
+    def derived_from(self, pixels: Pixels, level: int, step: int) -> Optional[Tuple[int, int]]:
+        """(source_level, k) of a derived level: it is made from source_level = max(L - 1,
+        level - step), k = level - source_level levels above it.  None: a stored level, or no
+        level of the image."""
+        last = self.stored_levels(pixels) - 1
+        if level <= last or level >= pixels.levels:
+            return None
+        src = max(last, level - step)
+        return src, level - src
+
+    def level_size(self, pixels: Pixels, level: int) -> Tuple[int, int]:
+        last = self.stored_levels(pixels) - 1
+        sx, sy = self.inner.level_size(pixels, min(level, last))
+        for _ in range(level - last):
+            sx, sy = (sx + 1) // 2, (sy + 1) // 2
+        return sx, sy
+
+    def _stored(self, name: str, pixels: Pixels, level: int, *args):
+        f = getattr(self.inner, name, None)
+        return f(pixels, *args) if f is not None and level < self.stored_levels(pixels) else None
+
+    def read_rows(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int, rows: int) -> bytes:
+        if level >= self.stored_levels(pixels):
+            raise PbxError(E_BADARG, "level %d is derived: its rows are made on the GPU, not read" % level)
+        return self.inner.read_rows(pixels, z, c, t, level, y0, rows)
+
+    def band_chunks(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int, rows: int) -> Optional[dict]:
+        return self._stored("band_chunks", pixels, level, z, c, t, level, y0, rows)
+
+    def plane_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int) -> Optional[dict]:
+        return self._stored("plane_segments", pixels, level, z, c, t, level)
+
+    def band_segments(self, pixels: Pixels, z: int, c: int, t: int, level: int, y0: int, rows: int) -> Optional[dict]:
+        return self._stored("band_segments", pixels, level, z, c, t, level, y0, rows)
+
+
 # ----------------------------------------------------------------- TileRequestHandler
 
 class TileRequestHandler:
@@ -3230,6 +3430,12 @@ class TileRequestHandler:
 
     def _get_tile(self) -> Optional[bytes]:
         svc, tc = self.pixels_service, self.tile_ctx
+        if self.band is not None and tc.resolution is not None:
+            # a rank's share of the rows is a share of stored levels only, resident or not (the
+            # source remembers an image's level counts: no metadata lookup on a resident hit)
+            derived = getattr(self.source, "resolution_is_derived", None)
+            if derived is not None and derived(tc.imageId, tc.resolution):
+                raise PbxError(E_BADARG, "derived levels are not sharded by rows")
         status, body = self._serve()
         if status != E_NOT_RESIDENT or self.source is None:
             return self._answer(status, body)
